@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: FA2 + T5-bias forward+backward TFLOP/s (bf16, d_head = 64).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--seq 512] [--mode rpe|dense|none]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--seq 512] [--mode rpe|dense|none] [--dump-outputs DIR]
 
 A step = one forward + one backward of the attention hot path over one synthetic batch
 (B,H,S,D) = (4,12,S,64), bias = 32-bucket T5 relative-position bias, inputs resident in HBM, every kernel
@@ -13,6 +13,8 @@ either way the step ends with ONE all-reduce (RCCL over xGMI) of the (32,12) bia
 Prints ONE JSON line on rank 0 (see the repo task contract); extra keys: by_seq, kernels, roofline, cpu_baseline,
 eager_autograd (the drop-in autograd.Function path, no plan / graph), rowwise (RMSNorm, CE bandwidth), reference_shape
 (the reference's own published benchmark shape).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last step computed (o, dq, dk, dv and the bias(-table)
+gradient) as DIR/<name>.npy in float32; the inputs come from a fixed seed, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -27,7 +29,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
-PEAK_BF16_TFLOPS = 2500.0  # dense MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_BF16_TFLOPS = 2500.0  # dense MFMA peak of the MI355X
 PEAK_HBM_GBS = 8000.0
 B, H, D = 4, 12, 64
 NUM_BUCKETS, MAX_DISTANCE = 32, 128
@@ -54,6 +56,34 @@ def make_plan(S, mode, device, seed, units=None):
     plan = AttentionPlan(q, k, v, do, causal=False, sm_scale=0.125, units=units, **kw)
     idx = pe.bucket_index(MAX_DISTANCE, True, NUM_BUCKETS, MAX_DISTANCE, device)
     return plan, table, idx
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(arrays, path, limit_bytes=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: write each tensor of `arrays` (name -> tensor) as path/<name>.npy in float32, in its logical shape.  The
+    files hold at most `limit_bytes` in all: the budget is shared smallest tensor first, and a tensor larger than its share is
+    replaced by a fixed, seeded sample of its flattened elements (sorted flat indices drawn from `seed`, the same every run).
+    Returns what was written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach() for k, v in arrays.items() if v is not None}
+    left = (limit_bytes - 1024 * len(arrays)) // 4  # float32 elements (1 KB per file for the .npy header)
+    out = {}
+    for i, name in enumerate(sorted(arrays, key=lambda k_: arrays[k_].numel())):
+        t = arrays[name]
+        n, share = t.numel(), left // (len(arrays) - i)
+        if n <= share:
+            a, sampled = t.float().cpu().contiguous().numpy(), False
+        else:
+            g = torch.Generator().manual_seed(seed)
+            pick = torch.randint(0, n, (share,), generator=g).sort().values
+            a, sampled = t.reshape(-1).index_select(0, pick.to(t.device)).float().cpu().numpy(), True
+        left -= a.size
+        np.save(os.path.join(path, name + ".npy"), a)
+        out[name] = {"shape": list(t.shape), "saved": list(a.shape), "sampled": sampled}
+    return out
 
 
 def eager_autograd(S, device, iters=200):
@@ -696,7 +726,14 @@ def main():
                     "all-reduce per replay (what DDP's bucketing does with small gradients).  NOT the default: a data-parallel step cannot defer its gradient "
                     "past its own optimizer step, so the default N > 1 line runs exactly one all-reduce per step; with this flag the line also reports the per-step form")
     ap.add_argument("--no-extras", action="store_true", help="skip by_seq / cpu baseline (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (o, dq, dk, dv, bias(-table) gradient) as DIR/<name>.npy, "
+                    "float32, at most 64 MB in all (a fixed, seeded sample of each tensor beyond that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.scaling == "strong" and args.gpus > 1:
+        ap.error("--dump-outputs: with --scaling strong a rank computes only its share of the outputs")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: launch the N ranks ourselves, one process per GPU, exactly the way the driver's
@@ -946,6 +983,9 @@ def main():
                          "host_enqueue_ms_per_step": round(h1 / args.steps * 1e3, 5)}
         if want_reduce:
             per_step_form["allreduces_per_step"] = round(n1 / args.steps, 4)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before the extras below: they launch single stages of the same plan)
+        dumped = dump_outputs({"o": plan.o, "dq": plan.dq, "dk": plan.dk, "dv": plan.dv, "dbias": plan.dbias}, args.dump_outputs)
     ms_per_step = elapsed / args.steps * 1e3
     flops_step = 3.5 * fwd_flops(S) * (1 if strong else world)
     value = flops_step / (ms_per_step * 1e-3) / 1e12
@@ -989,6 +1029,8 @@ def main():
                 out["allreduce_in_graph_fallback"] = ar_fallback
         if per_step_form is not None:
             out["one_replay_per_step"] = per_step_form
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if ar_ms is not None:
             out["bias_grad_allreduce_ms"] = round(ar_ms, 4)
             if strong:

@@ -15,6 +15,8 @@ import os
 import sys
 
 os.environ.setdefault("TRITON_INTERPRET", "1")
+if "--portable" in sys.argv:  # one MKL code path (fp32 matmul bits) on every x86 CPU, as tests/conftest.py sets for the tests
+    os.environ["MKL_CBWR"] = "COMPATIBLE"
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference"
@@ -497,8 +499,60 @@ def gen_norm_linear():
     save("norm_linear", **out)
 
 
+# ----------------------------------------------------------------------------------------------
+# 7. the arrays the oracle tests compare bit for bit / to 1e-6, re-frozen so that every x86 host reproduces them
+# ----------------------------------------------------------------------------------------------
+def gen_portable():
+    """`python tests/golden/make_golden.py --portable` writes <name>.portable.npz next to the fixtures, laid over <name>.npz by
+    tests/golden_io.load.  The fixtures above hold fp32 CPU results in the bits of the generating host: MKL picks its matmul code
+    path by CPU, and torch's fp32 CPU sqrt (MKL vector math, 1 ulp) rounds differently on different CPU vendors.  Here
+    * attention o, L: the oracle on the stored inputs under MKL_CBWR=COMPATIBLE (set at the top of this script; tests/conftest.py
+      sets it for the tests), the MKL path that gives the same bits on every x86 CPU;
+    * AdamWScale fp32 parameters: the reference class and the oracle on the stored inputs with a correctly rounded fp32 sqrt
+      (golden_io.ieee_sqrt, which the test applies too), asserted equal bit for bit."""
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE"
+    sys.path.insert(0, os.path.dirname(HERE))
+    import golden_io
+    from src.utils.adamw_scaled import AdamWScale
+    for name in ["attn_cfg1_fp32"] + golden_io.ATTN_CASES:
+        c = golden_io.load_attn(name)
+        o, L = oracle.attn_fwd_oracle(c["q"], c["k"], c["v"], c["bias"], c["sm_scale"], c["causal"])
+        old = np.load(os.path.join(HERE, name + ".npz"))
+        assert maxdiff(o, torch.from_numpy(old["o"])) < 1e-5, name
+        if "o_ref" in old.files:
+            assert maxdiff(o, torch.from_numpy(old["o_ref"])) < 2e-5, name
+        np.savez_compressed(os.path.join(HERE, name + ".portable.npz"), o=npy(o), L=npy(L))
+    z = np.load(os.path.join(HERE, "adamw_scale.npz"))
+    out = {}
+    with golden_io.ieee_sqrt():
+        for name in ("fp32", "fp32_wd", "fp32_plain_wd"):
+            cfg = z[f"{name}__cfg"]
+            wd, correct = float(cfg[2]), bool(cfg[8])
+            assert int(cfg[0]) == 0 and int(cfg[7]) == -1 and not bool(cfg[1])
+            p0 = [torch.from_numpy(z[f"{name}__p0_{i}"]) for i in range(4)]
+            grads = [[torch.from_numpy(z[f"{name}__g{step}_{i}"]) for i in range(4)] for step in range(3)]
+            rp = [torch.nn.Parameter(t.clone()) for t in p0]
+            opt = AdamWScale(rp, lr=0.01, betas=(0.9, 0.999), eps=1e-6, weight_decay=wd, kahan_sum=False, foreach=False, correct_bias=correct)
+            mp, m, v = [t.clone() for t in p0], [torch.zeros_like(t) for t in p0], [torch.zeros_like(t) for t in p0]
+            for step in range(3):
+                for t, gr in zip(rp, grads[step]):
+                    t.grad = gr.clone()
+                opt.step()
+                for i in range(4):
+                    oracle.adamw_scale_step(mp[i], grads[step][i].clone(), m[i], v[i], None, step + 1, 0.01, 0.9, 0.999, wd, 1e-6, correct)
+            for i in range(4):
+                assert torch.equal(mp[i], rp[i].detach()), (name, i)
+                assert np.array_equal(m[i].numpy(), z[f"{name}__m_{i}"]) and np.array_equal(v[i].numpy(), z[f"{name}__v_{i}"]), (name, i)
+                out[f"{name}__p_{i}"] = npy(mp[i])
+    np.savez_compressed(os.path.join(HERE, "adamw_scale.portable.npz"), **out)
+    print("wrote", sorted(f for f in os.listdir(HERE) if f.endswith(".portable.npz")))
+
+
 def main():
     torch.set_num_threads(8)
+    if "--portable" in sys.argv:
+        gen_portable()
+        return
     only = set(sys.argv[sys.argv.index("--only") + 1].split(",")) if "--only" in sys.argv else None
     if only is not None:  # regenerate a subset: `--only adamw,triton3,mgtn,gated` (every generator is seeded: the others are unchanged)
         f16 = torch.float16

@@ -13,9 +13,36 @@ def _t(a, dtype=None):
     return torch.from_numpy(a.copy())
 
 
+class ieee_sqrt:
+    """`with ieee_sqrt():` -- fp32 CPU `Tensor.sqrt` correctly rounded (numpy's, the hardware instruction).  torch computes it
+    with MKL's vector math, accurate to 1 ulp and rounded differently on different CPU vendors; the fp32 AdamWScale parameters of
+    adamw_scale.portable.npz are frozen under this context (reference and oracle alike, tests/golden/make_golden.py --portable),
+    so their bits are the same on every host."""
+
+    def __enter__(self):
+        self.orig = orig = torch.Tensor.sqrt
+
+        def sqrt(t):
+            if t.dtype == torch.float32 and t.device.type == "cpu":
+                return torch.from_numpy(np.sqrt(t.detach().numpy()))
+            return orig(t)
+        torch.Tensor.sqrt = sqrt
+
+    def __exit__(self, *exc):
+        torch.Tensor.sqrt = self.orig
+        return False
+
+
 def load(name):
+    """<name>.npz, with the arrays of <name>.portable.npz laid over it when that file exists: the values the oracle tests compare
+    bit for bit / to 1e-6, re-frozen so that every x86 host reproduces them (tests/golden/make_golden.py --portable)."""
     z = np.load(os.path.join(GOLDEN, name + ".npz"))
-    return {k: z[k] for k in z.files}
+    out = {k: z[k] for k in z.files}
+    portable = os.path.join(GOLDEN, name + ".portable.npz")
+    if os.path.exists(portable):
+        p = np.load(portable)
+        out.update({k: p[k] for k in p.files})
+    return out
 
 
 def load_attn(name):

@@ -182,8 +182,15 @@ ADAMW_CASES = ["fp32", "fp32_wd", "bf16", "bf16_kahan_wd", "fp16_kahan", "fp32_s
 @pytest.mark.parametrize("name", ADAMW_CASES)
 def test_adamw_scale_golden(name):
     """the optimizer-step oracle reproduces, bit for bit, what the reference class `AdamWScale` produced on the same seeded tensors
-    (three steps; fixture written by tests/golden/make_golden.py gen_adamw, which also asserted it against the live class)"""
-    from golden_io import _t
+    (three steps; fixture written by tests/golden/make_golden.py gen_adamw, which also asserted it against the live class; the fp32
+    cases' parameters from adamw_scale.portable.npz, frozen with a correctly rounded fp32 sqrt on both sides, golden_io.ieee_sqrt,
+    so that the bits do not depend on the host CPU)"""
+    from golden_io import _t, ieee_sqrt
+    with ieee_sqrt():
+        _adamw_scale_golden(name, _t)
+
+
+def _adamw_scale_golden(name, _t):
     z = load("adamw_scale")
     cfg = z[f"{name}__cfg"]
     dtype = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[int(cfg[0])]
