@@ -44,12 +44,28 @@ class AttnParams(ctypes.Structure):
     ]
 
 
+c_i64x3x3 = c_i64x3 * 3
+
+
+class RopeParams(ctypes.Structure):
+    """Mirror of `fat5_rope_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("S", ctypes.c_int32), ("S_k", ctypes.c_int32), ("H", ctypes.c_int32), ("D", ctypes.c_int32),
+        ("rd", ctypes.c_int32), ("dtype", ctypes.c_int32), ("interleaved", ctypes.c_int32), ("conjugate", ctypes.c_int32),
+        ("n_tensors", ctypes.c_int32), ("n_q", ctypes.c_int32), ("table_rows", ctypes.c_int32),
+        ("cos", ctypes.c_void_p), ("sin", ctypes.c_void_p), ("cos_k", ctypes.c_void_p), ("sin_k", ctypes.c_void_p),
+        ("x", ctypes.c_void_p * 3), ("y", ctypes.c_void_p * 3), ("x_stride", c_i64x3x3), ("y_stride", c_i64x3x3),
+        ("cu_seqlens", ctypes.c_void_p), ("cu_seqlens_k", ctypes.c_void_p),
+    ]
+
+
 EXPORTS = (
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
     "fat5_rmsnorm_fwd", "fat5_rmsnorm_bwd_workspace_bytes", "fat5_rmsnorm_bwd", "fat5_add_rmsnorm_fwd", "fat5_add_rmsnorm_bwd",
     "fat5_ce_fwd", "fat5_ce_bwd", "fat5_ce_fwd_bwd", "fat5_fold_weights", "fat5_fold_weights_bwd", "fat5_fold_weights_bwd_scratch_bytes", "fat5_rmsnorm_unit_bwd", "fat5_gated_act_fwd", "fat5_gated_act_bwd",
     "fat5_adamw_scale_step", "fat5_adamw_scale_step_clipped", "fat5_adamw_scale_step_dev", "fat5_adamw_grad_sumsq", "fat5_sizeof_adamw_tensor",
+    "fat5_rope_apply", "fat5_sizeof_rope_params",
 )
 
 _lib = None
@@ -121,6 +137,12 @@ def load():
     lib.fat5_adamw_grad_sumsq.restype = ctypes.c_int
     lib.fat5_adamw_grad_sumsq.argtypes = [vp, i32, i32, vp, i32, vp]
     lib.fat5_sizeof_adamw_tensor.restype = ctypes.c_size_t
+    lib.fat5_rope_apply.restype = ctypes.c_int
+    lib.fat5_rope_apply.argtypes = [ctypes.POINTER(RopeParams), ctypes.c_void_p]
+    lib.fat5_sizeof_rope_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_rope_params() != ctypes.sizeof(RopeParams):
+        raise ImportError(f"fat5_rope_params layout mismatch: library {lib.fat5_sizeof_rope_params()} B, "
+                          f"binding {ctypes.sizeof(RopeParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

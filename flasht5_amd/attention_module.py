@@ -12,8 +12,12 @@ the following blocks.  Two attention types:
                   once by block 0 and consumed in-kernel by every block (`flash_attention_v2_rpe1d`); nothing of size
                   S x S is allocated in either direction (the role of the reference's external "fa2_rpe" type, :272-279).
 
-Only the T5 relative-position producer lives here; other producers' dense outputs (ALiBi, FIRE, ...) can be passed as
-`position_bias`.  Dropout is not supported (like the reference's Triton path, :201)."""
+`position_encoding_type="RoPE"` (config keys `rotary_emb_fraction`, `rotary_base`, `rotary_interleaved`, `rotary_scale_base`,
+`max_sequence_length`) builds a `RotaryPositionalEncoding` in EVERY layer, cross-attention included, as the reference does
+(:214-220 carry no `has_positional_encoding` condition): q, k and v are rotated (v too, like the reference) in one kernel launch
+and the attention runs without a bias.  As in the reference (:259), a layer handed a `position_bias` uses that bias and
+does not rotate.  Only the T5 and RoPE producers live here; other producers' dense outputs (ALiBi, FIRE,
+...) can be passed as `position_bias`.  Dropout is not supported (like the reference's Triton path, :201)."""
 import math
 
 import torch
@@ -21,6 +25,7 @@ from torch import nn
 
 from .flash_attention_v2_bias import flash_attention_v2_bias, flash_attention_v2_rpe1d
 from .positional_encoding import RelativePositionalEncoding
+from .rotary import RotaryPositionalEncoding, apply_rotary_emb_packed
 
 
 def _cfg(config, name, default):
@@ -88,16 +93,22 @@ class FlashT5Attention(nn.Module):
             raise ValueError(f"attention_type {self.attention_type!r}: this module implements 'triton' (dense bias) and 'fat5_rpe'")
         if _cfg(config, "attention_dropout_rate", 0.0) != 0.0:
             raise ValueError("attention dropout is not supported by the fused kernels")
-        if self.attention_type == "fat5_rpe" and (self.position_encoding_type != "t5" or self.use_masking):
-            raise ValueError("fat5_rpe needs the T5 relative-position encoding and no key masking (use var-len batches)")
+        if self.attention_type == "fat5_rpe" and (self.position_encoding_type not in ("t5", "RoPE") or self.use_masking):
+            raise ValueError("fat5_rpe needs the T5 relative-position encoding or RoPE, and no key masking (use var-len batches)")
         self.pe_encoding = None
-        if self.position_encoding_type == "t5" and has_positional_encoding:
+        self.rotary = self.position_encoding_type == "RoPE"
+        if self.rotary:  # (every layer: the reference's RoPE branch has no has_positional_encoding condition, :214)
+            self.pe_encoding = RotaryPositionalEncoding(
+                int(self.key_value_proj_dim * _cfg(config, "rotary_emb_fraction", 1.0)), _cfg(config, "max_sequence_length", 1024),
+                _cfg(config, "rotary_base", 10000), _cfg(config, "rotary_interleaved", False), _cfg(config, "rotary_scale_base", None),
+                randomized_position=_cfg(config, "use_randomized_position_encoding", False))
+        elif self.position_encoding_type == "t5" and has_positional_encoding:
             self.pe_encoding = RelativePositionalEncoding(
                 config.relative_attention_num_buckets, config.relative_attention_max_distance, self.n_heads,
                 _cfg(config, "max_sequence_length", 0), bidirectional=not self.is_decoder,
                 randomized_position=_cfg(config, "use_randomized_position_encoding", False))
         elif self.position_encoding_type != "t5" and has_positional_encoding:
-            raise ValueError("only the T5 producer is built in; pass other encodings' dense bias as position_bias")
+            raise ValueError("only the T5 and RoPE producers are built in; pass other encodings' dense bias as position_bias")
         self.Wq = nn.Linear(self.d_model, self.inner_dim, bias=False)
         self.Wk = nn.Linear(self.d_model, self.inner_dim, bias=False)
         self.Wv = nn.Linear(self.d_model, self.inner_dim, bias=False)
@@ -108,9 +119,12 @@ class FlashT5Attention(nn.Module):
         src = hidden_states if key_value_states is None else key_value_states
         N = src.shape[1]
         # (B, S, H, D) storage viewed as (B, H, S, D): the kernels take the strided views as they are
-        q = self.Wq(hidden_states).view(B, M, self.n_heads, self.key_value_proj_dim).permute(0, 2, 1, 3)
-        k = self.Wk(src).view(B, N, self.n_heads, self.key_value_proj_dim).permute(0, 2, 1, 3)
-        v = self.Wv(src).view(B, N, self.n_heads, self.key_value_proj_dim).permute(0, 2, 1, 3)
+        q = self.Wq(hidden_states).view(B, M, self.n_heads, self.key_value_proj_dim)
+        k = self.Wk(src).view(B, N, self.n_heads, self.key_value_proj_dim)
+        v = self.Wv(src).view(B, N, self.n_heads, self.key_value_proj_dim)
+        if self.rotary and position_bias is None:  # q, k, v in one launch (new tensors: nothing autograd saved is touched)
+            q, k, v, _ = self.pe_encoding(q, k, v)
+        q, k, v = q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3)
         out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias)
         return self.o(out), position_bias
 
@@ -124,19 +138,29 @@ class FlashT5Attention(nn.Module):
         H, Dh = self.n_heads, self.key_value_proj_dim
         if key_value_states is None:  # self-attention: ONE GEMM for q, k, v
             qkv, res = rmsnorm_linear(hidden_states, norm_weight, (self.Wq.weight, self.Wk.weight, self.Wv.weight), eps, return_residual=True)
+            if self.rotary and position_bias is None:  # the packed buffer in, a packed buffer out (and its gradient packed again): one launch each way
+                (qkv,) = apply_rotary_emb_packed((qkv,), (3,), H, *self._rotary_tables(qkv), nq=1, interleaved=self.pe_encoding.interleaved)
             q, k, v = unpack_heads(qkv, 3, H)
         else:                         # cross-attention: the decoder side is normed, the encoder output is not (:330-336)
-            N = key_value_states.shape[1]
             q, res = rmsnorm_linear(hidden_states, norm_weight, self.Wq.weight, eps, return_residual=True)
+            kv = torch.nn.functional.linear(key_value_states, torch.cat((self.Wk.weight, self.Wv.weight), 0))
+            if self.rotary and position_bias is None:  # q and the packed k | v in one launch
+                q, kv = apply_rotary_emb_packed((q, kv), (1, 2), H, *self._rotary_tables(q), nq=1, interleaved=self.pe_encoding.interleaved)
             q = q.view(B, M, H, Dh).permute(0, 2, 1, 3)
-            k, v = unpack_heads(torch.nn.functional.linear(key_value_states, torch.cat((self.Wk.weight, self.Wv.weight), 0)), 2, H)
+            k, v = unpack_heads(kv, 2, H)
         out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias)
         return linear_residual(out, self.o.weight, res), position_bias
+
+    def _rotary_tables(self, x):
+        return self.pe_encoding.tables(x.device, x.dtype)
 
     def _attend(self, q, k, v, dtype, mask, is_self, position_bias):
         """attention of projected (B, H, S, D) views -> (B, M, inner_dim), plus the position bias to hand on"""
         B, _, M, _ = q.shape
         N = k.shape[2]
+        if self.rotary and position_bias is None:  # (q, k, v already rotated: no bias, and none handed on)
+            out = flash_attention_v2_bias(q, k, v, None, self.is_causal, self.softmax_scale)
+            return out.permute(0, 2, 1, 3).reshape(B, M, self.inner_dim), None
         key_value_states = None if is_self else True
         hidden_dtype = dtype
         if self.attention_type == "fat5_rpe":

@@ -16,6 +16,7 @@
 #include "rowwise_kernels.h"
 #include "adamw_kernels.h"
 #include "fold_weights.h"
+#include "rope_kernels.h"
 
 using namespace fat5;
 
@@ -1212,6 +1213,85 @@ int fat5_gated_act_bwd(const void* dout, const void* h0, const void* h1, void* d
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "gated_act_bwd launch");
+  return FAT5_OK;
+}
+
+// ---- rotary position embedding (rope_kernels.h) ----
+size_t fat5_sizeof_rope_params(void) { return sizeof(fat5_rope_params); }
+
+int fat5_rope_apply(const fat5_rope_params* p, void* stream_) {
+  if (!p) return fail(FAT5_EINVAL, "rope: null params");
+  if (!dtype_ok(p->dtype)) return fail(FAT5_EINVAL, "rope: unsupported dtype %d", p->dtype);
+  if (p->D != 16 && p->D != 32 && p->D != 64 && p->D != 128) return fail(FAT5_EINVAL, "rope: head_dim %d (16, 32, 64 or 128)", p->D);
+  if (p->rd <= 0 || p->rd % 2 || p->rd > p->D) return fail(FAT5_EINVAL, "rope: rd %d must be even and in [2, head_dim %d]", p->rd, p->D);
+  if (p->n_tensors < 1 || p->n_tensors > 3 || p->n_q < 0 || p->n_q > p->n_tensors)
+    return fail(FAT5_EINVAL, "rope: n_tensors %d / n_q %d", p->n_tensors, p->n_q);
+  const int Sk = p->S_k ? p->S_k : p->S;
+  if (p->B < 0 || p->S < 0 || Sk < 0 || p->H < 1) return fail(FAT5_EINVAL, "rope: bad shape B %d S %d S_k %d H %d", p->B, p->S, Sk, p->H);
+  const bool use_q = p->n_q > 0, use_k = p->n_q < p->n_tensors;
+  const int Smax = std::max(use_q ? p->S : 0, use_k ? Sk : 0);
+  if (Smax > p->table_rows)
+    return fail(FAT5_EINVAL, "rope: positions up to %d beyond the table's %d rows", Smax - 1, p->table_rows);
+  if ((use_q || !p->cos_k) && (!p->cos || !p->sin)) return fail(FAT5_EINVAL, "rope: null cos / sin table");
+  if (use_k && ((p->cos_k == nullptr) != (p->sin_k == nullptr))) return fail(FAT5_EINVAL, "rope: cos_k and sin_k go together");
+  const int v = vec_of(p->dtype);
+  const bool vl = p->cu_seqlens != nullptr;
+  if (!vl && p->cu_seqlens_k) return fail(FAT5_EINVAL, "rope: cu_seqlens_k without cu_seqlens");
+  for (int i = 0; i < p->n_tensors; ++i) {
+    if (!p->x[i] || !p->y[i] || !aligned16(p->x[i]) || !aligned16(p->y[i]))
+      return fail(FAT5_EINVAL, "rope: tensor %d: null or unaligned pointer (16-byte aligned bases)", i);
+    for (int d = vl ? 1 : 0; d < 3; ++d)
+      if (p->x_stride[i][d] % v || p->y_stride[i][d] % v)
+        return fail(FAT5_EINVAL, "rope: tensor %d: strides must be multiples of %d elements", i, v);
+  }
+  if (p->B == 0 || Smax == 0) return FAT5_OK;
+
+  RopeArgs a = {};
+  for (int i = 0; i < 3; ++i) {
+    const int j = i < p->n_tensors ? i : 0;  // (unused slots repeat tensor 0: never addressed)
+    a.x[i] = p->x[j];
+    a.y[i] = p->y[j];
+    for (int d = 0; d < 3; ++d) {
+      a.xs[i][d] = p->x_stride[j][d];
+      a.ys[i][d] = p->y_stride[j][d];
+    }
+  }
+  a.tab[0] = p->cos ? p->cos : p->cos_k;
+  a.tab[1] = p->sin ? p->sin : p->sin_k;
+  a.tab[2] = p->cos_k ? p->cos_k : a.tab[0];
+  a.tab[3] = p->sin_k ? p->sin_k : a.tab[1];
+  a.cu[0] = p->cu_seqlens;
+  a.cu[1] = p->cu_seqlens_k ? p->cu_seqlens_k : p->cu_seqlens;
+  a.S[0] = use_q ? p->S : 0;
+  a.S[1] = use_k ? Sk : 0;
+  a.nt = p->n_tensors;
+  a.nq = p->n_q;
+  a.H = p->H;
+  a.D = p->D;
+  a.rd = p->rd;
+  a.rows = p->table_rows;
+  a.sgn = p->conjugate ? -1.f : 1.f;
+  const int h = p->rd / 2;
+  const int mode = p->interleaved ? ROPE_INTERLEAVED : (h % v == 0 ? ROPE_PAIR : ROPE_SCALAR);
+  a.ipr = mode == ROPE_PAIR ? h / v + (p->D - p->rd) / v : mode == ROPE_INTERLEAVED ? p->D / v : h + p->D - p->rd;
+  const long per_t = (long)a.nt * a.H * a.ipr;
+  if (per_t * ROPE_MAX_T > 0x7fffffffL) return fail(FAT5_EINVAL, "rope: %d heads is too many", p->H);
+  a.T = (int)std::max(1L, std::min<long>(ROPE_MAX_T, ROPE_THREADS * ROPE_KMAX / per_t));
+  a.nsb = (Smax + a.T - 1) / a.T;
+  const long grid = (long)p->B * a.nsb;
+  if (grid > 0x7fffffffL) return fail(FAT5_EINVAL, "rope: grid of %ld workgroups", grid);
+  hipStream_t stream = (hipStream_t)stream_;
+  dispatch_dtype(p->dtype, [&](auto dt_) {
+    constexpr int DT = decltype(dt_)::value;
+    if (mode == ROPE_PAIR)
+      hipLaunchKernelGGL((rope_kernel<DT, ROPE_PAIR>), dim3((unsigned)grid), dim3(ROPE_THREADS), 0, stream, a);
+    else if (mode == ROPE_INTERLEAVED)
+      hipLaunchKernelGGL((rope_kernel<DT, ROPE_INTERLEAVED>), dim3((unsigned)grid), dim3(ROPE_THREADS), 0, stream, a);
+    else
+      hipLaunchKernelGGL((rope_kernel<DT, ROPE_SCALAR>), dim3((unsigned)grid), dim3(ROPE_THREADS), 0, stream, a);
+  });
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "rope launch");
   return FAT5_OK;
 }
 

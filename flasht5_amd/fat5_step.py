@@ -17,6 +17,7 @@ exchange (RCCL over xGMI): a single flat fp32 all-reduce that carries the two `(
 """
 import math
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.distributed as dist
@@ -44,7 +45,11 @@ class FAT5Config:
     label_smoothing: float = 0.1
     attention_scale: float = 1.0
     attention_type: str = "fat5_rpe"      # "fat5_rpe": O(S) bias memory; "triton": the reference's dense-bias operator
-    position_encoding_type: str = "t5"
+    position_encoding_type: str = "t5"      # "t5" or "RoPE" (rotary, in every attention layer; no bias)
+    rotary_emb_fraction: float = 1.0       # RoPE: rotated share of d_kv
+    rotary_base: float = 10000.0
+    rotary_interleaved: bool = False
+    rotary_scale_base: Optional[float] = None  # xPos when set
     use_glu_mlp: bool = True
     use_gelu_act: bool = True
     decoder_start_token_id: int = 0
@@ -255,7 +260,7 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward onl
                 m.Wk.weight.normal_(0.0, c.d_model ** -0.5)
                 m.Wv.weight.normal_(0.0, c.d_model ** -0.5)
                 m.o.weight.normal_(0.0, (c.num_heads * c.d_kv) ** -0.5)
-                if m.pe_encoding is not None:
+                if m.pe_encoding is not None and hasattr(m.pe_encoding, "relative_attention_bias"):  # (RoPE has no table)
                     m.pe_encoding.relative_attention_bias.weight.normal_(0.0, c.d_model ** -0.5)
 
     def _shift_right(self, labels):  # HF T5 convention used by the reference (:713-714)
@@ -266,7 +271,9 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward onl
         return shifted.masked_fill(shifted == -100, c.pad_token_id)
 
     def rpe_tables(self):
-        """the two (num_buckets, H) relative-position tables (encoder, decoder): the bias gradients of the step"""
+        """the two (num_buckets, H) relative-position tables (encoder, decoder): the bias gradients of the step; none with RoPE"""
+        if self.config.position_encoding_type == "RoPE":
+            return []
         return [self.encoder.block[0].self_attention_layer.self_attention.pe_encoding.relative_attention_bias.weight,
                 self.decoder.block[0].self_attention_layer.self_attention.pe_encoding.relative_attention_bias.weight]
 

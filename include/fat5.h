@@ -244,6 +244,49 @@ int fat5_gated_act_bwd(const void* dout, const void* h0, const void* h1, void* d
                        int64_t dh1_row_stride, int act, int dtype, void* hip_stream);
 
 /*
+ * Rotary position embedding (RoPE) of q, k and v in ONE launch.  Replaces flash_attn.layers.rotary.apply_rotary_emb, the external
+ * package the reference's RotaryPositionalEncoding calls (src/utils/positional_encoding.py:5-8, :297-338); the tables are built by
+ * the caller (they depend on the dtype's rounding of the positions, :262-263).  With h = rd / 2 and p the position of a token in its
+ * own sequence:
+ *   y[j] = x[j] cos[p][j] - x[j+h] sin[p][j],   y[j+h] = x[j] sin[p][j] + x[j+h] cos[p][j]   (j < h)
+ * or, interleaved, the same on the pairs (2j, 2j+1); columns >= rd are copied bit for bit.  fp32 arithmetic on the table values as
+ * stored, each product rounded separately, one rounding per output element.  conjugate != 0: sin -> -sin (the backward).
+ * Tensors [0, n_q) rotate with (cos, sin), tensors [n_q, n_tensors) with (cos_k, sin_k) -- q, then k and v (the reference rotates v
+ * too, :331-336).  Each x[i] is a (B, S, H, D) view with element strides x_stride[i] = [b, s, h] (inner stride 1), or with
+ * cu_seqlens the packed (total, H, D) layout of fat5_attn_params: token s of sequence b at (cu_seqlens[b] + s) * stride[1]
+ * (stride[0] ignored; S is then the maximum length and no sequence may be longer).  y[i] has x[i]'s geometry; y[i] == x[i] is
+ * allowed (in place).  Bases 16-byte aligned, strides multiples of the 16-byte vector (8 elements; 4 for fp32).
+ * Rejected with FAT5_EINVAL before anything is launched: odd, zero or oversized rd, positions beyond table_rows, null or
+ * misaligned pointers, dtype outside {FAT5_F32, FAT5_F16, FAT5_BF16}, D outside {16, 32, 64, 128}.
+ */
+typedef struct fat5_rope_params {
+  int32_t B;                /* batch (number of sequences with cu_seqlens) */
+  int32_t S;                /* sequence length of tensors [0, n_q) (maximum length with cu_seqlens) */
+  int32_t S_k;              /* the same for tensors [n_q, n_tensors) (cross-attention: keys); 0 = S */
+  int32_t H, D;             /* heads, head_dim in {16, 32, 64, 128} */
+  int32_t rd;               /* rotated columns: even, 2 <= rd <= D (flash_attn: 2 * cos.shape[-1]) */
+  int32_t dtype;            /* of x, y and the tables */
+  int32_t interleaved;
+  int32_t conjugate;
+  int32_t n_tensors;        /* 1..3 */
+  int32_t n_q;              /* 0..n_tensors */
+  int32_t table_rows;       /* rows of every table: each position must be < table_rows */
+  const void* cos;          /* (table_rows, rd / 2) contiguous */
+  const void* sin;
+  const void* cos_k;        /* NULL: cos (no xPos) */
+  const void* sin_k;        /* NULL: sin */
+  const void* x[3];
+  void* y[3];
+  int64_t x_stride[3][3];
+  int64_t y_stride[3][3];
+  const int32_t* cu_seqlens;   /* (B + 1,) int32 device array, or NULL: the dense (B, S, H, D) layout */
+  const int32_t* cu_seqlens_k; /* for tensors [n_q, n_tensors); NULL = cu_seqlens */
+} fat5_rope_params;
+/* sizeof(fat5_rope_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_rope_params(void);
+int fat5_rope_apply(const fat5_rope_params* p, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)
