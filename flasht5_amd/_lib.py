@@ -58,6 +58,18 @@ class RopeParams(ctypes.Structure):
         ("cu_seqlens", ctypes.c_void_p), ("cu_seqlens_k", ctypes.c_void_p),
     ]
 
+class FireParams(ctypes.Structure):
+    """Mirror of `fat5_fire_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("M", ctypes.c_int64), ("N", ctypes.c_int64), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("eps", ctypes.c_float),
+        ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+        ("c", ctypes.c_void_p), ("L_multiplier", ctypes.c_void_p), ("init_L", ctypes.c_void_p),
+        ("bias", ctypes.c_void_p), ("dbias", ctypes.c_void_p), ("bias_stride", ctypes.c_int64 * 2),
+        ("dw1", ctypes.c_void_p), ("db1", ctypes.c_void_p), ("dw2", ctypes.c_void_p), ("db2", ctypes.c_void_p),
+        ("dc", ctypes.c_void_p), ("dL_multiplier", ctypes.c_void_p),
+    ]
+
 
 EXPORTS = (
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
@@ -66,6 +78,7 @@ EXPORTS = (
     "fat5_ce_fwd", "fat5_ce_bwd", "fat5_ce_fwd_bwd", "fat5_fold_weights", "fat5_fold_weights_bwd", "fat5_fold_weights_bwd_scratch_bytes", "fat5_rmsnorm_unit_bwd", "fat5_gated_act_fwd", "fat5_gated_act_bwd",
     "fat5_adamw_scale_step", "fat5_adamw_scale_step_clipped", "fat5_adamw_scale_step_dev", "fat5_adamw_grad_sumsq", "fat5_sizeof_adamw_tensor",
     "fat5_rope_apply", "fat5_sizeof_rope_params",
+    "fat5_fire_fwd", "fat5_fire_bwd", "fat5_fire_bwd_workspace_bytes", "fat5_sizeof_fire_params",
 )
 
 _lib = None
@@ -143,6 +156,16 @@ def load():
     if lib.fat5_sizeof_rope_params() != ctypes.sizeof(RopeParams):
         raise ImportError(f"fat5_rope_params layout mismatch: library {lib.fat5_sizeof_rope_params()} B, "
                           f"binding {ctypes.sizeof(RopeParams)} B")
+    lib.fat5_fire_fwd.restype = ctypes.c_int
+    lib.fat5_fire_fwd.argtypes = [ctypes.POINTER(FireParams), ctypes.c_void_p]
+    lib.fat5_fire_bwd.restype = ctypes.c_int
+    lib.fat5_fire_bwd.argtypes = [ctypes.POINTER(FireParams), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.fat5_fire_bwd_workspace_bytes.restype = ctypes.c_size_t
+    lib.fat5_fire_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FireParams)]
+    lib.fat5_sizeof_fire_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_fire_params() != ctypes.sizeof(FireParams):
+        raise ImportError(f"fat5_fire_params layout mismatch: library {lib.fat5_sizeof_fire_params()} B, "
+                          f"binding {ctypes.sizeof(FireParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

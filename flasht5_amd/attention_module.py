@@ -16,14 +16,21 @@ the following blocks.  Two attention types:
 `max_sequence_length`) builds a `RotaryPositionalEncoding` in EVERY layer, cross-attention included, as the reference does
 (:214-220 carry no `has_positional_encoding` condition): q, k and v are rotated (v too, like the reference) in one kernel launch
 and the attention runs without a bias.  As in the reference (:259), a layer handed a `position_bias` uses that bias and
-does not rotate.  Only the T5 and RoPE producers live here; other producers' dense outputs (ALiBi, FIRE,
-...) can be passed as `position_bias`.  Dropout is not supported (like the reference's Triton path, :201)."""
+does not rotate.
+
+`position_encoding_type="FIRE"` (config key `fire_mlp_width`, default 32) builds, in the layer that owns the position encoding
+(block 0's self-attention, as in the reference, :221-225), `FIRE(n_heads, fire_mlp_width, 0.1, relative_attention_max_distance)`:
+its (1, H, S, S) bias comes from one HIP kernel (flasht5_amd/fire.py) and is handed on to the following blocks like the T5 bias,
+with `use_full_bias_size` and `use_masking` applied the same way.  FIRE needs the dense-bias type ("triton"): its bias is not
+Toeplitz once a row passes the threshold T, so `fat5_rpe` cannot carry it.  Other producers' dense outputs (ALiBi, ...) can be
+passed as `position_bias`.  Dropout is not supported (like the reference's Triton path, :201)."""
 import math
 
 import torch
 from torch import nn
 
 from .flash_attention_v2_bias import flash_attention_v2_bias, flash_attention_v2_rpe1d
+from .fire import FIRE
 from .positional_encoding import RelativePositionalEncoding
 from .rotary import RotaryPositionalEncoding, apply_rotary_emb_packed
 
@@ -93,6 +100,9 @@ class FlashT5Attention(nn.Module):
             raise ValueError(f"attention_type {self.attention_type!r}: this module implements 'triton' (dense bias) and 'fat5_rpe'")
         if _cfg(config, "attention_dropout_rate", 0.0) != 0.0:
             raise ValueError("attention dropout is not supported by the fused kernels")
+        if self.attention_type == "fat5_rpe" and self.position_encoding_type == "FIRE":
+            raise ValueError("FIRE needs attention_type='triton' (dense bias): its bias is not Toeplitz once a row passes the "
+                             "threshold T, so fat5_rpe cannot carry it")
         if self.attention_type == "fat5_rpe" and (self.position_encoding_type not in ("t5", "RoPE") or self.use_masking):
             raise ValueError("fat5_rpe needs the T5 relative-position encoding or RoPE, and no key masking (use var-len batches)")
         self.pe_encoding = None
@@ -107,8 +117,11 @@ class FlashT5Attention(nn.Module):
                 config.relative_attention_num_buckets, config.relative_attention_max_distance, self.n_heads,
                 _cfg(config, "max_sequence_length", 0), bidirectional=not self.is_decoder,
                 randomized_position=_cfg(config, "use_randomized_position_encoding", False))
+        elif self.position_encoding_type == "FIRE" and has_positional_encoding:
+            self.pe_encoding = FIRE(num_heads=self.n_heads, mlp_width=_cfg(config, "fire_mlp_width", 32), init_c=0.1,
+                                    init_L=config.relative_attention_max_distance)
         elif self.position_encoding_type != "t5" and has_positional_encoding:
-            raise ValueError("only the T5 and RoPE producers are built in; pass other encodings' dense bias as position_bias")
+            raise ValueError("only the T5, RoPE and FIRE producers are built in; pass other encodings' dense bias as position_bias")
         self.Wq = nn.Linear(self.d_model, self.inner_dim, bias=False)
         self.Wk = nn.Linear(self.d_model, self.inner_dim, bias=False)
         self.Wv = nn.Linear(self.d_model, self.inner_dim, bias=False)
@@ -178,7 +191,10 @@ class FlashT5Attention(nn.Module):
                 rpe1d, radius = position_bias
                 out = flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, self.is_causal, self.softmax_scale)
         else:
-            if position_bias is None and self.pe_encoding is not None:
+            if position_bias is None and isinstance(self.pe_encoding, FIRE):  # (the reference's FIRE.forward: (1, H, S, S), S = M)
+                # (no .contiguous(): when S is not a multiple of 8 the bias rows are padded to 16 bytes, which the kernels take as is)
+                position_bias = self.pe_encoding.compute_bias(M, M, q.device, q.dtype)
+            elif position_bias is None and self.pe_encoding is not None:
                 position_bias = self.pe_encoding.compute_bias(M, N, device=q.device).contiguous().to(q.dtype)
             bias = position_bias
             if bias is not None and self.use_full_bias_size:

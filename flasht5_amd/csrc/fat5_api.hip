@@ -17,6 +17,7 @@
 #include "adamw_kernels.h"
 #include "fold_weights.h"
 #include "rope_kernels.h"
+#include "fire_kernels.h"
 
 using namespace fat5;
 
@@ -1292,6 +1293,144 @@ int fat5_rope_apply(const fat5_rope_params* p, void* stream_) {
   });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "rope launch");
+  return FAT5_OK;
+}
+
+// ---- FIRE position bias (fire_kernels.h) ----
+size_t fat5_sizeof_fire_params(void) { return sizeof(fat5_fire_params); }
+
+static int fire_check(const fat5_fire_params* p, const char* what, bool bwd) {
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (!dtype_ok(p->dtype)) return fail(FAT5_EINVAL, "%s: unsupported dtype %d", what, p->dtype);
+  if (p->H < 1 || p->H > FIRE_MAX_H) return fail(FAT5_EINVAL, "%s: %d heads (1 to %d)", what, p->H, FIRE_MAX_H);
+  if (p->W < 1 || p->W > FIRE_MAX_W) return fail(FAT5_EINVAL, "%s: MLP width %d (1 to %d)", what, p->W, FIRE_MAX_W);
+  constexpr int64_t kMaxLen = 0x7fffffffL - 1024;
+  if (p->M < 0 || p->N < 0 || p->M > kMaxLen || p->N > kMaxLen)
+    return fail(FAT5_EINVAL, "%s: M %lld / N %lld outside [0, %lld]", what, (long long)p->M, (long long)p->N, (long long)kMaxLen);
+  if (!(p->eps >= 0.f) || !std::isfinite(p->eps)) return fail(FAT5_EINVAL, "%s: eps must be finite and >= 0", what);
+  const void* ptrs[7] = {p->w1, p->b1, p->w2, p->b2, p->c, p->L_multiplier, p->init_L};
+  for (int i = 0; i < 7; ++i)
+    if (!ptrs[i] || (reinterpret_cast<uintptr_t>(ptrs[i]) & 3)) return fail(FAT5_EINVAL, "%s: parameter %d: null or misaligned pointer", what, i);
+  const void* b = bwd ? p->dbias : p->bias;
+  if (!b || !aligned16(b)) return fail(FAT5_EINVAL, "%s: %s: null or unaligned pointer (16-byte aligned base)", what, bwd ? "dbias" : "bias");
+  const int v = vec_of(p->dtype);
+  if (p->bias_stride[0] % v || p->bias_stride[1] % v)
+    return fail(FAT5_EINVAL, "%s: bias strides must be multiples of %d elements", what, v);
+  if (p->M > 0 && p->N > 0 &&
+      (p->bias_stride[1] < p->N || p->bias_stride[0] < 0 || (p->H > 1 && p->bias_stride[0] < p->bias_stride[1] * p->M)))
+    return fail(FAT5_EINVAL, "%s: bias strides [%lld, %lld] overlap an (H, M, N) = (%d, %lld, %lld) tensor", what,
+                (long long)p->bias_stride[0], (long long)p->bias_stride[1], p->H, (long long)p->M, (long long)p->N);
+  if (bwd) {
+    const float* outs[6] = {p->dw1, p->db1, p->dw2, p->db2, p->dc, p->dL_multiplier};
+    for (int i = 0; i < 6; ++i)
+      if (!outs[i] || (reinterpret_cast<uintptr_t>(outs[i]) & 3)) return fail(FAT5_EINVAL, "%s: gradient %d: null or misaligned pointer", what, i);
+  }
+  return FAT5_OK;
+}
+
+static FireArgs fire_args(const fat5_fire_params* p) {
+  FireArgs a = {};
+  a.w1 = p->w1;
+  a.b1 = p->b1;
+  a.w2 = p->w2;
+  a.b2 = p->b2;
+  a.c = p->c;
+  a.lm = p->L_multiplier;
+  a.l0 = p->init_L;
+  a.out = p->bias;
+  a.dout = p->dbias;
+  a.M = p->M;
+  a.N = p->N;
+  a.sh = p->bias_stride[0];
+  a.sm = p->bias_stride[1];
+  a.H = p->H;
+  a.W = p->W;
+  a.eps = p->eps;
+  a.dw1 = p->dw1;
+  a.db1 = p->db1;
+  a.dw2 = p->dw2;
+  a.db2 = p->db2;
+  a.dc = p->dc;
+  a.dlm = p->dL_multiplier;
+  return a;
+}
+
+static int fire_nwg(const fat5_fire_params* p) {
+  const int64_t tiles = (p->M * p->N + FIRE_TILE - 1) / FIRE_TILE;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, FIRE_MAX_WG));
+}
+static int fire_nout(const fat5_fire_params* p) { return p->H * p->W + 2 * p->W + p->H + 2; }
+
+int fat5_fire_fwd(const fat5_fire_params* p, void* stream_) {
+  if (int rc = fire_check(p, "fire_fwd", false)) return rc;
+  if (p->M == 0 || p->N == 0) return FAT5_OK;
+  FireArgs a = fire_args(p);
+  const int64_t span = (int64_t)FIRE_THREADS * vec_of(p->dtype);
+  const int64_t grid = p->M * ((p->N + span - 1) / span);
+  if (grid > 0x7fffffffL) return fail(FAT5_EINVAL, "fire_fwd: grid of %lld workgroups", (long long)grid);
+  // heads per accumulation pass: the fewest (hidden recomputations + padded heads) -- 12 heads in one pass of 12
+  int hc = 16;
+  long best = -1;
+  for (int c : {4, 8, 12, 16}) {
+    const long passes = (p->H + c - 1) / c, cost = passes * (c * (long)p->W + 2L * p->W);
+    if (best < 0 || cost < best) best = cost, hc = c;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  dispatch_dtype(p->dtype, [&](auto dt_) {
+    constexpr int DT = decltype(dt_)::value;
+    switch (hc) {
+      case 4: hipLaunchKernelGGL((fire_fwd_kernel<DT, 4>), dim3((unsigned)grid), dim3(FIRE_THREADS), 0, stream, a); break;
+      case 8: hipLaunchKernelGGL((fire_fwd_kernel<DT, 8>), dim3((unsigned)grid), dim3(FIRE_THREADS), 0, stream, a); break;
+      case 12: hipLaunchKernelGGL((fire_fwd_kernel<DT, 12>), dim3((unsigned)grid), dim3(FIRE_THREADS), 0, stream, a); break;
+      default: hipLaunchKernelGGL((fire_fwd_kernel<DT, 16>), dim3((unsigned)grid), dim3(FIRE_THREADS), 0, stream, a); break;
+    }
+  });
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "fire_fwd launch");
+  return FAT5_OK;
+}
+
+size_t fat5_fire_bwd_workspace_bytes(const fat5_fire_params* p) {
+  if (!p || p->H < 1 || p->H > FIRE_MAX_H || p->W < 1 || p->W > FIRE_MAX_W || p->M <= 0 || p->N <= 0) return 0;
+  return align_up((size_t)fire_nout(p) * fire_nwg(p) * sizeof(float), 16);
+}
+
+extern "C++" template <int DT, int WT>
+static void fire_bwd_launch_h(int ht, int nwg, hipStream_t stream, const FireArgs& a) {
+  if (ht == 1) hipLaunchKernelGGL((fire_bwd_kernel<DT, WT, 1>), dim3(nwg), dim3(FIRE_THREADS), 0, stream, a);
+  else if (ht == 2) hipLaunchKernelGGL((fire_bwd_kernel<DT, WT, 2>), dim3(nwg), dim3(FIRE_THREADS), 0, stream, a);
+  else hipLaunchKernelGGL((fire_bwd_kernel<DT, WT, 4>), dim3(nwg), dim3(FIRE_THREADS), 0, stream, a);
+}
+
+int fat5_fire_bwd(const fat5_fire_params* p, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (int rc = fire_check(p, "fire_bwd", true)) return rc;
+  if (p->M == 0 || p->N == 0) return FAT5_OK;
+  const size_t need = fat5_fire_bwd_workspace_bytes(p);
+  if (!workspace || !aligned16(workspace) || workspace_bytes < need)
+    return fail(FAT5_EWORKSPACE, "fire_bwd: workspace of %zu bytes (16-byte aligned) needed, %zu given", need, workspace_bytes);
+  FireArgs a = fire_args(p);
+  a.ws = static_cast<float*>(workspace);
+  a.nwg = fire_nwg(p);
+  a.nout = fire_nout(p);
+  const int wt = (p->W + 15) / 16, ht = (p->H + 15) / 16;
+  const int wtp = wt <= 1 ? 1 : (wt <= 2 ? 2 : (wt <= 4 ? 4 : 8));
+  const int htp = ht <= 1 ? 1 : (ht <= 2 ? 2 : 4);
+  hipStream_t stream = (hipStream_t)stream_;
+  dispatch_dtype(p->dtype, [&](auto dt_) {
+    constexpr int DT = decltype(dt_)::value;
+    switch (wtp) {
+      case 1: fire_bwd_launch_h<DT, 1>(htp, a.nwg, stream, a); break;
+      case 2: fire_bwd_launch_h<DT, 2>(htp, a.nwg, stream, a); break;
+      case 4: fire_bwd_launch_h<DT, 4>(htp, a.nwg, stream, a); break;
+      default: fire_bwd_launch_h<DT, 8>(htp, a.nwg, stream, a); break;
+    }
+  });
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "fire_bwd launch");
+  const int per = FIRE_THREADS / 64;
+  hipLaunchKernelGGL(fire_bwd_reduce_kernel, dim3((a.nout + per - 1) / per), dim3(FIRE_THREADS), 0, stream, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "fire_bwd reduce launch");
   return FAT5_OK;
 }
 

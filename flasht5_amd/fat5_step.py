@@ -45,7 +45,8 @@ class FAT5Config:
     label_smoothing: float = 0.1
     attention_scale: float = 1.0
     attention_type: str = "fat5_rpe"      # "fat5_rpe": O(S) bias memory; "triton": the reference's dense-bias operator
-    position_encoding_type: str = "t5"      # "t5" or "RoPE" (rotary, in every attention layer; no bias)
+    position_encoding_type: str = "t5"      # "t5", "RoPE" (rotary, in every attention layer; no bias) or "FIRE" (needs "triton")
+    fire_mlp_width: int = 32               # FIRE: width of the bias MLP
     rotary_emb_fraction: float = 1.0       # RoPE: rotated share of d_kv
     rotary_base: float = 10000.0
     rotary_interleaved: bool = False
@@ -61,6 +62,11 @@ class FAT5Config:
                                            # output projection's GEMM epilogue, fused backward passes around them (fused_linear.py)
     fuse_gated_act: bool = True            # act(wi_0 x) * wi_1 x in one kernel forward, one backward (gated_act.py / fat5_gated_act_*)
     is_decoder: bool = False
+
+    def __post_init__(self):
+        if self.position_encoding_type == "FIRE" and self.attention_type == "fat5_rpe":
+            raise ValueError("position_encoding_type='FIRE' needs attention_type='triton' (dense bias): FIRE's bias is not "
+                             "Toeplitz once a row passes the threshold T, so fat5_rpe cannot carry it")
 
 
 class FAT5GatedAct(nn.Module):  # reference FlashT5DenseGatedAct / FlashT5DenseAct (:114-146)
@@ -260,7 +266,8 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward onl
                 m.Wk.weight.normal_(0.0, c.d_model ** -0.5)
                 m.Wv.weight.normal_(0.0, c.d_model ** -0.5)
                 m.o.weight.normal_(0.0, (c.num_heads * c.d_kv) ** -0.5)
-                if m.pe_encoding is not None and hasattr(m.pe_encoding, "relative_attention_bias"):  # (RoPE has no table)
+                # (RoPE has no table; FIRE keeps its own initialisation, which the reference's _init_weights does not touch)
+                if m.pe_encoding is not None and hasattr(m.pe_encoding, "relative_attention_bias"):
                     m.pe_encoding.relative_attention_bias.weight.normal_(0.0, c.d_model ** -0.5)
 
     def _shift_right(self, labels):  # HF T5 convention used by the reference (:713-714)
@@ -271,8 +278,9 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward onl
         return shifted.masked_fill(shifted == -100, c.pad_token_id)
 
     def rpe_tables(self):
-        """the two (num_buckets, H) relative-position tables (encoder, decoder): the bias gradients of the step; none with RoPE"""
-        if self.config.position_encoding_type == "RoPE":
+        """the two (num_buckets, H) relative-position tables (encoder, decoder): the bias gradients of the step; none with RoPE or
+        FIRE (FIRE's parameters are ordinary parameters of block 0's self-attention)"""
+        if self.config.position_encoding_type != "t5":
             return []
         return [self.encoder.block[0].self_attention_layer.self_attention.pe_encoding.relative_attention_bias.weight,
                 self.decoder.block[0].self_attention_layer.self_attention.pe_encoding.relative_attention_bias.weight]

@@ -287,6 +287,52 @@ size_t fat5_sizeof_rope_params(void);
 int fat5_rope_apply(const fat5_rope_params* p, void* hip_stream);
 
 /*
+ * FIRE position bias (the reference's FIRE module, src/utils/positional_encoding.py:341-417) and the gradients of its parameters,
+ * without the (M, N, W) hidden layer.  For query row i < M, key column j < N, head h < H, all in fp32:
+ *   T = |L_multiplier * init_L|,  P_i = max(i, T)
+ *   x = sign(i - j) * log(|c (i - j)| + 1) / (log(|c P_i| + 1) + eps)
+ *   bias[h][i][j] = b2[h] + sum_k w2[h][k] * relu(w1[k] x + b1[k])
+ * fat5_fire_fwd writes bias in `dtype` (FAT5_F32 / _F16 / _BF16).  fat5_fire_bwd takes the upstream gradient dbias in `dtype` and
+ * writes the fp32 gradients of w1, b1, w2, b2, c and L_multiplier, following torch autograd at its corner cases (relu'(0) = 0,
+ * sign'(x) = 0, abs'(0) = 0, max(i, T) splitting its gradient at i == T).  Deterministic: per-workgroup partials in the caller's
+ * workspace (fat5_fire_bwd_workspace_bytes), then a fixed-order reduction -- the same bits on every run and graph replay.
+ * Parameters: fp32, contiguous (w2 row-major (H, W)); c, L_multiplier and init_L are single fp32 values in DEVICE memory.
+ * bias / dbias: (H, M, N) with element strides bias_stride = [h, m] and unit inner stride; base 16-byte aligned, strides multiples
+ * of the 16-byte vector (8 elements; 4 for fp32).  Two launches each way at most; no float atomics.
+ * Rejected with FAT5_EINVAL before anything is launched: H outside [1, 64], W outside [1, 128], M or N outside [0, 2^31 - 1024],
+ * null or misaligned pointers, dtype outside {FAT5_F32, FAT5_F16, FAT5_BF16}, a workspace smaller than the query's answer.
+ * M == 0 or N == 0: a no-op after the checks (nothing is written; the gradients of an empty bias are zero).
+ */
+typedef struct fat5_fire_params {
+  int64_t M, N;              /* query rows, key columns */
+  int32_t H, W;              /* heads (1..64), MLP width (1..128) */
+  int32_t dtype;             /* of bias / dbias */
+  float eps;                 /* the denominator's epsilon (reference: 1e-6) */
+  const float* w1;           /* mlp.0.weight (W, 1) */
+  const float* b1;           /* mlp.0.bias (W) */
+  const float* w2;           /* mlp.2.weight (H, W) */
+  const float* b2;           /* mlp.2.bias (H) */
+  const float* c;            /* (1,) */
+  const float* L_multiplier; /* (1,) */
+  const float* init_L;       /* (1,) */
+  void* bias;                /* forward: output */
+  const void* dbias;         /* backward: upstream gradient */
+  int64_t bias_stride[2];    /* [h, m] element strides of bias (forward) or dbias (backward) */
+  float* dw1;                /* backward outputs, fp32, the parameters' shapes */
+  float* db1;
+  float* dw2;
+  float* db2;
+  float* dc;
+  float* dL_multiplier;
+} fat5_fire_params;
+/* sizeof(fat5_fire_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_fire_params(void);
+int fat5_fire_fwd(const fat5_fire_params* p, void* hip_stream);
+/* workspace fat5_fire_bwd needs for these shapes (bytes; 16-byte aligned) */
+size_t fat5_fire_bwd_workspace_bytes(const fat5_fire_params* p);
+int fat5_fire_bwd(const fat5_fire_params* p, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)
