@@ -71,6 +71,20 @@ class FireParams(ctypes.Structure):
     ]
 
 
+class DecodeParams(ctypes.Structure):
+    """Mirror of `fat5_decode_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("D", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("capacity", ctypes.c_int32), ("N", ctypes.c_int32), ("cache_seqlens", ctypes.c_void_p), ("sm_scale", ctypes.c_float),
+        ("bias_mode", ctypes.c_int32), ("rpe_radius", ctypes.c_int32), ("rpe1d", ctypes.c_void_p),
+        ("q", ctypes.c_void_p), ("k_cache", ctypes.c_void_p), ("v_cache", ctypes.c_void_p), ("k_new", ctypes.c_void_p),
+        ("v_new", ctypes.c_void_p), ("o", ctypes.c_void_p), ("lse", ctypes.c_void_p),
+        ("q_stride", ctypes.c_int64 * 2), ("k_cache_stride", c_i64x3), ("v_cache_stride", c_i64x3),
+        ("k_new_stride", ctypes.c_int64 * 2), ("v_new_stride", ctypes.c_int64 * 2), ("o_stride", ctypes.c_int64 * 2),
+        ("num_splits", ctypes.c_int32), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 EXPORTS = (
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
@@ -79,6 +93,7 @@ EXPORTS = (
     "fat5_adamw_scale_step", "fat5_adamw_scale_step_clipped", "fat5_adamw_scale_step_dev", "fat5_adamw_grad_sumsq", "fat5_sizeof_adamw_tensor",
     "fat5_rope_apply", "fat5_sizeof_rope_params",
     "fat5_fire_fwd", "fat5_fire_bwd", "fat5_fire_bwd_workspace_bytes", "fat5_sizeof_fire_params",
+    "fat5_attn_decode", "fat5_attn_decode_workspace_bytes", "fat5_sizeof_decode_params",
 )
 
 _lib = None
@@ -166,6 +181,14 @@ def load():
     if lib.fat5_sizeof_fire_params() != ctypes.sizeof(FireParams):
         raise ImportError(f"fat5_fire_params layout mismatch: library {lib.fat5_sizeof_fire_params()} B, "
                           f"binding {ctypes.sizeof(FireParams)} B")
+    lib.fat5_attn_decode.restype = ctypes.c_int
+    lib.fat5_attn_decode.argtypes = [ctypes.POINTER(DecodeParams), ctypes.c_void_p]
+    lib.fat5_attn_decode_workspace_bytes.restype = ctypes.c_size_t
+    lib.fat5_attn_decode_workspace_bytes.argtypes = [ctypes.POINTER(DecodeParams)]
+    lib.fat5_sizeof_decode_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_decode_params() != ctypes.sizeof(DecodeParams):
+        raise ImportError(f"fat5_decode_params layout mismatch: library {lib.fat5_sizeof_decode_params()} B, "
+                          f"binding {ctypes.sizeof(DecodeParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

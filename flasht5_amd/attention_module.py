@@ -32,7 +32,7 @@ from torch import nn
 from .flash_attention_v2_bias import flash_attention_v2_bias, flash_attention_v2_rpe1d
 from .fire import FIRE
 from .positional_encoding import RelativePositionalEncoding
-from .rotary import RotaryPositionalEncoding, apply_rotary_emb_packed
+from .rotary import RotaryPositionalEncoding, apply_rotary_emb, apply_rotary_emb_packed, apply_rotary_emb_qkv
 
 
 def _cfg(config, name, default):
@@ -106,6 +106,7 @@ class FlashT5Attention(nn.Module):
         if self.attention_type == "fat5_rpe" and (self.position_encoding_type not in ("t5", "RoPE") or self.use_masking):
             raise ValueError("fat5_rpe needs the T5 relative-position encoding or RoPE, and no key masking (use var-len batches)")
         self.pe_encoding = None
+        self._randomized = bool(_cfg(config, "use_randomized_position_encoding", False))  # (decode time: forward_decode refuses it)
         self.rotary = self.position_encoding_type == "RoPE"
         if self.rotary:  # (every layer: the reference's RoPE branch has no has_positional_encoding condition, :214)
             self.pe_encoding = RotaryPositionalEncoding(
@@ -163,6 +164,68 @@ class FlashT5Attention(nn.Module):
             k, v = unpack_heads(kv, 2, H)
         out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias)
         return linear_residual(out, self.o.weight, res), position_bias
+
+    def decode_supported(self):
+        """raise NotImplementedError when this layer cannot run a cached decoding step"""
+        if self.position_encoding_type == "FIRE":
+            raise NotImplementedError("FIRE at decode time: the bias row of query p needs a query offset the FIRE kernel does not take")
+        if self.position_encoding_type == "t5" and self._randomized:
+            raise NotImplementedError("randomized positions at decode time: they are not a function of n - m, so no cached row has "
+                                      "a fixed bias")
+        if self.position_encoding_type not in ("t5", "RoPE"):
+            raise NotImplementedError(f"position_encoding_type {self.position_encoding_type!r} at decode time")
+
+    def forward_decode(self, hidden_states, k_cache, v_cache, cache_seqlens=None, position_bias=None, position=None):
+        """One new token through this layer against a KV cache (flasht5_amd.decode.flash_attn_with_kvcache); returns (B, 1, d_model).
+
+        Self-attention (`cache_seqlens` given): q, k and v are projected from `hidden_states` (B, 1, d_model), k and v are appended
+        to `k_cache` / `v_cache` (B, L_cap, H, D) at index cache_seqlens[b] and the row attends over cache_seqlens[b] + 1 keys with
+        the decoder's `position_bias = (rpe1d, R)` (block 0's `forward_1d()`, bottom-right aligned: the query sits at the last key).
+        Cross-attention (`cache_seqlens` None): the caches hold the encoder's K / V (`project_kv`), all of them attended, no bias.
+        RoPE: `position` is a (1,) int64 device tensor (the step's position, shared by the batch); q is rotated with row `position`
+        of (cos, sin), the new k and v with that row of (cos_k, sin_k).  Forward only; nothing of the training path changes."""
+        self.decode_supported()
+        from .decode import flash_attn_with_kvcache
+        B = hidden_states.shape[0]
+        H, Dh = self.n_heads, self.key_value_proj_dim
+        q = self.Wq(hidden_states).view(B, 1, H, Dh)
+        is_self = cache_seqlens is not None
+        k = v = None
+        if is_self:
+            k = self.Wk(hidden_states).view(B, 1, H, Dh)
+            v = self.Wv(hidden_states).view(B, 1, H, Dh)
+        rpe1d, radius = None, 0
+        if self.rotary:
+            if position is None:
+                raise ValueError("forward_decode with RoPE needs the step's position (a (1,) int64 device tensor)")
+            cos, sin, cos_k, sin_k = self.pe_encoding.tables(q.device, q.dtype)
+            rows = lambda t: None if t is None else t.index_select(0, position)  # noqa: E731  (device-side: capturable)
+            if is_self:
+                q, k, v = apply_rotary_emb_qkv(q, k, v, rows(cos), rows(sin), rows(cos_k), rows(sin_k), self.pe_encoding.interleaved)
+            else:
+                q = apply_rotary_emb(q, rows(cos), rows(sin), self.pe_encoding.interleaved)
+        elif is_self:
+            if position_bias is None:
+                raise ValueError("forward_decode: T5 self-attention needs position_bias=(rpe1d, radius) from block 0's forward_1d()")
+            rpe1d, radius = position_bias
+            if self.attention_type == "triton":  # (the dense path adds the bias after a cast to the activation dtype)
+                rpe1d = rpe1d.to(q.dtype).float()
+        out = flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, self.softmax_scale, rpe1d, radius)
+        return self.o(out.reshape(B, 1, self.inner_dim))
+
+    def project_kv(self, key_value_states):
+        """the cross-attention K / V of an encoder output (B, L_enc, d_model) as (B, L_enc, H, D) caches for `forward_decode`:
+        projected once, and with RoPE rotated once at positions 0..L_enc-1 with (cos_k, sin_k), as the full forward does"""
+        self.decode_supported()
+        B, N = key_value_states.shape[:2]
+        k = self.Wk(key_value_states).view(B, N, self.n_heads, self.key_value_proj_dim)
+        v = self.Wv(key_value_states).view(B, N, self.n_heads, self.key_value_proj_dim)
+        if self.rotary:
+            cos, sin, cos_k, sin_k = self.pe_encoding.tables(k.device, k.dtype)
+            ck, sk = (cos, sin) if cos_k is None else (cos_k, sin_k)
+            k = apply_rotary_emb(k, ck, sk, self.pe_encoding.interleaved)
+            v = apply_rotary_emb(v, ck, sk, self.pe_encoding.interleaved)
+        return k.contiguous(), v.contiguous()
 
     def _rotary_tables(self, x):
         return self.pe_encoding.tables(x.device, x.dtype)

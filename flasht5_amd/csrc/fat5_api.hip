@@ -18,6 +18,7 @@
 #include "fold_weights.h"
 #include "rope_kernels.h"
 #include "fire_kernels.h"
+#include "decode_kernels.h"
 
 using namespace fat5;
 
@@ -1431,6 +1432,129 @@ int fat5_fire_bwd(const fat5_fire_params* p, void* workspace, size_t workspace_b
   hipLaunchKernelGGL(fire_bwd_reduce_kernel, dim3((a.nout + per - 1) / per), dim3(FIRE_THREADS), 0, stream, a);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "fire_bwd reduce launch");
+  return FAT5_OK;
+}
+
+// ---- decode attention against a KV cache (decode_kernels.h) ----
+size_t fat5_sizeof_decode_params(void) { return sizeof(fat5_decode_params); }
+
+// key-range splits per (b, h) from host-known arguments only: enough workgroups for two per CU of a 256-CU chip, but no more
+// splits than whole workgroup passes (G * DEC_UNROLL rows) fit into the capacity.  Fixed, not queried from the device: the same
+// arguments give the same split -- and the same bits -- on every machine.
+static int decode_splits(const fat5_decode_params* p) {
+  if (p->num_splits > 0) return p->num_splits;
+  const long bh = (long)p->B * p->H;
+  const long pass = (long)(DEC_THREADS / (p->D / 8)) * DEC_UNROLL;
+  const long by_cap = std::max<long>(1, (p->capacity + pass - 1) / pass);
+  const long want = std::max<long>(1, (512 + bh - 1) / bh);
+  return (int)std::min<long>(DEC_MAX_SPLITS, std::min(want, by_cap));
+}
+
+static bool decode_shape_ok(const fat5_decode_params* p) {
+  return p->B >= 1 && p->B <= 65535 && p->H >= 1 && p->H <= 65535 && (p->D == 64 || p->D == 128) && p->capacity >= 0 &&
+         p->num_splits >= 0 && p->num_splits <= DEC_MAX_SPLITS;
+}
+
+size_t fat5_attn_decode_workspace_bytes(const fat5_decode_params* p) {
+  if (!p || !decode_shape_ok(p)) return 0;
+  const int s = decode_splits(p);
+  if (s <= 1) return 0;
+  return align_up((size_t)p->B * p->H * s * (p->D + 2) * sizeof(float), 16);
+}
+
+static int decode_check(const fat5_decode_params* p) {
+  const char* what = "attn_decode";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (p->D != 64 && p->D != 128) return fail(FAT5_EINVAL, "%s: head_dim %d (64 or 128)", what, p->D);
+  if (p->dtype != FAT5_F16 && p->dtype != FAT5_BF16) return fail(FAT5_EINVAL, "%s: dtype %d (FAT5_F16 or FAT5_BF16)", what, p->dtype);
+  if (p->B < 1 || p->B > 65535 || p->H < 1 || p->H > 65535)
+    return fail(FAT5_EINVAL, "%s: B %d / H %d outside [1, 65535]", what, p->B, p->H);
+  if (p->capacity < 0) return fail(FAT5_EINVAL, "%s: capacity %d", what, p->capacity);
+  if (p->num_splits < 0 || p->num_splits > DEC_MAX_SPLITS)
+    return fail(FAT5_EINVAL, "%s: num_splits %d (0 for the library's choice, or 1 to %d)", what, p->num_splits, DEC_MAX_SPLITS);
+  if (!p->cache_seqlens && (p->N < 0 || p->N > p->capacity))
+    return fail(FAT5_EINVAL, "%s: N %d outside [0, capacity %d] without cache_seqlens", what, p->N, p->capacity);
+  if (p->cache_seqlens && (reinterpret_cast<uintptr_t>(p->cache_seqlens) & 3))
+    return fail(FAT5_EINVAL, "%s: cache_seqlens misaligned", what);
+  if (p->bias_mode != FAT5_BIAS_NONE && p->bias_mode != FAT5_BIAS_RPE1D)
+    return fail(FAT5_EINVAL, "%s: bias_mode %d (FAT5_BIAS_NONE or FAT5_BIAS_RPE1D)", what, p->bias_mode);
+  if (p->bias_mode == FAT5_BIAS_RPE1D) {
+    if (p->rpe_radius < 1 || p->rpe_radius > 2048) return fail(FAT5_EINVAL, "%s: rpe_radius %d outside 1..2048", what, p->rpe_radius);
+    if (!p->rpe1d || (reinterpret_cast<uintptr_t>(p->rpe1d) & 3)) return fail(FAT5_EINVAL, "%s: RPE1D needs rpe1d (fp32, aligned)", what);
+  }
+  if ((p->k_new == nullptr) != (p->v_new == nullptr)) return fail(FAT5_EINVAL, "%s: k_new and v_new must both be given or both be NULL", what);
+  if (p->k_new && !p->cache_seqlens) return fail(FAT5_EINVAL, "%s: appending k_new / v_new needs cache_seqlens", what);
+  if (!std::isfinite(p->sm_scale)) return fail(FAT5_EINVAL, "%s: sm_scale must be finite", what);
+  struct { const void* ptr; const int64_t* st; int n; const char* name; } t[] = {
+      {p->q, p->q_stride, 2, "q"}, {p->k_cache, p->k_cache_stride, 3, "k_cache"}, {p->v_cache, p->v_cache_stride, 3, "v_cache"},
+      {p->k_new, p->k_new_stride, 2, "k_new"}, {p->v_new, p->v_new_stride, 2, "v_new"}, {p->o, p->o_stride, 2, "o"}};
+  for (int k = 0; k < 6; ++k) {
+    const auto& e = t[k];
+    if ((k == 3 || k == 4) && !p->k_new) continue;  // (no append)
+    if (!e.ptr || !aligned16(e.ptr)) return fail(FAT5_EINVAL, "%s: %s: null or unaligned pointer (16-byte aligned base)", what, e.name);
+    for (int i = 0; i < e.n; ++i)
+      if (e.st[i] % 8) return fail(FAT5_EINVAL, "%s: %s strides must be multiples of 8 elements (innermost stride 1)", what, e.name);
+  }
+  if (p->lse && (reinterpret_cast<uintptr_t>(p->lse) & 3)) return fail(FAT5_EINVAL, "%s: lse misaligned", what);
+  const size_t need = fat5_attn_decode_workspace_bytes(p);
+  if (need && (!p->workspace || !aligned16(p->workspace) || p->workspace_bytes < need))
+    return fail(FAT5_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", what, need, p->workspace_bytes);
+  return FAT5_OK;
+}
+
+extern "C++" template <int DT, int D, bool APPEND, bool BIAS>
+static void decode_launch(const DecodeArgs& a, hipStream_t stream) {
+  const dim3 grid(a.splits, a.H, a.B);
+  if (a.splits == 1) {
+    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, true>), grid, dim3(DEC_THREADS), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, false>), grid, dim3(DEC_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((decode_combine_kernel<DT, D>), dim3(a.H, a.B), dim3(D), 0, stream, a);
+  }
+}
+
+int fat5_attn_decode(const fat5_decode_params* p, void* stream_) {
+  if (int rc = decode_check(p)) return rc;
+  DecodeArgs a = {};
+  a.q = p->q;
+  a.kc = p->k_cache;
+  a.vc = p->v_cache;
+  a.kn = p->k_new;
+  a.vn = p->v_new;
+  a.o = p->o;
+  a.lse = p->lse;
+  a.seqlens = p->cache_seqlens;
+  a.rpe1d = p->bias_mode == FAT5_BIAS_RPE1D ? p->rpe1d : nullptr;
+  a.ws = static_cast<float*>(p->workspace);
+  a.q_sb = p->q_stride[0], a.q_sh = p->q_stride[1];
+  a.o_sb = p->o_stride[0], a.o_sh = p->o_stride[1];
+  a.kn_sb = p->k_new_stride[0], a.kn_sh = p->k_new_stride[1];
+  a.vn_sb = p->v_new_stride[0], a.vn_sh = p->v_new_stride[1];
+  for (int i = 0; i < 3; ++i) a.kc_s[i] = p->k_cache_stride[i], a.vc_s[i] = p->v_cache_stride[i];
+  a.B = p->B, a.H = p->H, a.cap = p->capacity, a.N = p->N, a.R = p->rpe_radius;
+  a.splits = decode_splits(p);
+  a.scale_log2 = p->sm_scale * kLog2e;
+  const bool append = p->k_new != nullptr, bias = a.rpe1d != nullptr;
+  hipStream_t stream = (hipStream_t)stream_;
+  auto go = [&](auto dt_, auto d_) {
+    constexpr int DT = decltype(dt_)::value, D = decltype(d_)::value;
+    if (append) {
+      if (bias) decode_launch<DT, D, true, true>(a, stream);
+      else decode_launch<DT, D, true, false>(a, stream);
+    } else {
+      if (bias) decode_launch<DT, D, false, true>(a, stream);
+      else decode_launch<DT, D, false, false>(a, stream);
+    }
+  };
+  if (p->dtype == FAT5_F16) {
+    if (p->D == 64) go(IC<FAT5_F16>{}, IC<64>{});
+    else go(IC<FAT5_F16>{}, IC<128>{});
+  } else {
+    if (p->D == 64) go(IC<FAT5_BF16>{}, IC<64>{});
+    else go(IC<FAT5_BF16>{}, IC<128>{});
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "attn_decode launch");
   return FAT5_OK;
 }
 

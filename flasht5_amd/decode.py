@@ -1,0 +1,170 @@
+"""Decode attention against a KV cache: `flash_attn_with_kvcache` (flash_attn's layout and meaning) at seqlen_q = 1, on the
+split-KV HIP kernel behind `fat5_attn_decode` (csrc/decode_kernels.h).
+
+    o = flash_attn_with_kvcache(q, k_cache, v_cache, k=k_new, v=v_new, cache_seqlens=lens, rpe1d=rpe1d, rpe_radius=R)
+
+q (B, 1, H, D); caches (B, L_cap, H, D), strided views accepted (a (B, H, L_cap, D) buffer's transpose works as it is); k / v the new
+row (B, 1, H, D) or None.  `cache_seqlens` holds each batch element's length BEFORE the append and is not incremented: the caller
+advances it.  With k / v the row is written into the caches at index cache_seqlens[b] inside the same launch.  The optional T5 bias
+is the (H, 2R+1) fp32 generator of the linear-memory mode, bottom-right aligned: the query sits at position L_b - 1.
+
+Forward only: inputs that require grad under grad mode are rejected.  There is no eager fallback: CPU tensors are rejected."""
+import math
+from typing import List, Optional
+
+import torch
+
+from . import _lib
+
+
+def _dec_view(t):
+    """(B, 1, H, D) -> element strides [b, h]"""
+    return (t.stride(0), t.stride(2))
+
+
+def _params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse, sm_scale, rpe1d, radius, num_splits):
+    B, _, H, D = q.shape
+    p = _lib.DecodeParams()
+    p.B, p.H, p.D = B, H, D
+    p.dtype = _lib.dtype_code(q.dtype)
+    p.capacity = k_cache.shape[1]
+    p.N = k_cache.shape[1] if cache_seqlens is None else 0
+    p.cache_seqlens = cache_seqlens.data_ptr() if cache_seqlens is not None else None
+    p.sm_scale = float(sm_scale)
+    if rpe1d is not None:
+        p.bias_mode, p.rpe_radius, p.rpe1d = _lib.BIAS_RPE1D, int(radius), rpe1d.data_ptr()
+    p.q, p.k_cache, p.v_cache, p.o = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr()
+    p.q_stride[:] = _dec_view(q)
+    p.o_stride[:] = _dec_view(o)
+    p.k_cache_stride[:] = (k_cache.stride(0), k_cache.stride(1), k_cache.stride(2))
+    p.v_cache_stride[:] = (v_cache.stride(0), v_cache.stride(1), v_cache.stride(2))
+    if k is not None:
+        p.k_new, p.v_new = k.data_ptr(), v.data_ptr()
+        p.k_new_stride[:] = _dec_view(k)
+        p.v_new_stride[:] = _dec_view(v)
+    p.lse = lse.data_ptr() if lse is not None else None
+    p.num_splits = int(num_splits)
+    return p
+
+
+def _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius):
+    """everything the host can check without touching a device: shapes, dtypes, strides, the bias generator against its radius"""
+    if q.dim() != 4 or q.shape[1] != 1:
+        raise ValueError(f"flash_attn_with_kvcache: q must be (B, 1, H, D) (one query row per step), got {tuple(q.shape)}")
+    B, _, H, D = q.shape
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dim() != 4 or t.shape[0] != B or t.shape[2] != H or t.shape[3] != D:
+            raise ValueError(f"flash_attn_with_kvcache: {name} must be (B, L_cap, H, D) = ({B}, L_cap, {H}, {D}), got {tuple(t.shape)}")
+    if k_cache.shape[1] != v_cache.shape[1]:
+        raise ValueError("flash_attn_with_kvcache: k_cache and v_cache have different capacities")
+    if (k is None) != (v is None):
+        raise ValueError("flash_attn_with_kvcache: pass both k and v, or neither")
+    if k is not None:
+        for name, t in (("k", k), ("v", v)):
+            if tuple(t.shape) != (B, 1, H, D):
+                raise ValueError(f"flash_attn_with_kvcache: {name} must be ({B}, 1, {H}, {D}), got {tuple(t.shape)}")
+        if cache_seqlens is None:
+            raise ValueError("flash_attn_with_kvcache: appending k / v needs cache_seqlens")
+    for t in [q, k_cache, v_cache] + ([k, v] if k is not None else []):
+        if t.dtype != q.dtype:
+            raise ValueError(f"flash_attn_with_kvcache: dtype mismatch ({t.dtype} vs q {q.dtype})")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"flash_attn_with_kvcache: dtype {q.dtype} (fp16 or bf16)")
+    if D not in (64, 128):
+        raise ValueError(f"flash_attn_with_kvcache: head_dim {D} (64 or 128)")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not _lib.kernel_ready(t):
+            raise ValueError(f"flash_attn_with_kvcache: {name} needs innermost stride 1, a 16-byte aligned base and strides that are "
+                             "multiples of 8 elements (it is written in place, so it cannot be copied)")
+    if cache_seqlens is not None and (cache_seqlens.dim() != 1 or cache_seqlens.numel() != B):
+        raise ValueError(f"flash_attn_with_kvcache: cache_seqlens must hold {B} lengths, got shape {tuple(cache_seqlens.shape)}")
+    if rpe1d is not None:
+        # (the kernel reads rpe1d[h][clamp(rel, -R, R) + R]: a generator narrower than 2R + 1 would be read past its end)
+        if not 1 <= int(radius) <= 2048:
+            raise ValueError(f"flash_attn_with_kvcache: rpe_radius {radius} outside 1..2048")
+        if rpe1d.dtype != torch.float32 or tuple(rpe1d.shape) != (H, 2 * int(radius) + 1) or not rpe1d.is_contiguous():
+            raise ValueError(f"flash_attn_with_kvcache: rpe1d must be a contiguous fp32 ({H}, 2 * rpe_radius + 1) = "
+                             f"({H}, {2 * int(radius) + 1}) tensor, got {rpe1d.dtype} {tuple(rpe1d.shape)}")
+
+
+def _check_devices(q, k_cache, v_cache, k, v, rpe1d):
+    for t in (q, k_cache, v_cache, k, v, rpe1d):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise ValueError("flash_attn_with_kvcache: tensors must be on the GPU (there is no CPU path)")
+        if t.device != q.device:
+            raise ValueError("flash_attn_with_kvcache: tensors on different devices")
+
+
+def _check(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius):
+    _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius)
+    _check_devices(q, k_cache, v_cache, k, v, rpe1d)
+    if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or cache_seqlens.device != q.device or
+                                      not cache_seqlens.is_contiguous()):
+        raise ValueError(f"fat5::attn_decode: cache_seqlens must be a contiguous int32 tensor on {q.device}")
+
+
+def _ready(t):
+    return t if (t is None or _lib.kernel_ready(t)) else t.contiguous()
+
+
+@torch.library.custom_op("fat5::attn_decode", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor], v: Optional[torch.Tensor],
+                cache_seqlens: Optional[torch.Tensor], sm_scale: float, rpe1d: Optional[torch.Tensor], rpe_radius: int,
+                return_lse: bool, num_splits: int) -> List[torch.Tensor]:
+    """[o (B, 1, H, D) contiguous, lse (B, H, 1) fp32 (empty (0,) when return_lse is False)]; appends k / v to the caches"""
+    _check(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius)
+    q, k, v = _ready(q), _ready(k), _ready(v)
+    B, _, H, D = q.shape
+    o = torch.empty((B, 1, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, 1), dtype=torch.float32, device=q.device) if return_lse else q.new_empty((0,), dtype=torch.float32)
+    p = _params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse if return_lse else None, sm_scale, rpe1d, rpe_radius, num_splits)
+    lib = _lib.load()
+    ws = None
+    need = lib.fat5_attn_decode_workspace_bytes(p)
+    if need:
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        p.workspace, p.workspace_bytes = ws.data_ptr(), need
+    with _lib.on_device(q.device):
+        _lib.check(lib.fat5_attn_decode(p, _lib.stream_ptr(q.device)), "fat5_attn_decode")
+    return [o, lse]
+
+
+@attn_decode.register_fake
+def _attn_decode_fake(q, k_cache, v_cache, k, v, cache_seqlens, sm_scale, rpe1d, rpe_radius, return_lse, num_splits):
+    B, _, H, D = q.shape
+    o = q.new_empty((B, 1, H, D))
+    lse = q.new_empty((B, H, 1), dtype=torch.float32) if return_lse else q.new_empty((0,), dtype=torch.float32)
+    return [o, lse]
+
+
+def _as_seqlens(cache_seqlens, device):
+    """int32 device lengths, converted the way `_as_cu` converts cu_seqlens -- except inside a graph capture, where a conversion
+    would bake one value into the graph: there they must already be an int32 tensor on the device"""
+    if cache_seqlens is None:
+        return None
+    ok = cache_seqlens.dtype == torch.int32 and cache_seqlens.device == device and cache_seqlens.is_contiguous()
+    if ok:
+        return cache_seqlens
+    if torch.cuda.is_current_stream_capturing():
+        raise ValueError("flash_attn_with_kvcache: inside a graph capture cache_seqlens must already be a contiguous int32 tensor on "
+                         f"{device} (a conversion would fix its current value in the graph)")
+    return cache_seqlens.to(device=device, dtype=torch.int32).contiguous()
+
+
+def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, softmax_scale=None, rpe1d=None, rpe_radius=0,
+                            return_lse=False, num_splits=0):
+    """flash_attn's `flash_attn_with_kvcache` for one query row: returns o (B, 1, H, D), or (o, lse (B, H, 1) fp32) with
+    return_lse.  An int cache_seqlens broadcasts over the batch.  num_splits 0 lets the library pick the key-range split from
+    B, H and the cache capacity (never from the lengths: a captured graph stays valid while they grow)."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v, rpe1d)):
+        raise RuntimeError("flash_attn_with_kvcache is forward only: call it under torch.no_grad() / inference_mode(), or detach")
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32)
+    _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius)  # (before the device checks: every shape error is
+    _check_devices(q, k_cache, v_cache, k, v, rpe1d)                           #  reported as such, on any host)
+    lens = _as_seqlens(cache_seqlens, q.device)
+    scale = 1.0 / math.sqrt(q.shape[-1]) if softmax_scale is None else float(softmax_scale)
+    o, lse = attn_decode(q, k_cache, v_cache, k, v, lens, scale, rpe1d, int(rpe_radius), bool(return_lse), int(num_splits))
+    return (o, lse) if return_lse else o

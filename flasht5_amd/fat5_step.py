@@ -11,7 +11,10 @@ A minimal encoder-decoder with the reference's structure (src/model/modeling_fla
   * loss           -> `FlashT5CrossEntropyLoss` (cross_entropy_loss with z-loss and label smoothing, HIP)
   * everything else is plain torch-ROCm: `nn.Linear` (hipBLASLt), `nn.Embedding`, tanh-GELU gating, residual adds.
 
-This is the step DRIVER of the hot path, not a model zoo: no generation, heads, dropout (0 in every reference config),
+Generation: `generate` (greedy, the reference's algorithm and return value) and `decode_step` run one new token per step through
+the decoder against per-layer KV caches (flasht5_amd/generation.py, the split-KV decode kernel), optionally replayed from a HIP graph.
+
+This is the step DRIVER of the hot path, not a model zoo: no beam search or sampling, heads, dropout (0 in every reference config),
 HF plumbing or checkpoint conversion.  Data parallelism = one process per GPU; `allreduce_gradients` is the step's one
 exchange (RCCL over xGMI): a single flat fp32 all-reduce that carries the two `(32, H)` relative-position tables first.
 """
@@ -230,7 +233,7 @@ class FAT5Stack(nn.Module):  # :394-464
         return self.final_layer_norm(h)
 
 
-class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward only)
+class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; cached greedy generation in generation.py)
     def __init__(self, config: FAT5Config):
         super().__init__()
         import copy
@@ -294,6 +297,21 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward onl
             return lm_head_cross_entropy(dec, self.lm_head.weight, labels, label_smoothing=c.label_smoothing,
                                          lse_square_scale=c.z_loss, reduction="mean")[0]
         return self.loss_fct(self.lm_head(dec), labels)
+
+    def init_decode_state(self, input_ids, max_length=32, attention_mask=None):
+        """encoder output, cross K / V and empty self-attention caches of capacity max_length + 1 (generation.DecodeState)"""
+        from .generation import init_decode_state
+        return init_decode_state(self, input_ids, max_length, attention_mask)
+
+    def decode_step(self, state, token_ids):
+        """one token per row through the cached decoder -> logits (B, vocab) of the next position (generation.decode_step)"""
+        from .generation import decode_step
+        return decode_step(self, state, token_ids)
+
+    def generate(self, input_ids, attention_mask=None, max_length=32, graph=False):
+        """greedy decoding with a KV cache; returns what the reference's generate returns (generation.generate)"""
+        from .generation import generate
+        return generate(self, input_ids, attention_mask, max_length, graph)
 
 
 def allreduce_gradients(model: nn.Module, group=None, average=True):

@@ -1,0 +1,174 @@
+"""KV-cached greedy generation for `FAT5ForConditionalGeneration` (the reference's `generate`, src/model/modeling_flash_t5.py:648-690,
+reruns the whole decoder over every token so far at every step; here each step runs ONE new token through the decoder against
+per-layer caches).
+
+    state = model.init_decode_state(input_ids, max_length=32)   # encoder once, cross K / V once per layer
+    logits = model.decode_step(state, token_ids)                 # (B, vocab) for the next position; the caches grow by one
+    labels = model.generate(input_ids, max_length=32, graph=True)
+
+What a step runs: the embedding of the new token, then per decoder block the self-attention (q, k, v projected from the one row,
+k and v appended to the layer's cache by the decode kernel, the T5 bias of block 0's `forward_1d()` bottom-right aligned), the
+cross-attention against the encoder's K / V, and the feed-forward sub-layer -- the same modules, weights and dtype rules as the
+training forward (a bf16 model, or fp32 weights under bf16 autocast).  `cache_seqlens` is one (B,) int32 device tensor shared by
+every self-attention cache and incremented on the device at the end of each step; nothing a step reads comes from the host, so
+`graph=True` captures one step once and replays it per token.
+"""
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
+
+import torch
+
+
+@dataclass
+class DecodeState:
+    """Everything a decoding step reads and writes; all of it lives on the device.  `cache_seqlens[b]` is the number of tokens
+    already decoded (the length of every self-attention cache before the next append); the batch shares one length."""
+    encoder_hidden_states: torch.Tensor
+    self_k: List[torch.Tensor]          # per decoder layer (B, capacity, H, D)
+    self_v: List[torch.Tensor]
+    cross_k: List[torch.Tensor]         # per decoder layer (B, L_enc, H, D)
+    cross_v: List[torch.Tensor]
+    cache_seqlens: torch.Tensor         # (B,) int32
+    position_bias: Optional[Tuple[torch.Tensor, int]]  # the decoder's (rpe1d, R) (T5), or None (RoPE)
+    capacity: int
+    steps: int = 0                      # decode_step calls so far (host-side: decode_step refuses to run past the capacity)
+
+    @property
+    def position(self):
+        """the step's position as a (1,) int64 device tensor (the RoPE table row): the shared length, clamped on the device to the
+        capacity (which init_decode_state keeps within the rotary tables), so that no length a caller writes can index past them"""
+        return self.cache_seqlens[:1].long().clamp(0, self.capacity - 1)
+
+
+def _embed(model, ids):
+    h = model.shared(ids)
+    if torch.is_autocast_enabled() and h.is_cuda:  # (FAT5Stack.forward's rule)
+        h = h.to(torch.get_autocast_dtype("cuda"))
+    return h
+
+
+def _check_supported(model):
+    for blk in model.decoder.block:
+        blk.self_attention_layer.self_attention.decode_supported()
+        blk.cross_attention_layer.cross_attention.decode_supported()
+
+
+@torch.no_grad()
+def init_decode_state(model, input_ids, max_length, attention_mask=None):
+    """Run the encoder, project every decoder layer's cross-attention K / V once and allocate self-attention caches of capacity
+    `max_length + 1`.  `attention_mask` is accepted and not applied, as the reference does with use_masking=False."""
+    _check_supported(model)
+    first = model.decoder.block[0].self_attention_layer.self_attention
+    cap = int(max_length) + 1
+    if first.rotary and cap > first.pe_encoding.max_sequence_length:
+        # (step t reads row t of the rotary tables; the full forward refuses positions past them the same way)
+        raise ValueError(f"max_length {max_length}: the cache of {cap} positions exceeds the rotary tables' "
+                         f"{first.pe_encoding.max_sequence_length} rows (max_sequence_length); use max_length <= "
+                         f"{first.pe_encoding.max_sequence_length - 1}")
+    B = input_ids.shape[0]
+    enc = model.encoder(input_ids)
+    dev = enc.device
+    # (the projections' dtype: autocast's when it is on, the weights' otherwise -- the dtype of k and v in the training forward)
+    dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else model.shared.weight.dtype
+    H, D = first.n_heads, first.key_value_proj_dim
+    self_k, self_v, cross_k, cross_v = [], [], [], []
+    for blk in model.decoder.block:
+        self_k.append(torch.zeros((B, cap, H, D), dtype=dtype, device=dev))
+        self_v.append(torch.zeros((B, cap, H, D), dtype=dtype, device=dev))
+        k, v = blk.cross_attention_layer.cross_attention.project_kv(enc)
+        cross_k.append(k)
+        cross_v.append(v)
+    pb = None
+    if not first.rotary:
+        pb = first.pe_encoding.forward_1d()  # (the (H, 2R+1) generator, built once per generate as the training path builds it per step)
+    return DecodeState(enc, self_k, self_v, cross_k, cross_v, torch.zeros((B,), dtype=torch.int32, device=dev), pb, cap)
+
+
+@torch.no_grad()
+def decode_step(model, state, token_ids):
+    """one token per batch row (B,) or (B, 1) through the decoder against the caches -> logits (B, vocab) of the next position;
+    the self-attention caches grow by one (cache_seqlens is incremented on the device)"""
+    B = state.cache_seqlens.shape[0]
+    if state.steps >= state.capacity:
+        raise ValueError(f"decode_step: the caches hold {state.capacity} positions and all of them are used (init_decode_state with a "
+                         "larger max_length)")
+    state.steps += 1
+    h = _embed(model, token_ids.reshape(B, 1))
+    pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
+    for i, blk in enumerate(model.decoder.block):
+        sa = blk.self_attention_layer
+        h = h + sa.self_attention.forward_decode(sa.layer_norm(h), state.self_k[i], state.self_v[i], state.cache_seqlens,
+                                                 position_bias=state.position_bias, position=pos)
+        ca = blk.cross_attention_layer
+        h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos)
+        h = blk.ff_layer(h)
+    h = model.decoder.final_layer_norm(h)
+    state.cache_seqlens.add_(1)
+    return model.lm_head(h)[:, 0]
+
+
+def _greedy_step(model, state, tok, labels, seen_eos):
+    """decode_step + argmax: the token goes to `tok` and to column cache_seqlens of `labels` (a device-side index), and rows that
+    produced a 1 are marked in `seen_eos` -- nothing here reads the host, so the same code is captured as it is"""
+    logits = decode_step(model, state, tok)
+    nxt = logits.argmax(-1)
+    tok.copy_(nxt)
+    col = state.cache_seqlens.long().unsqueeze(1)  # (already incremented: the new token's column)
+    labels.scatter_(1, col, nxt.unsqueeze(1))
+    seen_eos.logical_or_(nxt == 1)
+
+
+def finish_labels(labels):
+    """the reference's ending (:682-688): the last column becomes 1, and everything after each row's first 1 becomes 0"""
+    labels = labels.clone()
+    labels[:, -1] = 1
+    L = labels.shape[1]
+    first = (labels == 1).long().argmax(-1, keepdim=True)
+    keep = torch.arange(L, device=labels.device).unsqueeze(0) <= first
+    return labels.masked_fill(~keep, 0)
+
+
+@torch.no_grad()
+def generate(model, input_ids, attention_mask=None, max_length=32, graph=False):
+    """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
+    (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
+
+    graph=True captures one decoding step (for this batch and capacity) once in a HIP graph on one stream and replays it per
+    token; the first step runs eagerly (it also builds what the step allocates lazily), so both modes run the same kernels with the
+    same arguments and give the same tokens."""
+    B = input_ids.shape[0]
+    dev = input_ids.device
+    state = init_decode_state(model, input_ids, max_length, attention_mask)
+    labels = torch.zeros((B, state.capacity), dtype=torch.long, device=dev)
+    tok = torch.zeros((B,), dtype=torch.long, device=dev)
+    seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)
+    steps = 0
+    g = None
+    try:
+        for _ in range(int(max_length)):
+            if g is not None:
+                g.replay()
+            else:
+                _greedy_step(model, state, tok, labels, seen_eos)
+            steps += 1
+            if bool(seen_eos.all()):
+                break
+            if graph and g is None and steps < max_length:  # (after the stop check: no capture when the first step ends it)
+                g = _capture(model, state, tok, labels, seen_eos)
+    finally:
+        del g
+    return finish_labels(labels[:, :steps + 1])
+
+
+def _capture(model, state, tok, labels, seen_eos):
+    """one greedy step captured in a HIP graph (nothing runs during the capture: the state is unchanged)"""
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    ac = torch.is_autocast_enabled()
+    with torch.cuda.graph(g):  # (torch's capture stream: one stream, no parallel branches)
+        if ac:  # (autocast's weight-cast cache must not hand tensors from outside the capture to it)
+            with torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False):
+                _greedy_step(model, state, tok, labels, seen_eos)
+        else:
+            _greedy_step(model, state, tok, labels, seen_eos)
+    return g

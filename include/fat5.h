@@ -333,6 +333,59 @@ size_t fat5_fire_bwd_workspace_bytes(const fat5_fire_params* p);
 int fat5_fire_bwd(const fat5_fire_params* p, void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /*
+ * Decode attention against a KV cache: one query row per (batch, head), the key range split over several workgroups (split-KV)
+ * and merged in a fixed order (decode_kernels.h).  Stands in for flash_attn's `flash_attn_with_kvcache` at seqlen_q = 1; the
+ * reference has no cached decoding (its generate reruns the whole decoder per token, src/model/modeling_flash_t5.py:648-690).
+ *   o[b,h] = softmax(q[b,h] . K[b,h,0:L_b]^T * sm_scale + bias) . V[b,h,0:L_b],  fp32 accumulation;
+ *   lse[b,h] (optional) natural-log LSE, fp32, (B, H) contiguous.  L_b == 0 gives o = 0, lse = -inf.
+ * Lengths, as flash_attn_with_kvcache means them (the length BEFORE the append): len_b = cache_seqlens[b], or N for every b when
+ * cache_seqlens is NULL.
+ *   - k_new / v_new given: the kernel writes the new row into the caches at index len_b and attends over L_b = len_b + 1 keys;
+ *     the workgroup whose key range holds that row reads it from k_new / v_new, no other one reads it.  Needs cache_seqlens.
+ *   - no new row: L_b = len_b.
+ * Bad device lengths are a caller error that never becomes a fault: a length below 0 counts as 0, one above the capacity as the
+ * capacity, and an append at len_b == capacity is skipped (L_b = capacity, the new row is neither written nor attended).  No
+ * cache row at or beyond L_b is read, and nothing outside rows [0, capacity) is read or written.  cache_seqlens is never written.
+ * bias_mode FAT5_BIAS_NONE or FAT5_BIAS_RPE1D, bottom-right aligned: the query sits at p_b = L_b - 1 and
+ *   bias[j] = rpe1d[h][clamp(j - p_b, -R, R) + R].
+ * The grid depends on B, H, capacity and num_splits only -- never on the device lengths -- so a captured graph stays valid while
+ * the lengths grow; results are bitwise identical run to run.  Element strides, 64-bit offsets, innermost stride 1; every base
+ * 16-byte aligned and every stride a multiple of 8 elements.  q / k_new / v_new / o are (B, H, D) views with strides [b, h]; the
+ * caches are (B, capacity, H, D) views with strides [b, l, h] (so (B, L, H, D) and (B, H, L, D) storage both work).
+ * Rejected with FAT5_EINVAL before anything is launched: D outside {64, 128}, dtype outside {FAT5_F16, FAT5_BF16}, B / H / capacity
+ * out of range, N outside [0, capacity], num_splits outside [0, 128], a radius outside 1..2048 or a NULL rpe1d with RPE1D,
+ * exactly one of k_new / v_new, an append without cache_seqlens, NULL / misaligned pointers or strides; FAT5_EWORKSPACE when the
+ * workspace is missing, misaligned or smaller than fat5_attn_decode_workspace_bytes().
+ */
+typedef struct fat5_decode_params {
+  int32_t B, H, D;            /* D in {64, 128} */
+  int32_t dtype;              /* FAT5_F16 | FAT5_BF16: q, caches, k_new, v_new, o */
+  int32_t capacity;           /* cache rows per (b, h) */
+  int32_t N;                  /* key count of every batch element when cache_seqlens is NULL (0..capacity) */
+  const int32_t* cache_seqlens; /* (B,) int32 device array, or NULL */
+  float sm_scale;
+  int32_t bias_mode;          /* FAT5_BIAS_NONE | FAT5_BIAS_RPE1D */
+  int32_t rpe_radius;         /* R, 1..2048 with RPE1D */
+  const float* rpe1d;         /* (H, 2R + 1) fp32 contiguous */
+  const void* q;              /* (B, H, D): q_stride [b, h] */
+  void* k_cache;              /* (B, capacity, H, D): k_cache_stride [b, l, h] */
+  void* v_cache;
+  const void* k_new;          /* (B, H, D) or NULL (then v_new NULL too) */
+  const void* v_new;
+  void* o;                    /* (B, H, D) */
+  float* lse;                 /* (B, H) contiguous fp32, or NULL */
+  int64_t q_stride[2], k_cache_stride[3], v_cache_stride[3], k_new_stride[2], v_new_stride[2], o_stride[2];
+  int32_t num_splits;         /* key-range splits per (b, h), 1..128; 0 = the library's choice from B, H, capacity */
+  void* workspace;            /* fat5_attn_decode_workspace_bytes(); 16-byte aligned; may be NULL when that is 0 */
+  size_t workspace_bytes;
+} fat5_decode_params;
+/* sizeof(fat5_decode_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_decode_params(void);
+/* workspace fat5_attn_decode needs for these host-known arguments (bytes; 0 when one split is used) */
+size_t fat5_attn_decode_workspace_bytes(const fat5_decode_params* p);
+int fat5_attn_decode(const fat5_decode_params* p, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)
