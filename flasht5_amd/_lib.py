@@ -41,6 +41,7 @@ class AttnParams(ctypes.Structure):
         ("rpe_num_buckets", ctypes.c_int32), ("unit_begin", ctypes.c_int32), ("unit_count", ctypes.c_int32),
         ("variant", ctypes.c_int32),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+        ("rpe_bucket_host", ctypes.c_void_p),
     ]
 
 
@@ -208,6 +209,7 @@ V_FUSED64_ON, V_FUSED64_OFF = 65536, 131072
 V_DBIAS_NOSPLIT = 262144
 V_QDB64_ON, V_QDB64_OFF = 2097152, 4194304
 V_QDIAG_ON, V_QDIAG_OFF = 8388608, 16777216  # T5 bias, one-launch backward: the per-diagonal sums of the table gradient in the dQ workgroups always / never
+V_DTABLE_RUNS_ON, V_DTABLE_RUNS_OFF = 33554432, 67108864  # T5 table gradient: the per-bucket-run reduction wherever legal (the default) / never
 _variant = 0  # what the host mirror writes into every descriptor it builds; 0 = the library's own choice (production)
 
 
@@ -311,7 +313,8 @@ def kernel_ready(t):
     return (t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1]))
 
 
-def describe(B, H, M, N, D=64, dtype=FAT5_BF16, causal=False, bias_mode=0, radius=0, need_dbias=False, variant=0, sm_scale=None):
+def describe(B, H, M, N, D=64, dtype=FAT5_BF16, causal=False, bias_mode=0, radius=0, need_dbias=False, variant=0, sm_scale=None,
+             bucket=None, num_buckets=32):
     """Which kernel bodies the library would run for a problem -- {"fwd": "64row-ksplit", "dq": "32row", "dkdv": "64key-mixed:4",
     "fused": "0", "dbias": "direct"} -- from shapes alone (fat5_attn_describe: host-only, works without a GPU)."""
     p = AttnParams()
@@ -325,7 +328,11 @@ def describe(B, H, M, N, D=64, dtype=FAT5_BF16, causal=False, bias_mode=0, radiu
             p.dbias, p.dbias_batch, p.dbias_heads = 16, 1, H
     elif bias_mode == BIAS_RPE1D:
         p.rpe1d = 16
-        if need_dbias:
+        if need_dbias and bucket is not None:  # the (num_buckets, H) table gradient; `bucket`: the host bucket map (2R+1 ids)
+            host = (ctypes.c_int32 * len(bucket))(*[int(x) for x in bucket])
+            p.rpe_bucket, p.drpe_table, p.rpe_num_buckets = 16, 16, int(num_buckets)
+            p.rpe_bucket_host = ctypes.addressof(host)
+        elif need_dbias:
             p.drpe1d = 16
     buf = ctypes.create_string_buffer(256)
     check(load().fat5_attn_describe(ctypes.byref(p), buf, 256), "fat5_attn_describe")

@@ -691,6 +691,28 @@ static int bwd_layout(const fat5_attn_params* p, BwdLayout& L) {
   return rc;
 }
 
+// T5 table gradient in bucket-run form (drpe_runs_reduce_kernel): taken where the call asks for the (num_buckets, H) table only --
+// drpe_table set, drpe1d NULL -- and hands over a host copy of the bucket map in which every id in [0, num_buckets) occupies one
+// contiguous run of entries (ids outside that range stay out of the table, as in the per-diagonal form).  Not part of the cached
+// layout: it reads the map's contents, a few hundred ints per call.  No threshold: the reduction is one pass either way, the
+// run form skips the LDS pass of the per-diagonal sums and the scan of every entry for its bucket.
+static bool table_runs(const fat5_attn_params* p, BucketRuns* out) {
+  if (p->bias_mode != FAT5_BIAS_RPE1D || !p->drpe_table || p->drpe1d || !p->rpe_bucket_host || (p->variant & FAT5_V_DTABLE_RUNS_OFF)) return false;
+  const int nb = p->rpe_num_buckets, n1 = 2 * p->rpe_radius + 1;
+  if (nb <= 0 || nb > kMaxRunBuckets || p->rpe_radius < 0) return false;
+  BucketRuns r;
+  for (int b = 0; b < kMaxRunBuckets; ++b) r.lo[b] = r.len[b] = 0;
+  for (int i = 0; i < n1; ++i) {
+    const int b = p->rpe_bucket_host[i];
+    if (b < 0 || b >= nb) continue;
+    if (r.len[b] == 0) r.lo[b] = i;
+    else if (r.lo[b] + r.len[b] != i) return false;  // (a second run of the same id)
+    ++r.len[b];
+  }
+  if (out) *out = r;
+  return true;
+}
+
 size_t fat5_attn_bwd_workspace_bytes(const fat5_attn_params* p) {
   if (check_common(p)) return 0;
   BwdLayout L;
@@ -731,6 +753,13 @@ int fat5_attn_describe(const fat5_attn_params* p, char* out, size_t n) {
            L.qdb64 ? "64row-batch4" : (L.q64 ? "64row" : "32row"), kv, (fused || L.fused64 || L.dfused64) ? 1 : 0,
            L.qdb64 ? (L.qdb_groups > 1 ? "dq-kernel+partials" : "dq-kernel") : (L.dbias_inkernel ? "inkernel" : (L.ds_staged ? "staged" : "direct")),
            L.diag_q ? 1 : 0);  // (qdiag: T5 bias, the table gradient's per-diagonal sums come from the dQ workgroups)
+  // dtable: how the reduction launch forms the T5 table gradient -- "runs" (per bucket run, drpe_runs_reduce_kernel), "scan"
+  // (per-diagonal sums, then the scan of the entries for their bucket: drpe_reduce_kernel); absent without a table gradient.
+  // (The one pointer this function follows: the HOST copy of the bucket map.)
+  if (p->bias_mode == FAT5_BIAS_RPE1D && p->drpe_table && !p->drpe1d) {
+    const size_t used = strlen(out);
+    if (used < n) snprintf(out + used, n - used, " dtable=%s", table_runs(p, nullptr) ? "runs" : "scan");
+  }
   return FAT5_OK;
 }
 
@@ -930,7 +959,14 @@ int fat5_attn_bwd_stages(const fat5_attn_params* p, int stages, void* stream_) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "dbias_reduce launch");
   }
-  if (a.drpe_part && (stages & FAT5_BWD_REDUCE)) {
+  BucketRuns runs;
+  if (a.drpe_part && (stages & FAT5_BWD_REDUCE) && table_runs(p, &runs)) {
+    const long parts = (long)p->B * L.part_rows;
+    hipLaunchKernelGGL(drpe_runs_reduce_kernel, dim3(p->rpe_num_buckets, p->H), dim3(kRunsNT), 0, stream, a.drpe_part, p->drpe_table, runs, p->B,
+                       p->H, L.part_rows, 2 * p->rpe_radius + 1, p->unit_begin, p->unit_count, div_magic(L.part_rows, parts));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "drpe_runs_reduce launch");
+  } else if (a.drpe_part && (stages & FAT5_BWD_REDUCE)) {
     const int n1 = 2 * p->rpe_radius + 1;
     const size_t smem = (size_t)n1 * 24;
     if (smem > 48 * 1024) {

@@ -163,6 +163,61 @@ __global__ __launch_bounds__(1024) void drpe_reduce_kernel(const float* __restri
   }
 }
 
+// Bucket-run form of the T5 table gradient (drpe1d not asked for, every bucket id one contiguous run of entries: the T5 map).
+// The host reads the runs off its copy of the bucket map and passes them by value, so the launch starts with its only memory round
+// trip: dtable[bk][h] = sum over the (b, block) partial rows of (b, h) and the entries lo .. lo + len - 1 of bucket bk.  No LDS
+// pass of the per-diagonal sums, no per-entry bucket scan.  One workgroup per (bucket, head); lanes own a fixed set of (entry,
+// partial row) pairs -- W = min(len, NT) consecutive entries per group of lanes, groups strided over the partial rows --, then a
+// fixed butterfly per wave and the waves in order: the same bits on every run and in graph replay.
+constexpr int kMaxRunBuckets = 128;
+struct BucketRuns {  // (kernel argument: 1 KiB)
+  int32_t lo[kMaxRunBuckets];
+  int32_t len[kMaxRunBuckets];
+};
+constexpr int kRunsNT = 256;
+__global__ __launch_bounds__(kRunsNT) void drpe_runs_reduce_kernel(const float* __restrict__ part, float* __restrict__ dtable, const BucketRuns runs,
+                                                                   int B, int H, int nblk, int n1, int unit_begin, int unit_count, uint32_t mg_nblk) {
+  __shared__ float sw[kRunsNT / 64];
+  const int bk = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
+  const int lo = runs.lo[bk], len = runs.len[bk];
+  const int nparts = B * nblk;
+  float acc = 0.f;
+  if (len > 0) {
+    const int W = min(len, kRunsNT), G = kRunsNT / W;
+    const int jj = tid % W, g = tid / W;
+    if (g < G && g < nparts) {
+      const int nj = (len - jj + W - 1) / W, np = (nparts - g + G - 1) / G, n = nj * np;
+      const float* src = part + lo + jj;
+      int u = 0, v = 0;  // (partial row g + G u, entry jj + W v): v runs fastest
+      for (int f0 = 0; f0 < n; f0 += 16) {
+        float vv[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          vv[k] = 0.f;
+          if (f0 + k < n) {
+            const int pidx = g + G * u, b = fast_div(pidx, nblk, mg_nblk), blk = pidx - b * nblk;
+            // a unit-range call wrote the partial rows of its own units only (u = h * B + b): the others stay out of the sum
+            const bool mine = unit_count <= 0 || (unsigned)(h * B + b - unit_begin) < (unsigned)unit_count;
+            if (mine) vv[k] = src[(((int64_t)b * H + h) * nblk + blk) * n1 + W * v];
+            if (++v == nj) {
+              v = 0;
+              ++u;
+            }
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc += vv[k];  // (in the fixed order above; the zeros past n add nothing)
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((tid & 63) == 0) sw[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) dtable[(int64_t)bk * H + h] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+}
+static_assert(kRunsNT == 256, "the final sum above adds four waves");
+
 // rpe1d[h][i] = table[bucket[i]][h] as fp32: the (H, 2R+1) Toeplitz generator of the T5 bias from the (num_buckets, H) table
 // (reference: the embedding lookup + permute of RelativePositionalEncoding.compute_bias, src/utils/positional_encoding.py:100-101,
 //  restricted to the 2R+1 distinct relative positions).  One launch per forward call: the generator is never cached across

@@ -679,6 +679,14 @@ class AttentionPlan:
                 self.rpe_bucket = rpe_bucket
                 self.dbias = torch.empty((num_buckets, H), dtype=torch.float32, device=dev)
                 p.rpe_bucket, p.drpe_table, p.rpe_num_buckets = rpe_bucket.data_ptr(), self.dbias.data_ptr(), num_buckets
+                # the same ids on the host, copied once per plan (not while a graph is being captured): the library reads the bucket
+                # runs of the table gradient off them at every call
+                host = _pe.host_bucket_map(rpe_bucket)
+                if host is None and not (rpe_bucket.is_cuda and torch.cuda.is_current_stream_capturing()):
+                    host = rpe_bucket.detach().to("cpu", torch.int32).contiguous()
+                self.rpe_bucket_host = host
+                if host is not None:
+                    p.rpe_bucket_host = host.data_ptr()
             elif need_dbias:
                 self.dbias = torch.empty_like(rpe1d)
                 p.drpe1d = self.dbias.data_ptr()

@@ -76,7 +76,18 @@ def bucket_index32(radius, bidirectional, num_buckets, max_distance, device):
     if idx is None:
         idx = bucket_index(radius, bidirectional, num_buckets, max_distance, device).to(torch.int32).contiguous()
         _IDX_CACHE[key] = idx
+        # the same ids on the host (the C ABI's `rpe_bucket_host`: the library reads the bucket runs of the table gradient off it)
+        _HOST_OF[id(idx)] = (idx, _bucket_index_cpu(radius, bool(bidirectional), num_buckets, max_distance).to(torch.int32).contiguous())
     return idx
+
+
+_HOST_OF = {}  # id(device map from bucket_index32) -> (that map, its host copy); both live as long as the cache
+
+
+def host_bucket_map(rpe_bucket):
+    """The host copy of a bucket map made by `bucket_index32`, or None for any other tensor (no device read, no sync)."""
+    ent = _HOST_OF.get(id(rpe_bucket))
+    return ent[1] if ent is not None and ent[0] is rpe_bucket else None
 
 
 def rpe_radius(max_distance):

@@ -55,7 +55,8 @@ enum fat5_variant {
   FAT5_V_FWD64_MIX_ON = 524288, FAT5_V_FWD64_MIX_OFF = 1048576,  /* 64-row forward: 256-row and key-split 128-row workgroups in ONE launch wherever legal / never */
   FAT5_V_DBIAS_NOSPLIT = 262144,                                 /* batch-inner dbias kernel: the one-group form (one wave per SIMD) of rounds 2-3 */
   FAT5_V_QDB64_ON = 2097152, FAT5_V_QDB64_OFF = 4194304,        /* dense (1,H,M,N) bias, bf16, D = 64: dQ and the batch-reduced dbias in one kernel, four batch elements per workgroup (attn_bwd_qdb64.h) wherever legal / never */
-  FAT5_V_QDIAG_ON = 8388608, FAT5_V_QDIAG_OFF = 16777216,       /* T5 bias, one-launch 64-wide backward: the table gradient's per-diagonal sums formed by the dQ workgroups (attn_bwd_q64_body<QDG>) wherever that launch runs / never */
+  FAT5_V_QDIAG_ON = 8388608, FAT5_V_QDIAG_OFF = 16777216,       /* (continued below) */
+  FAT5_V_DTABLE_RUNS_ON = 33554432, FAT5_V_DTABLE_RUNS_OFF = 67108864, /* T5 table gradient: the per-bucket reduction over the runs of rpe_bucket_host wherever legal (the default) / never (the per-diagonal reduction + bucket scan) */       /* T5 bias, one-launch 64-wide backward: the table gradient's per-diagonal sums formed by the dQ workgroups (attn_bwd_q64_body<QDG>) wherever that launch runs / never */
   FAT5_V_FUSED64_ON = 65536, FAT5_V_FUSED64_OFF = 131072         /* backward: the 64-wide dK/dV and dQ bodies in ONE launch (the dK/dV half forms its row statistics itself) wherever legal / never; dense (1,H,M,N) bias: the dense dK/dV body beside the dQ + dBias body in one launch behind a small row-statistics kernel */
 };
 
@@ -135,6 +136,12 @@ typedef struct fat5_attn_params {
                                variables, no process-wide switches: the choice is part of the call). */
   void* workspace;          /* size from fat5_attn_bwd_workspace_bytes(); 256-B aligned */
   size_t workspace_bytes;
+  /* RPE1D with drpe_table, optional (appended at the end: the fields above keep their offsets): a HOST copy of rpe_bucket, the same 2R+1 ids.  Where every bucket id of it
+   * occupies one contiguous run of entries (the T5 map) and drpe1d is NULL, the reduction launch sums each bucket's run of the
+   * partial rows straight into drpe_table (one pass, no per-entry bucket scan); the runs travel as kernel arguments, so the
+   * array is read on the host at every backward call (and by fat5_attn_describe) and may be freed after it.  NULL: the
+   * per-diagonal reduction. */
+  const int32_t* rpe_bucket_host;
 } fat5_attn_params;
 
 int fat5_version(void);
