@@ -550,6 +550,9 @@ __global__ __launch_bounds__(1024) void rmsnorm_dw_reduce_kernel(const float* __
 // Cross-entropy forward: one 256-thread workgroup per row, online max / sum-exp per thread over
 // 16-byte chunks, then a workgroup combine.
 // ---------------------------------------------------------------------------------------------
+// The reference point of a thread's running sum: its running max, or 0 while that is still -inf (every logit it has seen is -inf,
+// e.g. a masked part of the vocabulary) -- exp2(-inf - -inf) would be NaN, and a NaN l survives every later rescale by 0.
+FAT5_DEV float ref_max(float mn) { return mn == -INFINITY ? 0.f : mn; }
 template <int DT, bool VECOK>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* __restrict__ logits_, const int64_t* __restrict__ labels,
                                                      float* __restrict__ losses, float* __restrict__ z_losses,
@@ -578,19 +581,19 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* __restrict__ lo
           cm = fmaxf(cm, f[j]);
           sum_logits += f[j];
         }
-        const float mn = fmaxf(m, cm);
+        const float mn = fmaxf(m, cm), mr = ref_max(mn);
         float acc = 0.f;
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) acc += fast_exp2((f[j] - mn) * kLog2e);
-        l = l * fast_exp2((m - mn) * kLog2e) + acc;
+        for (int j = 0; j < VEC; ++j) acc += fast_exp2((f[j] - mr) * kLog2e);
+        l = l * fast_exp2((m - mr) * kLog2e) + acc;
         m = mn;
       }
     } else {
       for (int c = tid; c < n_cols; c += 256) {
         const float f = X::ld1(x + c) * logit_scale;
         sum_logits += f;
-        const float mn = fmaxf(m, f);
-        l = l * fast_exp2((m - mn) * kLog2e) + fast_exp2((f - mn) * kLog2e);
+        const float mn = fmaxf(m, f), mr = ref_max(mn);
+        l = l * fast_exp2((m - mr) * kLog2e) + fast_exp2((f - mr) * kLog2e);
         m = mn;
       }
     }
@@ -715,11 +718,11 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(const void* logits_, co
       cm = fmaxf(cm, t[j]);
       sum_logits += t[j];
     }
-    const float mn = fmaxf(m, cm);
+    const float mn = fmaxf(m, cm), mr = ref_max(mn);
     float acc = 0.f;
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) acc += fast_exp2((t[j] - mn) * kLog2e);
-    l = l * fast_exp2((m - mn) * kLog2e) + acc;
+    for (int j = 0; j < VEC; ++j) acc += fast_exp2((t[j] - mr) * kLog2e);
+    l = l * fast_exp2((m - mr) * kLog2e) + acc;
     m = mn;
   };
   if constexpr (HOLD) {
