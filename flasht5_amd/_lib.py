@@ -86,6 +86,16 @@ class DecodeParams(ctypes.Structure):
     ]
 
 
+class SampleParams(ctypes.Structure):
+    """Mirror of `fat5_sample_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("V", ctypes.c_int32), ("dtype", ctypes.c_int32), ("top_k", ctypes.c_int32),
+        ("logits", ctypes.c_void_p), ("row_stride", ctypes.c_int64), ("temperature", ctypes.c_float), ("top_p", ctypes.c_float),
+        ("seed", ctypes.c_uint64), ("offset", ctypes.c_int64), ("offsets", ctypes.c_void_p), ("uniforms", ctypes.c_void_p),
+        ("tokens", ctypes.c_void_p), ("aux", ctypes.c_void_p),
+    ]
+
+
 EXPORTS = (
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
@@ -95,6 +105,7 @@ EXPORTS = (
     "fat5_rope_apply", "fat5_sizeof_rope_params",
     "fat5_fire_fwd", "fat5_fire_bwd", "fat5_fire_bwd_workspace_bytes", "fat5_sizeof_fire_params",
     "fat5_attn_decode", "fat5_attn_decode_workspace_bytes", "fat5_sizeof_decode_params",
+    "fat5_sample_logits", "fat5_sizeof_sample_params",
 )
 
 _lib = None
@@ -190,6 +201,12 @@ def load():
     if lib.fat5_sizeof_decode_params() != ctypes.sizeof(DecodeParams):
         raise ImportError(f"fat5_decode_params layout mismatch: library {lib.fat5_sizeof_decode_params()} B, "
                           f"binding {ctypes.sizeof(DecodeParams)} B")
+    lib.fat5_sample_logits.restype = ctypes.c_int
+    lib.fat5_sample_logits.argtypes = [ctypes.POINTER(SampleParams), ctypes.c_void_p]
+    lib.fat5_sizeof_sample_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_sample_params() != ctypes.sizeof(SampleParams):
+        raise ImportError(f"fat5_sample_params layout mismatch: library {lib.fat5_sizeof_sample_params()} B, "
+                          f"binding {ctypes.sizeof(SampleParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

@@ -19,6 +19,7 @@
 #include "rope_kernels.h"
 #include "fire_kernels.h"
 #include "decode_kernels.h"
+#include "sample_kernels.h"
 
 using namespace fat5;
 
@@ -1591,6 +1592,56 @@ int fat5_attn_decode(const fat5_decode_params* p, void* stream_) {
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "attn_decode launch");
+  return FAT5_OK;
+}
+
+// ---- temperature / top-k / top-p sampling (sample_kernels.h) ----
+size_t fat5_sizeof_sample_params(void) { return sizeof(fat5_sample_params); }
+
+int fat5_sample_logits(const fat5_sample_params* p, void* stream_) {
+  const char* what = "sample_logits";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (p->B < 0) return fail(FAT5_EINVAL, "%s: B %d", what, p->B);
+  if (p->V < 1 || p->V > SAMPLE_MAX_V) return fail(FAT5_EINVAL, "%s: V %d outside [1, %d]", what, p->V, SAMPLE_MAX_V);
+  if (p->dtype != FAT5_F32 && p->dtype != FAT5_F16 && p->dtype != FAT5_BF16) return fail(FAT5_EINVAL, "%s: dtype %d", what, p->dtype);
+  if (!std::isfinite(p->temperature) || !(p->temperature > 0.f))
+    return fail(FAT5_EINVAL, "%s: temperature %g (finite and > 0)", what, (double)p->temperature);
+  if (p->top_k < 0) return fail(FAT5_EINVAL, "%s: top_k %d (>= 0)", what, p->top_k);
+  if (!(p->top_p > 0.f && p->top_p <= 1.f)) return fail(FAT5_EINVAL, "%s: top_p %g outside (0, 1]", what, (double)p->top_p);
+  const size_t es = p->dtype == FAT5_F32 ? 4 : 2;
+  if (p->B > 1 && p->row_stride < p->V) return fail(FAT5_EINVAL, "%s: row_stride %lld < V %d", what, (long long)p->row_stride, p->V);
+  if (!p->logits || (reinterpret_cast<uintptr_t>(p->logits) % es)) return fail(FAT5_EINVAL, "%s: logits: null or misaligned pointer", what);
+  if (!p->tokens || (reinterpret_cast<uintptr_t>(p->tokens) & 7)) return fail(FAT5_EINVAL, "%s: tokens: null or misaligned pointer", what);
+  if (p->offsets && (reinterpret_cast<uintptr_t>(p->offsets) & 3)) return fail(FAT5_EINVAL, "%s: offsets misaligned", what);
+  if (p->uniforms && (reinterpret_cast<uintptr_t>(p->uniforms) & 3)) return fail(FAT5_EINVAL, "%s: uniforms misaligned", what);
+  if (p->aux && (reinterpret_cast<uintptr_t>(p->aux) & 3)) return fail(FAT5_EINVAL, "%s: aux misaligned", what);
+  if (p->B == 0) return FAT5_OK;
+  SampleArgs a = {};
+  a.logits = p->logits;
+  a.stride = p->row_stride;
+  a.offsets = p->offsets;
+  a.uniforms = p->uniforms;
+  a.tokens = p->tokens;
+  a.aux = p->aux;
+  a.seed = p->seed;
+  a.offset = p->offset;
+  a.V = p->V;
+  a.top_k = p->top_k;
+  a.temperature = p->temperature;
+  a.top_p = p->top_p;
+  a.vec = aligned16(p->logits) && (p->B == 1 || p->row_stride % 8 == 0);
+  hipStream_t stream = (hipStream_t)stream_;
+  const bool reg = p->V <= SAMPLE_REG_TILES * SAMPLE_TILE;
+  auto go = [&](auto dt_) {
+    constexpr int DT = decltype(dt_)::value;
+    if (reg) hipLaunchKernelGGL((sample_logits_kernel<DT, SAMPLE_REG_TILES>), dim3(p->B), dim3(SAMPLE_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((sample_logits_kernel<DT, 0>), dim3(p->B), dim3(SAMPLE_THREADS), 0, stream, a);
+  };
+  if (p->dtype == FAT5_F32) go(IC<FAT5_F32>{});
+  else if (p->dtype == FAT5_F16) go(IC<FAT5_F16>{});
+  else go(IC<FAT5_BF16>{});
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "sample_logits launch");
   return FAT5_OK;
 }
 

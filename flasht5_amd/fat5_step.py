@@ -11,10 +11,10 @@ A minimal encoder-decoder with the reference's structure (src/model/modeling_fla
   * loss           -> `FlashT5CrossEntropyLoss` (cross_entropy_loss with z-loss and label smoothing, HIP)
   * everything else is plain torch-ROCm: `nn.Linear` (hipBLASLt), `nn.Embedding`, tanh-GELU gating, residual adds.
 
-Generation: `generate` (greedy, the reference's algorithm and return value) and `decode_step` run one new token per step through
+Generation: `generate` (greedy -- the reference's algorithm and return value -- or sampled) and `decode_step` run one new token per step through
 the decoder against per-layer KV caches (flasht5_amd/generation.py, the split-KV decode kernel), optionally replayed from a HIP graph.
 
-This is the step DRIVER of the hot path, not a model zoo: no beam search or sampling, heads, dropout (0 in every reference config),
+This is the step DRIVER of the hot path, not a model zoo: no beam search, heads, dropout (0 in every reference config),
 HF plumbing or checkpoint conversion.  Data parallelism = one process per GPU; `allreduce_gradients` is the step's one
 exchange (RCCL over xGMI): a single flat fp32 all-reduce that carries the two `(32, H)` relative-position tables first.
 """
@@ -233,7 +233,7 @@ class FAT5Stack(nn.Module):  # :394-464
         return self.final_layer_norm(h)
 
 
-class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; cached greedy generation in generation.py)
+class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; cached greedy / sampled generation in generation.py)
     def __init__(self, config: FAT5Config):
         super().__init__()
         import copy
@@ -308,10 +308,13 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         from .generation import decode_step
         return decode_step(self, state, token_ids)
 
-    def generate(self, input_ids, attention_mask=None, max_length=32, graph=False):
-        """greedy decoding with a KV cache; returns what the reference's generate returns (generation.generate)"""
+    def generate(self, input_ids, attention_mask=None, max_length=32, graph=False, *, do_sample=False, temperature=1.0, top_k=50,
+                 top_p=1.0, seed=None):
+        """greedy (or, with do_sample=True, temperature / top-k / top-p sampled) decoding with a KV cache; returns what the
+        reference's generate returns (generation.generate)"""
         from .generation import generate
-        return generate(self, input_ids, attention_mask, max_length, graph)
+        return generate(self, input_ids, attention_mask, max_length, graph, do_sample=do_sample, temperature=temperature,
+                        top_k=top_k, top_p=top_p, seed=seed)
 
 
 def allreduce_gradients(model: nn.Module, group=None, average=True):

@@ -1,10 +1,11 @@
-"""KV-cached greedy generation for `FAT5ForConditionalGeneration` (the reference's `generate`, src/model/modeling_flash_t5.py:648-690,
+"""KV-cached greedy and sampled generation for `FAT5ForConditionalGeneration` (the reference's `generate`, src/model/modeling_flash_t5.py:648-690,
 reruns the whole decoder over every token so far at every step; here each step runs ONE new token through the decoder against
 per-layer caches).
 
     state = model.init_decode_state(input_ids, max_length=32)   # encoder once, cross K / V once per layer
     logits = model.decode_step(state, token_ids)                 # (B, vocab) for the next position; the caches grow by one
     labels = model.generate(input_ids, max_length=32, graph=True)
+    labels = model.generate(input_ids, do_sample=True, temperature=0.7, top_k=50, top_p=0.9, seed=1234, graph=True)
 
 What a step runs: the embedding of the new token, then per decoder block the self-attention (q, k, v projected from the one row,
 k and v appended to the layer's cache by the decode kernel, the T5 bias of block 0's `forward_1d()` bottom-right aligned), the
@@ -12,6 +13,9 @@ cross-attention against the encoder's K / V, and the feed-forward sub-layer -- t
 training forward (a bf16 model, or fp32 weights under bf16 autocast).  `cache_seqlens` is one (B,) int32 device tensor shared by
 every self-attention cache and incremented on the device at the end of each step; nothing a step reads comes from the host, so
 `graph=True` captures one step once and replays it per token.
+
+Sampling (`do_sample=True`) replaces the argmax by `sample_logits` (one HIP launch: temperature, top-k, top-p and a Philox draw
+keyed by the call's seed with the token's position, cache_seqlens, as the counter), so it is captured and replayed the same way.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -118,6 +122,19 @@ def _greedy_step(model, state, tok, labels, seen_eos):
     seen_eos.logical_or_(nxt == 1)
 
 
+def _sample_step(model, state, tok, labels, seen_eos, sampling):
+    """decode_step + sample_logits, with _greedy_step's bookkeeping; the Philox counter of row b is cache_seqlens[b] after the
+    increment (the new token's position), read on the device -- so the captured step draws a fresh uniform at every replay"""
+    from .sampling import sample_logits
+    temperature, top_k, top_p, seed = sampling
+    logits = decode_step(model, state, tok)
+    nxt = sample_logits(logits, temperature, top_k, top_p, seed=seed, offsets=state.cache_seqlens)
+    tok.copy_(nxt)
+    col = state.cache_seqlens.long().unsqueeze(1)
+    labels.scatter_(1, col, nxt.unsqueeze(1))
+    seen_eos.logical_or_(nxt == 1)
+
+
 def finish_labels(labels):
     """the reference's ending (:682-688): the last column becomes 1, and everything after each row's first 1 becomes 0"""
     labels = labels.clone()
@@ -129,13 +146,30 @@ def finish_labels(labels):
 
 
 @torch.no_grad()
-def generate(model, input_ids, attention_mask=None, max_length=32, graph=False):
+def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, *, do_sample=False, temperature=1.0, top_k=50,
+             top_p=1.0, seed=None):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
+
+    do_sample=True draws each token with `sample_logits` instead of the argmax (HF's GenerationConfig defaults: temperature 1,
+    top_k 50, top_p 1): row b's token at position t uses the Philox counter t with the row index b, under one seed per call --
+    `seed`, or one drawn from torch's default CPU generator when it is None (so torch.manual_seed makes runs reproducible).
+    With do_sample=True the arguments are checked on the host before the encoder runs; with do_sample=False they are neither
+    checked nor used.
 
     graph=True captures one decoding step (for this batch and capacity) once in a HIP graph on one stream and replays it per
     token; the first step runs eagerly (it also builds what the step allocates lazily), so both modes run the same kernels with the
     same arguments and give the same tokens."""
+    step = _greedy_step
+    if do_sample:
+        from .sampling import check_args
+        check_args(temperature, top_k, top_p)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64))
+        sampling = (float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+        def step(model, state, tok, labels, seen_eos):
+            _sample_step(model, state, tok, labels, seen_eos, sampling)
     B = input_ids.shape[0]
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask)
@@ -149,26 +183,26 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False):
             if g is not None:
                 g.replay()
             else:
-                _greedy_step(model, state, tok, labels, seen_eos)
+                step(model, state, tok, labels, seen_eos)
             steps += 1
             if bool(seen_eos.all()):
                 break
             if graph and g is None and steps < max_length:  # (after the stop check: no capture when the first step ends it)
-                g = _capture(model, state, tok, labels, seen_eos)
+                g = _capture(model, state, tok, labels, seen_eos, step)
     finally:
         del g
     return finish_labels(labels[:, :steps + 1])
 
 
-def _capture(model, state, tok, labels, seen_eos):
-    """one greedy step captured in a HIP graph (nothing runs during the capture: the state is unchanged)"""
+def _capture(model, state, tok, labels, seen_eos, step=_greedy_step):
+    """one decoding step (greedy by default) captured in a HIP graph (nothing runs during the capture: the state is unchanged)"""
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     ac = torch.is_autocast_enabled()
     with torch.cuda.graph(g):  # (torch's capture stream: one stream, no parallel branches)
         if ac:  # (autocast's weight-cast cache must not hand tensors from outside the capture to it)
             with torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False):
-                _greedy_step(model, state, tok, labels, seen_eos)
+                step(model, state, tok, labels, seen_eos)
         else:
-            _greedy_step(model, state, tok, labels, seen_eos)
+            step(model, state, tok, labels, seen_eos)
     return g

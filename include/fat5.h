@@ -393,6 +393,45 @@ size_t fat5_attn_decode_workspace_bytes(const fat5_decode_params* p);
 int fat5_attn_decode(const fat5_decode_params* p, void* hip_stream);
 
 /*
+ * Temperature / top-k / top-p sampling: one token per logits row in one launch (sample_kernels.h), HF's warper order
+ * (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper, then a draw).  The reference's generate has no sampling.
+ *   x_j = float(logits[b, j]) / temperature (an fp32 division);
+ *   top-k (0 < top_k < V): keep x_j >= tau_k, the top_k-th largest x counting duplicates (ties at the threshold are kept);
+ *   e_j = exp(x_j - max x) over the kept tokens, S their sum;
+ *   top-p (top_p < 1): keep x_j >= tau_p, the smallest kept x with C(x) > (1 - top_p) * S, C(z) = sum of e over kept x <= z;
+ *   draw: u in [0, 1) is (word0 >> 8) * 2^-24 of Philox4x32-10 with key (seed lo, seed hi) and counter
+ *   (lo, hi of offset + offsets[b], b, 0) -- or uniforms[b] when given; the token is the smallest kept j, in vocabulary order,
+ *   whose inclusive prefix sum of e exceeds u * S_kept.
+ * The masses are exact uint64 sums of the fp32 e_j truncated to multiples of 2^-40 (order-free, so bitwise reproducible).
+ * A row whose x holds a NaN or +inf, or only -inf, gives torch.argmax's index (first NaN, else first +inf, else 0).
+ * aux (optional, (B, 4) fp32 contiguous): the lowest kept x (tau), S_kept / S (S after top-k), u, the kept count; NaN, NaN, u, 0
+ * on a degenerate row.  The grid is (B): a row's token depends only on its logits, seed and counter, never on B.
+ * Rows: logits + b * row_stride elements; 16-byte vector loads when the base is 16-byte aligned and row_stride a multiple of 8,
+ * element loads otherwise.  B == 0 is a no-op.
+ * Rejected with FAT5_EINVAL before anything is launched: B < 0, V outside [1, 2^20], dtype outside {FAT5_F32, FAT5_F16,
+ * FAT5_BF16}, a non-finite or non-positive temperature, top_k < 0, top_p outside (0, 1], row_stride < V with B > 1, NULL or
+ * misaligned logits / tokens / offsets / uniforms / aux.
+ */
+typedef struct fat5_sample_params {
+  int32_t B, V;
+  int32_t dtype;              /* FAT5_F32 | FAT5_F16 | FAT5_BF16 */
+  int32_t top_k;              /* 0 (or >= V): no top-k */
+  const void* logits;         /* (B, V), row stride row_stride elements, innermost stride 1 */
+  int64_t row_stride;
+  float temperature;          /* > 0, finite */
+  float top_p;                /* (0, 1]; 1: no top-p */
+  uint64_t seed;              /* Philox key */
+  int64_t offset;             /* added to every row's counter */
+  const int32_t* offsets;     /* (B,) int32 device array (per-row counters, e.g. the position), or NULL */
+  const float* uniforms;      /* (B,) fp32 device array replacing the Philox draw, or NULL */
+  int64_t* tokens;            /* (B,) int64 out */
+  float* aux;                 /* (B, 4) fp32 out, or NULL */
+} fat5_sample_params;
+/* sizeof(fat5_sample_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_sample_params(void);
+int fat5_sample_logits(const fat5_sample_params* p, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)
