@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: FA2 + T5-bias forward+backward TFLOP/s (bf16, d_head = 64).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--seq 512] [--mode rpe|dense|none] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--seq 512] [--mode rpe|dense|none] [--dump-outputs DIR] [--full]
 
 A step = one forward + one backward of the attention hot path over one synthetic batch
 (B,H,S,D) = (4,12,S,64), bias = 32-bucket T5 relative-position bias, inputs resident in HBM, every kernel
@@ -10,9 +10,12 @@ launched through the C ABI of libfat5.so and replayed from a HIP graph.  At N > 
   --scaling strong the ONE (4,12,S,64) batch is split over the ranks by (batch, head) units (head-major chunks):
                    a rank runs its unit range in one forward and one backward call (fat5_attn_params.unit_begin/unit_count);
 either way the step ends with ONE all-reduce (RCCL over xGMI) of the (32,12) bias-table gradient.
-Prints ONE JSON line on rank 0 (see the repo task contract); extra keys: by_seq, kernels, roofline, cpu_baseline,
-eager_autograd (the drop-in autograd.Function path, no plan / graph), rowwise (RMSNorm, CE bandwidth), reference_shape
-(the reference's own published benchmark shape).
+Prints ONE JSON line on rank 0 (see the repo task contract).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line: nothing else.  --full measures the rest after the timed steps (the headline is taken
+the same way either way): one_replay_per_step (the same steps at one graph replay each), bias_grad_allreduce_ms (N > 1),
+and, unless --no-extras (which implies --full), the keys by_seq, kernels, roofline, cpu_baseline, eager_autograd (the
+drop-in autograd.Function path, no plan / graph), rowwise (RMSNorm, CE bandwidth), reference_shape (the reference's own
+published benchmark shape), d128_forward, dense_by_seq, n3_fusions.
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last step computed (o, dq, dk, dv and the bias(-table)
 gradient) as DIR/<name>.npy in float32; the inputs come from a fixed seed, so two builds can be compared output for output.
 """
@@ -724,12 +727,17 @@ def main():
                     "With more than one rank the default is ONE step per replay and one all-reduce per step (see --bucket-allreduce)")
     ap.add_argument("--bucket-allreduce", action="store_true", help="N > 1 only: keep --graph-steps steps per replay and send their bias(-table) gradients in ONE "
                     "all-reduce per replay (what DDP's bucketing does with small gradients).  NOT the default: a data-parallel step cannot defer its gradient "
-                    "past its own optimizer step, so the default N > 1 line runs exactly one all-reduce per step; with this flag the line also reports the per-step form")
-    ap.add_argument("--no-extras", action="store_true", help="skip by_seq / cpu baseline (profiling runs)")
+                    "past its own optimizer step, so the default N > 1 line runs exactly one all-reduce per step; with --full the line also reports the per-step form")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure the one-replay-per-step form, the all-reduce alone "
+                    "(N > 1) and the extras (by_seq, kernels, roofline, other shapes and precisions, row-wise kernels, CPU baseline, ...); "
+                    "a plain run measures the headline only")
+    ap.add_argument("--no-extras", action="store_true", help="--full without by_seq / cpu baseline and the other extras: the headline, "
+                    "one_replay_per_step and (N > 1) bias_grad_allreduce_ms (profiling runs)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's outputs (o, dq, dk, dv, bias(-table) gradient) as DIR/<name>.npy, "
                     "float32, at most 64 MB in all (a fixed, seeded sample of each tensor beyond that)")
     args = ap.parse_args()
+    args.full = args.full or args.no_extras  # --no-extras: everything --full measures but the extras
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and args.scaling == "strong" and args.gpus > 1:
@@ -976,7 +984,7 @@ def main():
 
     elapsed, n_ar, host_s = timed("replay-u")
     per_step_form = None
-    if graph_u is not None:
+    if args.full and graph_u is not None:
         # the other launch form beside the headline: one replay (and, N > 1, one all-reduce enqueued from Python) per step
         e1, n1, h1 = timed("per-step", OverlappedGradReduce(plan.dbias) if want_reduce else None)
         per_step_form = {"ms_per_step": round(e1 / args.steps * 1e3, 5), "launch": "hipGraph replay, 1 step per replay",
@@ -984,13 +992,19 @@ def main():
         if want_reduce:
             per_step_form["allreduces_per_step"] = round(n1 / args.steps, 4)
     dumped = None
-    if args.dump_outputs and rank == 0:  # (before the extras below: they launch single stages of the same plan)
+    if args.dump_outputs and rank == 0:  # (before the --full extras below: they launch single stages of the same plan)
+        if per_step_form is None and lp["allreduce"] == "in-graph":
+            # the dump holds this rank's own last step, which the one-replay-per-step form leaves in plan.dbias (its all-reduces run on the
+            # reducer's copies); the captured all-reduces of the timed region leave the sum over the ranks there instead.  Without that form,
+            # one untimed replay of the one-step graph (no collective in it) puts the rank's own gradient back.
+            graph.replay()
+            torch.cuda.synchronize()
         dumped = dump_outputs({"o": plan.o, "dq": plan.dq, "dk": plan.dk, "dv": plan.dv, "dbias": plan.dbias}, args.dump_outputs)
     ms_per_step = elapsed / args.steps * 1e3
     flops_step = 3.5 * fwd_flops(S) * (1 if strong else world)
     value = flops_step / (ms_per_step * 1e-3) / 1e12
     ar_ms = None
-    if world > 1 and plan.dbias is not None:  # the all-reduce alone (blocking), reported beside the step time
+    if args.full and world > 1 and plan.dbias is not None:  # the all-reduce alone (blocking), reported beside the step time
         buf = plan.dbias.float().clone()
         for _ in range(5):
             dist.all_reduce(buf)
@@ -1016,6 +1030,7 @@ def main():
             "per_gpu_tflops": round(value / world, 2),
             # host time spent enqueueing the timed region / steps (graph replays and, in the per-step form, collectives): the loop is device-bound while this stays below ms_per_step
             "host_enqueue_ms_per_step": round(host_s / args.steps * 1e3, 5),
+            "full": args.full,
         }
         if want_reduce:
             # collectives this rank submitted inside the timed region / steps: 1.0 = the north star's "single RCCL all-reduce of the bias
@@ -1033,9 +1048,9 @@ def main():
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if ar_ms is not None:
             out["bias_grad_allreduce_ms"] = round(ar_ms, 4)
-            if strong:
-                out["heads_needing_reduction"] = heads_needing_reduction(B, H, world)
-        if not args.no_extras:
+        if strong and plan.dbias is not None:
+            out["heads_needing_reduction"] = heads_needing_reduction(B, H, world)
+        if args.full and not args.no_extras:
             iters = max(10, min(args.steps, 50))
             kern, timed = kernel_breakdown(plan, S, iters)
             dom = max(timed, key=lambda n: kern[n]["us"])
