@@ -83,6 +83,7 @@ class DecodeParams(ctypes.Structure):
         ("q_stride", ctypes.c_int64 * 2), ("k_cache_stride", c_i64x3), ("v_cache_stride", c_i64x3),
         ("k_new_stride", ctypes.c_int64 * 2), ("v_new_stride", ctypes.c_int64 * 2), ("o_stride", ctypes.c_int64 * 2),
         ("num_splits", ctypes.c_int32), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+        ("cache_batch_idx", ctypes.c_void_p), ("cache_row_batch", ctypes.c_void_p), ("cache_B", ctypes.c_int32),
     ]
 
 
@@ -96,6 +97,19 @@ class SampleParams(ctypes.Structure):
     ]
 
 
+class BeamParams(ctypes.Structure):
+    """Mirror of `fat5_beam_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("k", ctypes.c_int32), ("V", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("logits", ctypes.c_void_p), ("row_stride", ctypes.c_int64), ("running_scores", ctypes.c_void_p),
+        ("running_seqs", ctypes.c_void_p), ("cache_row_batch", ctypes.c_void_p), ("finished_seqs", ctypes.c_void_p),
+        ("finished_scores", ctypes.c_void_p), ("finished_flags", ctypes.c_void_p), ("finished_lens", ctypes.c_void_p),
+        ("heuristic", ctypes.c_void_p), ("status", ctypes.c_void_p), ("tokens", ctypes.c_void_p), ("step", ctypes.c_void_p),
+        ("seq_len", ctypes.c_int32), ("capacity", ctypes.c_int32), ("max_length", ctypes.c_int32), ("early_stopping", ctypes.c_int32),
+        ("length_penalty", ctypes.c_float), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 EXPORTS = (
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
@@ -106,6 +120,7 @@ EXPORTS = (
     "fat5_fire_fwd", "fat5_fire_bwd", "fat5_fire_bwd_workspace_bytes", "fat5_sizeof_fire_params",
     "fat5_attn_decode", "fat5_attn_decode_workspace_bytes", "fat5_sizeof_decode_params",
     "fat5_sample_logits", "fat5_sizeof_sample_params",
+    "fat5_beam_step", "fat5_beam_step_workspace_bytes", "fat5_sizeof_beam_params",
 )
 
 _lib = None
@@ -207,6 +222,14 @@ def load():
     if lib.fat5_sizeof_sample_params() != ctypes.sizeof(SampleParams):
         raise ImportError(f"fat5_sample_params layout mismatch: library {lib.fat5_sizeof_sample_params()} B, "
                           f"binding {ctypes.sizeof(SampleParams)} B")
+    lib.fat5_beam_step.restype = ctypes.c_int
+    lib.fat5_beam_step.argtypes = [ctypes.POINTER(BeamParams), ctypes.c_void_p]
+    lib.fat5_beam_step_workspace_bytes.restype = ctypes.c_size_t
+    lib.fat5_beam_step_workspace_bytes.argtypes = [ctypes.POINTER(BeamParams)]
+    lib.fat5_sizeof_beam_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_beam_params() != ctypes.sizeof(BeamParams):
+        raise ImportError(f"fat5_beam_params layout mismatch: library {lib.fat5_sizeof_beam_params()} B, "
+                          f"binding {ctypes.sizeof(BeamParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

@@ -175,7 +175,8 @@ class FlashT5Attention(nn.Module):
         if self.position_encoding_type not in ("t5", "RoPE"):
             raise NotImplementedError(f"position_encoding_type {self.position_encoding_type!r} at decode time")
 
-    def forward_decode(self, hidden_states, k_cache, v_cache, cache_seqlens=None, position_bias=None, position=None):
+    def forward_decode(self, hidden_states, k_cache, v_cache, cache_seqlens=None, position_bias=None, position=None,
+                       cache_batch_idx=None, cache_row_batch=None):
         """One new token through this layer against a KV cache (flasht5_amd.decode.flash_attn_with_kvcache); returns (B, 1, d_model).
 
         Self-attention (`cache_seqlens` given): q, k and v are projected from `hidden_states` (B, 1, d_model), k and v are appended
@@ -183,7 +184,9 @@ class FlashT5Attention(nn.Module):
         the decoder's `position_bias = (rpe1d, R)` (block 0's `forward_1d()`, bottom-right aligned: the query sits at the last key).
         Cross-attention (`cache_seqlens` None): the caches hold the encoder's K / V (`project_kv`), all of them attended, no bias.
         RoPE: `position` is a (1,) int64 device tensor (the step's position, shared by the batch); q is rotated with row `position`
-        of (cos, sin), the new k and v with that row of (cos_k, sin_k).  Forward only; nothing of the training path changes."""
+        of (cos, sin), the new k and v with that row of (cos_k, sin_k).  Forward only; nothing of the training path changes.
+        Beam search: `cache_batch_idx` (B,) int32 lets B * k beam rows read B cross-attention caches; `cache_row_batch`
+        (B, L_cap) int32 reads each self-attention key row from the cache row of the beam that wrote it (decode.py)."""
         self.decode_supported()
         from .decode import flash_attn_with_kvcache
         B = hidden_states.shape[0]
@@ -210,7 +213,8 @@ class FlashT5Attention(nn.Module):
             rpe1d, radius = position_bias
             if self.attention_type == "triton":  # (the dense path adds the bias after a cast to the activation dtype)
                 rpe1d = rpe1d.to(q.dtype).float()
-        out = flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, self.softmax_scale, rpe1d, radius)
+        out = flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, self.softmax_scale, rpe1d, radius,
+                                      cache_batch_idx=cache_batch_idx, cache_row_batch=cache_row_batch)
         return self.o(out.reshape(B, 1, self.inner_dim))
 
     def project_kv(self, key_value_states):

@@ -18,6 +18,13 @@
 // is read, and nothing outside [0, capacity) is read or written, whatever cache_seqlens holds.
 // RPE1D bias: the query sits at p_b = L_b - 1 and bias[j] = rpe1d[h][clamp(j - p_b, -R, R) + R] (bottom-right aligned).
 // L_b == 0: o = 0, lse = -inf (the convention of the forward's fully masked rows).
+//
+// Indexed cache reads (beam search).  cache_batch_idx (B,): query row b reads batch element cache_batch_idx[b]
+// of the caches (flash_attn's meaning; the beams of one input share its encoder K / V).  cache_row_batch (B, capacity): key row
+// j < L_b of sequence b is read from batch element cache_row_batch[b * capacity + j] at row j (the ROWMAP instantiation; the beam
+// history as a table of parents instead of a reordered cache); the appended row is still read from k_new / v_new and written to
+// batch element b.  Every map entry is clamped to [0, cacheB), as the lengths are clamped.  Without maps the code and the bits are
+// those of the plain kernel (cb = b).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,12 +46,17 @@ struct DecodeArgs {
   float* lse;             // (B, H) contiguous, or null
   const int32_t* seqlens; // (B,) or null: every batch element uses N
   const float* rpe1d;     // (H, 2R + 1) or null: no bias
+  const int32_t* bidx;    // (B,) cache batch element of query row b, or null
+  const int32_t* rowmap;  // (B, cap) cache batch element of key row j of sequence b (ROWMAP only)
   float* ws;              // [B][H][S][2] (max, sum) then [B][H][S][D] o, fp32
   int64_t q_sb, q_sh, o_sb, o_sh, kn_sb, kn_sh, vn_sb, vn_sh;
   int64_t kc_s[3], vc_s[3];
   int32_t B, H, cap, N, R, splits;
+  int32_t cacheB;         // batch elements of the caches (map entries are clamped to [0, cacheB))
   float scale_log2;       // sm_scale * log2(e)
 };
+
+FAT5_DEV int decode_clamp_batch(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
 // the device-side key count of batch element b and whether (and where) it appends
 FAT5_DEV int decode_len(const DecodeArgs& a, int b, bool append, bool& do_append) {
@@ -54,7 +66,7 @@ FAT5_DEV int decode_len(const DecodeArgs& a, int b, bool append, bool& do_append
   return do_append ? len + 1 : len;
 }
 
-template <int DT, int D, bool APPEND, bool BIAS, bool DIRECT>
+template <int DT, int D, bool APPEND, bool BIAS, bool DIRECT, bool ROWMAP = false>
 __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) {
   typedef Elem<DT> E;
   typedef typename E::T T;
@@ -73,8 +85,10 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) 
 
   float qf[8];
   E::load(reinterpret_cast<const T*>(a.q) + (int64_t)b * a.q_sb + (int64_t)h * a.q_sh + t * 8, qf);
-  const T* kbase = reinterpret_cast<const T*>(a.kc) + (int64_t)b * a.kc_s[0] + (int64_t)h * a.kc_s[2] + t * 8;
-  const T* vbase = reinterpret_cast<const T*>(a.vc) + (int64_t)b * a.vc_s[0] + (int64_t)h * a.vc_s[2] + t * 8;
+  const int cb = a.bidx ? decode_clamp_batch(a.bidx[b], a.cacheB) : b;  // (never with an append: rejected on the host)
+  const T* kbase = reinterpret_cast<const T*>(a.kc) + (int64_t)cb * a.kc_s[0] + (int64_t)h * a.kc_s[2] + t * 8;
+  const T* vbase = reinterpret_cast<const T*>(a.vc) + (int64_t)cb * a.vc_s[0] + (int64_t)h * a.vc_s[2] + t * 8;
+  const int32_t* rmap = ROWMAP ? a.rowmap + (int64_t)b * a.cap : nullptr;
   const float* bias_row = BIAS ? a.rpe1d + (int64_t)h * (2 * a.R + 1) + a.R : nullptr;
 
   float m = -INFINITY, l = 0.f, acc[8];
@@ -92,6 +106,10 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) 
         if (APPEND && j == pnew) {
           E::load(reinterpret_cast<const T*>(a.kn) + (int64_t)b * a.kn_sb + (int64_t)h * a.kn_sh + t * 8, kf[u]);
           E::load(reinterpret_cast<const T*>(a.vn) + (int64_t)b * a.vn_sb + (int64_t)h * a.vn_sh + t * 8, vf[u]);
+        } else if constexpr (ROWMAP) {
+          const int64_t db = (int64_t)(decode_clamp_batch(rmap[j], a.cacheB) - b);  // (rows [0, L_b) of row b's parents)
+          E::load(kbase + db * a.kc_s[0] + (int64_t)j * a.kc_s[1], kf[u]);
+          E::load(vbase + db * a.vc_s[0] + (int64_t)j * a.vc_s[1], vf[u]);
         } else {
           E::load(kbase + (int64_t)j * a.kc_s[1], kf[u]);
           E::load(vbase + (int64_t)j * a.vc_s[1], vf[u]);

@@ -20,6 +20,7 @@
 #include "fire_kernels.h"
 #include "decode_kernels.h"
 #include "sample_kernels.h"
+#include "beam_kernels.h"
 
 using namespace fat5;
 
@@ -1533,21 +1534,36 @@ static int decode_check(const fat5_decode_params* p) {
       if (e.st[i] % 8) return fail(FAT5_EINVAL, "%s: %s strides must be multiples of 8 elements (innermost stride 1)", what, e.name);
   }
   if (p->lse && (reinterpret_cast<uintptr_t>(p->lse) & 3)) return fail(FAT5_EINVAL, "%s: lse misaligned", what);
+  if (p->cache_batch_idx && p->cache_row_batch)
+    return fail(FAT5_EINVAL, "%s: cache_batch_idx and cache_row_batch cannot be combined", what);
+  if (p->cache_batch_idx && p->k_new) return fail(FAT5_EINVAL, "%s: cache_batch_idx cannot be combined with an append", what);
+  if ((reinterpret_cast<uintptr_t>(p->cache_batch_idx) & 3) || (reinterpret_cast<uintptr_t>(p->cache_row_batch) & 3))
+    return fail(FAT5_EINVAL, "%s: cache_batch_idx / cache_row_batch misaligned", what);
+  if (p->cache_B < 0) return fail(FAT5_EINVAL, "%s: cache_B %d", what, p->cache_B);
+  const bool own_rows = !(p->cache_batch_idx || p->cache_row_batch) || (p->cache_row_batch && p->k_new);
+  if (own_rows && p->cache_B != 0 && p->cache_B < p->B)
+    return fail(FAT5_EINVAL, "%s: cache_B %d < B %d (rows read or written at their own batch element)", what, p->cache_B, p->B);
   const size_t need = fat5_attn_decode_workspace_bytes(p);
   if (need && (!p->workspace || !aligned16(p->workspace) || p->workspace_bytes < need))
     return fail(FAT5_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", what, need, p->workspace_bytes);
   return FAT5_OK;
 }
 
-extern "C++" template <int DT, int D, bool APPEND, bool BIAS>
-static void decode_launch(const DecodeArgs& a, hipStream_t stream) {
+extern "C++" template <int DT, int D, bool APPEND, bool BIAS, bool ROWMAP>
+static void decode_launch_map(const DecodeArgs& a, hipStream_t stream) {
   const dim3 grid(a.splits, a.H, a.B);
   if (a.splits == 1) {
-    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, true>), grid, dim3(DEC_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, true, ROWMAP>), grid, dim3(DEC_THREADS), 0, stream, a);
   } else {
-    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, false>), grid, dim3(DEC_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, false, ROWMAP>), grid, dim3(DEC_THREADS), 0, stream, a);
     hipLaunchKernelGGL((decode_combine_kernel<DT, D>), dim3(a.H, a.B), dim3(D), 0, stream, a);
   }
+}
+
+extern "C++" template <int DT, int D, bool APPEND, bool BIAS>
+static void decode_launch(const DecodeArgs& a, hipStream_t stream) {
+  if (a.rowmap) decode_launch_map<DT, D, APPEND, BIAS, true>(a, stream);
+  else decode_launch_map<DT, D, APPEND, BIAS, false>(a, stream);
 }
 
 int fat5_attn_decode(const fat5_decode_params* p, void* stream_) {
@@ -1562,6 +1578,9 @@ int fat5_attn_decode(const fat5_decode_params* p, void* stream_) {
   a.lse = p->lse;
   a.seqlens = p->cache_seqlens;
   a.rpe1d = p->bias_mode == FAT5_BIAS_RPE1D ? p->rpe1d : nullptr;
+  a.bidx = p->cache_batch_idx;
+  a.rowmap = p->cache_row_batch;
+  a.cacheB = p->cache_B ? p->cache_B : p->B;
   a.ws = static_cast<float*>(p->workspace);
   a.q_sb = p->q_stride[0], a.q_sh = p->q_stride[1];
   a.o_sb = p->o_stride[0], a.o_sh = p->o_stride[1];
@@ -1642,6 +1661,77 @@ int fat5_sample_logits(const fat5_sample_params* p, void* stream_) {
   else go(IC<FAT5_BF16>{});
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "sample_logits launch");
+  return FAT5_OK;
+}
+
+// ---- one beam-search step (beam_kernels.h) ----
+size_t fat5_sizeof_beam_params(void) { return sizeof(fat5_beam_params); }
+
+static bool beam_shape_ok(const fat5_beam_params* p) {
+  return p->B >= 1 && p->B <= 65535 && p->k >= 2 && p->k <= BEAM_MAX_K && p->V >= 2 && p->V <= SAMPLE_MAX_V;
+}
+
+size_t fat5_beam_step_workspace_bytes(const fat5_beam_params* p) {
+  if (!p || !beam_shape_ok(p)) return 0;
+  return align_up((size_t)p->B * p->k * (2 * p->k) * (sizeof(float) + sizeof(int32_t)), 16);
+}
+
+int fat5_beam_step(const fat5_beam_params* p, void* stream_) {
+  const char* what = "beam_step";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (p->k < 2 || p->k > BEAM_MAX_K) return fail(FAT5_EINVAL, "%s: num_beams %d outside [2, %d]", what, p->k, BEAM_MAX_K);
+  if (p->V < 2 || p->V > SAMPLE_MAX_V) return fail(FAT5_EINVAL, "%s: V %d outside [2, %d]", what, p->V, SAMPLE_MAX_V);
+  if (p->B < 1 || p->B > 65535) return fail(FAT5_EINVAL, "%s: B %d outside [1, 65535]", what, p->B);
+  if (p->dtype != FAT5_F32 && p->dtype != FAT5_F16 && p->dtype != FAT5_BF16) return fail(FAT5_EINVAL, "%s: dtype %d", what, p->dtype);
+  if (p->row_stride < p->V) return fail(FAT5_EINVAL, "%s: row_stride %lld < V %d", what, (long long)p->row_stride, p->V);
+  if (p->seq_len < 2 || p->capacity < 1 || (int64_t)p->B * p->k * p->capacity > INT32_MAX ||
+      (int64_t)p->B * p->k * p->seq_len > INT32_MAX)
+    return fail(FAT5_EINVAL, "%s: seq_len %d (>= 2) / capacity %d (>= 1) outside the int32 tables", what, p->seq_len, p->capacity);
+  if (p->max_length < 1) return fail(FAT5_EINVAL, "%s: max_length %d (>= 1)", what, p->max_length);
+  if (!std::isfinite(p->length_penalty)) return fail(FAT5_EINVAL, "%s: length_penalty must be finite", what);
+  if (p->early_stopping < 0 || p->early_stopping > 2)
+    return fail(FAT5_EINVAL, "%s: early_stopping %d (0 False, 1 True, 2 never)", what, p->early_stopping);
+  const size_t es = p->dtype == FAT5_F32 ? 4 : 2;
+  struct { const void* ptr; size_t al; const char* name; } t[] = {
+      {p->logits, es, "logits"}, {p->running_scores, 4, "running_scores"}, {p->running_seqs, 8, "running_seqs"},
+      {p->cache_row_batch, 4, "cache_row_batch"}, {p->finished_seqs, 8, "finished_seqs"}, {p->finished_scores, 4, "finished_scores"},
+      {p->finished_flags, 1, "finished_flags"}, {p->finished_lens, 4, "finished_lens"}, {p->heuristic, 1, "heuristic"},
+      {p->status, 4, "status"}, {p->tokens, 8, "tokens"}, {p->step, 4, "step"}};
+  for (const auto& e : t)
+    if (!e.ptr || (reinterpret_cast<uintptr_t>(e.ptr) % e.al)) return fail(FAT5_EINVAL, "%s: %s: null or misaligned pointer", what, e.name);
+  const size_t need = fat5_beam_step_workspace_bytes(p);
+  if (!p->workspace || !aligned16(p->workspace) || p->workspace_bytes < need)
+    return fail(FAT5_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", what, need, p->workspace_bytes);
+  BeamArgs a = {};
+  a.logits = p->logits;
+  a.stride = p->row_stride;
+  a.rs = p->running_scores;
+  a.run_seq = p->running_seqs;
+  a.table = p->cache_row_batch;
+  a.fin_seq = p->finished_seqs;
+  a.fin_score = p->finished_scores;
+  a.fin_flag = p->finished_flags;
+  a.fin_len = p->finished_lens;
+  a.unsat = p->heuristic;
+  a.status = p->status;
+  a.tokens = p->tokens;
+  a.step = p->step;
+  a.B = p->B, a.k = p->k, a.V = p->V, a.K = 2 * p->k, a.Kr = std::min(2 * p->k, p->V);
+  a.ws_score = static_cast<float*>(p->workspace);
+  a.ws_tok = reinterpret_cast<int32_t*>(a.ws_score + (size_t)p->B * p->k * a.K);
+  a.Lseq = p->seq_len, a.cap = p->capacity, a.max_length = p->max_length, a.early = p->early_stopping;
+  a.lp = p->length_penalty;
+  a.vec = aligned16(p->logits) && p->row_stride % 8 == 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 rows(p->B * p->k);
+  if (p->dtype == FAT5_F32) hipLaunchKernelGGL((beam_topk_kernel<FAT5_F32>), rows, dim3(BEAM_TOPK_THREADS), 0, stream, a);
+  else if (p->dtype == FAT5_F16) hipLaunchKernelGGL((beam_topk_kernel<FAT5_F16>), rows, dim3(BEAM_TOPK_THREADS), 0, stream, a);
+  else hipLaunchKernelGGL((beam_topk_kernel<FAT5_BF16>), rows, dim3(BEAM_TOPK_THREADS), 0, stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "beam_step top-k launch");
+  hipLaunchKernelGGL(beam_update_kernel, dim3(p->B), dim3(BEAM_THREADS), 0, stream, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "beam_step update launch");
   return FAT5_OK;
 }
 

@@ -22,7 +22,8 @@ def _dec_view(t):
     return (t.stride(0), t.stride(2))
 
 
-def _params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse, sm_scale, rpe1d, radius, num_splits):
+def _params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse, sm_scale, rpe1d, radius, num_splits, cache_batch_idx=None,
+            cache_row_batch=None):
     B, _, H, D = q.shape
     p = _lib.DecodeParams()
     p.B, p.H, p.D = B, H, D
@@ -44,19 +45,38 @@ def _params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse, sm_scale, rpe1d, r
         p.v_new_stride[:] = _dec_view(v)
     p.lse = lse.data_ptr() if lse is not None else None
     p.num_splits = int(num_splits)
+    if cache_batch_idx is not None or cache_row_batch is not None:
+        p.cache_B = k_cache.shape[0]
+        p.cache_batch_idx = cache_batch_idx.data_ptr() if cache_batch_idx is not None else None
+        p.cache_row_batch = cache_row_batch.data_ptr() if cache_row_batch is not None else None
     return p
 
 
-def _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius):
+def _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius, cache_batch_idx=None, cache_row_batch=None):
     """everything the host can check without touching a device: shapes, dtypes, strides, the bias generator against its radius"""
     if q.dim() != 4 or q.shape[1] != 1:
         raise ValueError(f"flash_attn_with_kvcache: q must be (B, 1, H, D) (one query row per step), got {tuple(q.shape)}")
     B, _, H, D = q.shape
+    mapped = cache_batch_idx is not None or cache_row_batch is not None
+    CB = k_cache.shape[0] if (mapped and k_cache.dim() == 4) else B  # (a map reads the caches' own batch count)
     for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.dim() != 4 or t.shape[0] != B or t.shape[2] != H or t.shape[3] != D:
-            raise ValueError(f"flash_attn_with_kvcache: {name} must be (B, L_cap, H, D) = ({B}, L_cap, {H}, {D}), got {tuple(t.shape)}")
+        if t.dim() != 4 or t.shape[0] != CB or t.shape[2] != H or t.shape[3] != D:
+            raise ValueError(f"flash_attn_with_kvcache: {name} must be (B, L_cap, H, D) = ({CB}, L_cap, {H}, {D}), got {tuple(t.shape)}")
     if k_cache.shape[1] != v_cache.shape[1]:
         raise ValueError("flash_attn_with_kvcache: k_cache and v_cache have different capacities")
+    if cache_batch_idx is not None and cache_row_batch is not None:
+        raise ValueError("flash_attn_with_kvcache: cache_batch_idx and cache_row_batch cannot be combined")
+    if cache_batch_idx is not None:
+        if k is not None:
+            raise ValueError("flash_attn_with_kvcache: cache_batch_idx cannot be combined with an append (k / v)")
+        if cache_batch_idx.dim() != 1 or cache_batch_idx.numel() != B:
+            raise ValueError(f"flash_attn_with_kvcache: cache_batch_idx must hold {B} entries, got {tuple(cache_batch_idx.shape)}")
+    if cache_row_batch is not None:
+        if tuple(cache_row_batch.shape) != (B, k_cache.shape[1]):
+            raise ValueError(f"flash_attn_with_kvcache: cache_row_batch must be (B, L_cap) = ({B}, {k_cache.shape[1]}), got "
+                             f"{tuple(cache_row_batch.shape)}")
+        if k is not None and CB < B:
+            raise ValueError(f"flash_attn_with_kvcache: an append with cache_row_batch writes row b of the caches: they hold {CB} < {B}")
     if (k is None) != (v is None):
         raise ValueError("flash_attn_with_kvcache: pass both k and v, or neither")
     if k is not None:
@@ -97,12 +117,12 @@ def _check_devices(q, k_cache, v_cache, k, v, rpe1d):
             raise ValueError("flash_attn_with_kvcache: tensors on different devices")
 
 
-def _check(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius):
-    _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius)
+def _check(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius, cache_batch_idx=None, cache_row_batch=None):
+    _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius, cache_batch_idx, cache_row_batch)
     _check_devices(q, k_cache, v_cache, k, v, rpe1d)
-    if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or cache_seqlens.device != q.device or
-                                      not cache_seqlens.is_contiguous()):
-        raise ValueError(f"fat5::attn_decode: cache_seqlens must be a contiguous int32 tensor on {q.device}")
+    for name, t in (("cache_seqlens", cache_seqlens), ("cache_batch_idx", cache_batch_idx), ("cache_row_batch", cache_row_batch)):
+        if t is not None and (t.dtype != torch.int32 or t.device != q.device or not t.is_contiguous()):
+            raise ValueError(f"fat5::attn_decode: {name} must be a contiguous int32 tensor on {q.device}")
 
 
 def _ready(t):
@@ -112,14 +132,16 @@ def _ready(t):
 @torch.library.custom_op("fat5::attn_decode", mutates_args=("k_cache", "v_cache"), device_types="cuda")
 def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor], v: Optional[torch.Tensor],
                 cache_seqlens: Optional[torch.Tensor], sm_scale: float, rpe1d: Optional[torch.Tensor], rpe_radius: int,
-                return_lse: bool, num_splits: int) -> List[torch.Tensor]:
+                return_lse: bool, num_splits: int, cache_batch_idx: Optional[torch.Tensor] = None,
+                cache_row_batch: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
     """[o (B, 1, H, D) contiguous, lse (B, H, 1) fp32 (empty (0,) when return_lse is False)]; appends k / v to the caches"""
-    _check(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius)
+    _check(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius, cache_batch_idx, cache_row_batch)
     q, k, v = _ready(q), _ready(k), _ready(v)
     B, _, H, D = q.shape
     o = torch.empty((B, 1, H, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, 1), dtype=torch.float32, device=q.device) if return_lse else q.new_empty((0,), dtype=torch.float32)
-    p = _params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse if return_lse else None, sm_scale, rpe1d, rpe_radius, num_splits)
+    p = _params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse if return_lse else None, sm_scale, rpe1d, rpe_radius, num_splits,
+                cache_batch_idx, cache_row_batch)
     lib = _lib.load()
     ws = None
     need = lib.fat5_attn_decode_workspace_bytes(p)
@@ -132,7 +154,8 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k
 
 
 @attn_decode.register_fake
-def _attn_decode_fake(q, k_cache, v_cache, k, v, cache_seqlens, sm_scale, rpe1d, rpe_radius, return_lse, num_splits):
+def _attn_decode_fake(q, k_cache, v_cache, k, v, cache_seqlens, sm_scale, rpe1d, rpe_radius, return_lse, num_splits, cache_batch_idx=None,
+                      cache_row_batch=None):
     B, _, H, D = q.shape
     o = q.new_empty((B, 1, H, D))
     lse = q.new_empty((B, H, 1), dtype=torch.float32) if return_lse else q.new_empty((0,), dtype=torch.float32)
@@ -154,17 +177,27 @@ def _as_seqlens(cache_seqlens, device):
 
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, softmax_scale=None, rpe1d=None, rpe_radius=0,
-                            return_lse=False, num_splits=0):
+                            return_lse=False, num_splits=0, cache_batch_idx=None, cache_row_batch=None):
     """flash_attn's `flash_attn_with_kvcache` for one query row: returns o (B, 1, H, D), or (o, lse (B, H, 1) fp32) with
     return_lse.  An int cache_seqlens broadcasts over the batch.  num_splits 0 lets the library pick the key-range split from
-    B, H and the cache capacity (never from the lengths: a captured graph stays valid while they grow)."""
+    B, H and the cache capacity (never from the lengths: a captured graph stays valid while they grow).
+
+    Indexed reads (beam search): `cache_batch_idx` (B,) int32 -- query row b reads batch element cache_batch_idx[b] of the caches
+    (flash_attn's meaning; the caches may then hold another batch count); `cache_row_batch` (B, L_cap) int32 -- key row j of row
+    b is read from batch element cache_row_batch[b, j] at row j, while an appended row still goes to element b.  Entries are
+    clamped on the device to the caches' batch range.  Both must already be contiguous int32 tensors on the device."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v, rpe1d)):
         raise RuntimeError("flash_attn_with_kvcache is forward only: call it under torch.no_grad() / inference_mode(), or detach")
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32)
-    _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius)  # (before the device checks: every shape error is
-    _check_devices(q, k_cache, v_cache, k, v, rpe1d)                           #  reported as such, on any host)
+    _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius, cache_batch_idx,  # (before the device checks: every
+                  cache_row_batch)                                                           #  shape error is reported as such)
+    _check_devices(q, k_cache, v_cache, k, v, rpe1d)
     lens = _as_seqlens(cache_seqlens, q.device)
     scale = 1.0 / math.sqrt(q.shape[-1]) if softmax_scale is None else float(softmax_scale)
-    o, lse = attn_decode(q, k_cache, v_cache, k, v, lens, scale, rpe1d, int(rpe_radius), bool(return_lse), int(num_splits))
+    if cache_batch_idx is None and cache_row_batch is None:
+        o, lse = attn_decode(q, k_cache, v_cache, k, v, lens, scale, rpe1d, int(rpe_radius), bool(return_lse), int(num_splits))
+    else:
+        o, lse = attn_decode(q, k_cache, v_cache, k, v, lens, scale, rpe1d, int(rpe_radius), bool(return_lse), int(num_splits),
+                             cache_batch_idx, cache_row_batch)
     return (o, lse) if return_lse else o

@@ -11,10 +11,10 @@ A minimal encoder-decoder with the reference's structure (src/model/modeling_fla
   * loss           -> `FlashT5CrossEntropyLoss` (cross_entropy_loss with z-loss and label smoothing, HIP)
   * everything else is plain torch-ROCm: `nn.Linear` (hipBLASLt), `nn.Embedding`, tanh-GELU gating, residual adds.
 
-Generation: `generate` (greedy -- the reference's algorithm and return value -- or sampled) and `decode_step` run one new token per step through
+Generation: `generate` (greedy -- the reference's algorithm and return value --, sampled, or beam search) and `decode_step` run one new token per step through
 the decoder against per-layer KV caches (flasht5_amd/generation.py, the split-KV decode kernel), optionally replayed from a HIP graph.
 
-This is the step DRIVER of the hot path, not a model zoo: no beam search, heads, dropout (0 in every reference config),
+This is the step DRIVER of the hot path, not a model zoo: no heads, dropout (0 in every reference config),
 HF plumbing or checkpoint conversion.  Data parallelism = one process per GPU; `allreduce_gradients` is the step's one
 exchange (RCCL over xGMI): a single flat fp32 all-reduce that carries the two `(32, H)` relative-position tables first.
 """
@@ -309,12 +309,14 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         return decode_step(self, state, token_ids)
 
     def generate(self, input_ids, attention_mask=None, max_length=32, graph=False, *, do_sample=False, temperature=1.0, top_k=50,
-                 top_p=1.0, seed=None):
+                 top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
+                 return_scores=False):
         """greedy (or, with do_sample=True, temperature / top-k / top-p sampled) decoding with a KV cache; returns what the
-        reference's generate returns (generation.generate)"""
+        reference's generate returns; num_beams > 1: HF's beam search (generation.generate)"""
         from .generation import generate
         return generate(self, input_ids, attention_mask, max_length, graph, do_sample=do_sample, temperature=temperature,
-                        top_k=top_k, top_p=top_p, seed=seed)
+                        top_k=top_k, top_p=top_p, seed=seed, num_beams=num_beams, num_return_sequences=num_return_sequences,
+                        length_penalty=length_penalty, early_stopping=early_stopping, return_scores=return_scores)
 
 
 def allreduce_gradients(model: nn.Module, group=None, average=True):

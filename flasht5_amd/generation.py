@@ -16,6 +16,11 @@ every self-attention cache and incremented on the device at the end of each step
 
 Sampling (`do_sample=True`) replaces the argmax by `sample_logits` (one HIP launch: temperature, top-k, top-p and a Philox draw
 keyed by the call's seed with the token's position, cache_seqlens, as the counter), so it is captured and replayed the same way.
+
+Beam search (`num_beams=k > 1`) runs the encoder and the cross K / V projections once on B rows, shared by the
+B * k beam rows through the decode kernel's `cache_batch_idx`; the self-attention caches hold B * k rows and are never copied
+or reordered: each beam reads its history through the `cache_row_batch` table of parents, which the beam-step kernel
+(flasht5_amd/beam.py) reorders in place with the running and finished sequences.  Decode step plus beam step is one graph.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -36,6 +41,8 @@ class DecodeState:
     position_bias: Optional[Tuple[torch.Tensor, int]]  # the decoder's (rpe1d, R) (T5), or None (RoPE)
     capacity: int
     steps: int = 0                      # decode_step calls so far (host-side: decode_step refuses to run past the capacity)
+    cross_batch_idx: Optional[torch.Tensor] = None  # beam search: (B * k,) int32, beam row -> encoder row (b // k)
+    row_batch: Optional[torch.Tensor] = None        # beam search: (B * k, capacity) int32 history table (cache_row_batch)
 
     @property
     def position(self):
@@ -58,9 +65,11 @@ def _check_supported(model):
 
 
 @torch.no_grad()
-def init_decode_state(model, input_ids, max_length, attention_mask=None):
+def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1):
     """Run the encoder, project every decoder layer's cross-attention K / V once and allocate self-attention caches of capacity
-    `max_length + 1`.  `attention_mask` is accepted and not applied, as the reference does with use_masking=False."""
+    `max_length + 1`.  `attention_mask` is accepted and not applied, as the reference does with use_masking=False.
+    num_beams > 1: the encoder and the cross K / V stay at B rows; the self-attention caches, the lengths and the history table
+    get B * num_beams rows (row b * k + j: beam j of input b)."""
     _check_supported(model)
     first = model.decoder.block[0].self_attention_layer.self_attention
     cap = int(max_length) + 1
@@ -70,6 +79,7 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None):
                          f"{first.pe_encoding.max_sequence_length} rows (max_sequence_length); use max_length <= "
                          f"{first.pe_encoding.max_sequence_length - 1}")
     B = input_ids.shape[0]
+    Bk = B * int(num_beams)
     enc = model.encoder(input_ids)
     dev = enc.device
     # (the projections' dtype: autocast's when it is on, the weights' otherwise -- the dtype of k and v in the training forward)
@@ -77,15 +87,19 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None):
     H, D = first.n_heads, first.key_value_proj_dim
     self_k, self_v, cross_k, cross_v = [], [], [], []
     for blk in model.decoder.block:
-        self_k.append(torch.zeros((B, cap, H, D), dtype=dtype, device=dev))
-        self_v.append(torch.zeros((B, cap, H, D), dtype=dtype, device=dev))
+        self_k.append(torch.zeros((Bk, cap, H, D), dtype=dtype, device=dev))
+        self_v.append(torch.zeros((Bk, cap, H, D), dtype=dtype, device=dev))
         k, v = blk.cross_attention_layer.cross_attention.project_kv(enc)
         cross_k.append(k)
         cross_v.append(v)
     pb = None
     if not first.rotary:
         pb = first.pe_encoding.forward_1d()  # (the (H, 2R+1) generator, built once per generate as the training path builds it per step)
-    return DecodeState(enc, self_k, self_v, cross_k, cross_v, torch.zeros((B,), dtype=torch.int32, device=dev), pb, cap)
+    state = DecodeState(enc, self_k, self_v, cross_k, cross_v, torch.zeros((Bk,), dtype=torch.int32, device=dev), pb, cap)
+    if num_beams > 1:
+        state.cross_batch_idx = torch.arange(Bk, dtype=torch.int32, device=dev) // int(num_beams)
+        state.row_batch = torch.zeros((Bk, cap), dtype=torch.int32, device=dev)
+    return state
 
 
 @torch.no_grad()
@@ -102,9 +116,10 @@ def decode_step(model, state, token_ids):
     for i, blk in enumerate(model.decoder.block):
         sa = blk.self_attention_layer
         h = h + sa.self_attention.forward_decode(sa.layer_norm(h), state.self_k[i], state.self_v[i], state.cache_seqlens,
-                                                 position_bias=state.position_bias, position=pos)
+                                                 position_bias=state.position_bias, position=pos, cache_row_batch=state.row_batch)
         ca = blk.cross_attention_layer
-        h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos)
+        h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos,
+                                                  cache_batch_idx=state.cross_batch_idx)
         h = blk.ff_layer(h)
     h = model.decoder.final_layer_norm(h)
     state.cache_seqlens.add_(1)
@@ -145,9 +160,52 @@ def finish_labels(labels):
     return labels.masked_fill(~keep, 0)
 
 
+def _beam_step(model, state, tok, bs, opts):
+    """decode_step + the beam-step kernel: the next tokens go straight into `tok`; the step count is cache_seqlens after the
+    increment, read on the device -- nothing here reads the host, so the same code is captured as it is"""
+    from .beam import beam_step
+    max_length, length_penalty, early_stopping = opts
+    logits = decode_step(model, state, tok)
+    bs.tokens = tok
+    beam_step(logits, bs, state.cache_seqlens, max_length, length_penalty, early_stopping)
+
+
+def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, length_penalty, early_stopping, return_scores):
+    from .beam import new_state, keep_going
+    B = input_ids.shape[0]
+    dev = input_ids.device
+    state = init_decode_state(model, input_ids, max_length, attention_mask, num_beams=k)
+    bs = new_state(B, k, int(max_length) + 1, state.capacity, dev)
+    bs.cache_row_batch = state.row_batch  # (one table: the decode kernel reads it, the beam step reorders it)
+    tok = torch.zeros((B * k,), dtype=torch.long, device=dev)
+    opts = (int(max_length), float(length_penalty), early_stopping)
+    g = None
+    steps = 0
+    try:
+        for _ in range(int(max_length)):
+            if g is not None:
+                g.replay()
+            else:
+                _beam_step(model, state, tok, bs, opts)
+            steps += 1
+            if not bool(keep_going(bs.status, early_stopping)):
+                break
+            if graph and g is None and steps < max_length:
+                g = _capture_call(lambda: _beam_step(model, state, tok, bs, opts))
+    finally:
+        del g
+    seqs = bs.finished_seqs[:, :R].reshape(B * R, -1)
+    T = int(bs.finished_lens[:, :R].max())
+    out = seqs[:, :T + 1].clone()
+    if return_scores:
+        return out, bs.finished_scores[:, :R].reshape(B * R).clone()
+    return out
+
+
 @torch.no_grad()
 def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, *, do_sample=False, temperature=1.0, top_k=50,
-             top_p=1.0, seed=None):
+             top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
+             return_scores=False):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -159,7 +217,19 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
 
     graph=True captures one decoding step (for this batch and capacity) once in a HIP graph on one stream and replays it per
     token; the first step runs eagerly (it also builds what the step allocates lazily), so both modes run the same kernels with the
-    same arguments and give the same tokens."""
+    same arguments and give the same tokens.
+
+    num_beams=k in [2, 16]: HF's beam search (transformers 5.x `_beam_search`, one EOS id 1, max_new_tokens = max_length, no logits
+    processors) with `num_return_sequences`, `length_penalty` and `early_stopping` (False, True or "never") as HF means them.
+    Returns (B * num_return_sequences, 1 + T) int64: column 0 is the start token 0, then each hypothesis's tokens including its
+    EOS, 0 past its end; T is the longest returned hypothesis.  return_scores=True adds HF's `sequences_scores`
+    (B * num_return_sequences,) fp32.  The beam arguments are checked on the host before the encoder runs; do_sample=True with
+    beams is rejected.  num_beams=1 is the greedy / sampled path above, unchanged."""
+    from .beam import check_args as check_beam_args
+    check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample)
+    if num_beams > 1:
+        return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
+                              early_stopping, return_scores)
     step = _greedy_step
     if do_sample:
         from .sampling import check_args
@@ -196,13 +266,18 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
 
 def _capture(model, state, tok, labels, seen_eos, step=_greedy_step):
     """one decoding step (greedy by default) captured in a HIP graph (nothing runs during the capture: the state is unchanged)"""
+    return _capture_call(lambda: step(model, state, tok, labels, seen_eos))
+
+
+def _capture_call(fn):
+    """fn() captured in a HIP graph"""
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     ac = torch.is_autocast_enabled()
     with torch.cuda.graph(g):  # (torch's capture stream: one stream, no parallel branches)
         if ac:  # (autocast's weight-cast cache must not hand tensors from outside the capture to it)
             with torch.autocast("cuda", dtype=torch.get_autocast_dtype("cuda"), cache_enabled=False):
-                step(model, state, tok, labels, seen_eos)
+                fn()
         else:
-            step(model, state, tok, labels, seen_eos)
+            fn()
     return g

@@ -359,10 +359,21 @@ int fat5_fire_bwd(const fat5_fire_params* p, void* workspace, size_t workspace_b
  * the lengths grow; results are bitwise identical run to run.  Element strides, 64-bit offsets, innermost stride 1; every base
  * 16-byte aligned and every stride a multiple of 8 elements.  q / k_new / v_new / o are (B, H, D) views with strides [b, h]; the
  * caches are (B, capacity, H, D) views with strides [b, l, h] (so (B, L, H, D) and (B, H, L, D) storage both work).
+ * Indexed reads (beam search): the caches hold cache_B batch elements (0 means B).
+ *   - cache_batch_idx (B,): query row b reads batch element cache_batch_idx[b] of the caches (flash_attn's meaning: the B * k beam
+ *     rows attend to the B encoder caches without copies).  Not with an append, not with cache_row_batch.
+ *   - cache_row_batch (B, capacity) contiguous: key row j < L_b of row b is read from batch element cache_row_batch[b * capacity + j]
+ *     at row j (the beam history as a table of parents, instead of a reordered cache).  The appended row is still read from
+ *     k_new / v_new and written to batch element b, at row len_b.
+ *   Every map entry is clamped on the device to [0, cache_B), as the lengths are, so no entry becomes an out-of-bounds access.
+ *   Without a map, or with cache_row_batch and an append, cache_B must be 0 or >= B.  With an append, an entry that sends row
+ *   b' != e to element e's row len_e reads the row e writes in the same launch: its value is then either one (beam search never
+ *   does this: every row shares one length and reads only rows below it).
  * Rejected with FAT5_EINVAL before anything is launched: D outside {64, 128}, dtype outside {FAT5_F16, FAT5_BF16}, B / H / capacity
  * out of range, N outside [0, capacity], num_splits outside [0, 128], a radius outside 1..2048 or a NULL rpe1d with RPE1D,
- * exactly one of k_new / v_new, an append without cache_seqlens, NULL / misaligned pointers or strides; FAT5_EWORKSPACE when the
- * workspace is missing, misaligned or smaller than fat5_attn_decode_workspace_bytes().
+ * exactly one of k_new / v_new, an append without cache_seqlens, NULL / misaligned pointers or strides, cache_B < 0 or one
+ * smaller than B where the rule above needs B, cache_batch_idx together with cache_row_batch or with an append, a misaligned
+ * map; FAT5_EWORKSPACE when the workspace is missing, misaligned or smaller than fat5_attn_decode_workspace_bytes().
  */
 typedef struct fat5_decode_params {
   int32_t B, H, D;            /* D in {64, 128} */
@@ -385,6 +396,10 @@ typedef struct fat5_decode_params {
   int32_t num_splits;         /* key-range splits per (b, h), 1..128; 0 = the library's choice from B, H, capacity */
   void* workspace;            /* fat5_attn_decode_workspace_bytes(); 16-byte aligned; may be NULL when that is 0 */
   size_t workspace_bytes;
+  /* indexed cache reads (beam search); all zero: the plain kernel, same grid, split and bits */
+  const int32_t* cache_batch_idx; /* (B,) int32 device array, or NULL: query row b reads cache batch element cache_batch_idx[b] */
+  const int32_t* cache_row_batch; /* (B, capacity) int32 device array, or NULL: key row j of row b from element [b][j], at row j */
+  int32_t cache_B;            /* batch elements of the caches; 0 = B */
 } fat5_decode_params;
 /* sizeof(fat5_decode_params) as compiled into the library (bindings check their mirror against it). */
 size_t fat5_sizeof_decode_params(void);
@@ -430,6 +445,65 @@ typedef struct fat5_sample_params {
 /* sizeof(fat5_sample_params) as compiled into the library (bindings check their mirror against it). */
 size_t fat5_sizeof_sample_params(void);
 int fat5_sample_logits(const fat5_sample_params* p, void* hip_stream);
+
+/*
+ * One beam-search step for B batch items of k beams (beam_kernels.h).  HF's vectorized `_beam_search` (transformers
+ * 5.x: _get_top_k_continuations, _get_running_beams_for_next_iteration, _update_finished_beams, _check_early_stop_heuristic) with
+ * one EOS id (1), K = 2k kept candidates and the start token as the decoder prompt.  Every state array lives on the device and is
+ * updated in place, so a captured step reads nothing from the host.  With s = clamp(step[b * k], 1, min(seq_len - 1, capacity))
+ * (the tokens fed so far: cache_seqlens after the increment) and t = s - 1 (the cache position this step's decode wrote):
+ *   - Scores.  Candidate (beam i, token x) of batch item b scores running_scores[b, i] + (x_f - lse_i), in fp32 from the fp32
+ *     value of the logit, lse_i = max + log(sum exp(x - max)) of row b * k + i.
+ *   - Top K.  The K best candidates by score; on an equal score the lower flat index i * V + token wins.
+ *   - Stopping.  A candidate hits the stopping criterion when its token is 1 (EOS) or when s >= max_length (it is the
+ *     max_length-th generated token): HF with max_new_tokens = max_length.
+ *   - Running beams.  v = score + (hit ? -1e9 : 0); the first k candidates by (v descending, candidate rank ascending);
+ *     running_scores = v.  tokens[b * k + j] = running beam j's token.
+ *   - Finished merge.  A candidate's finished score is score / s ** length_penalty (the power in double, the division in fp32),
+ *     then + -1e9 when every finished flag is set and early_stopping is True, + -1e9 when the heuristic flag is clear, + -1e9
+ *     unless the candidate hit and ranks below k -- HF's additions, in HF's order.  The k old entries followed by the K candidates
+ *     (HF's cat order) are ranked by (score descending, entry ascending) and the first k kept: finished_scores, finished_flags (an
+ *     old entry's flag, or hit && rank < k), finished_lens (an old entry's length, or s).
+ *   - Heuristic.  best = running_scores[b, 0] / n ** length_penalty with n = max_length when early_stopping is "never" and
+ *     length_penalty > 0, else s; heuristic[b] &= any_j(best > (finished_flags[b, j] ? min_j finished_scores[b, j] : -1e9)).
+ *   - status[b] = bit 0: heuristic[b]; bit 1: every finished flag set; bit 2: every one of the K candidates hit.  The host ends
+ *     the loop as HF does: unless any(bit 0) && !(all(bit 1) && early_stopping is True) && !all(bit 2).
+ *   - History tables, reordered in place.  Running row j takes its parent p_j's row, columns [0, s); its token goes into column
+ *     s.  A finished row takes an old finished row or a candidate's (parent row and token).  cache_row_batch row b * k + j takes
+ *     row b * k + p_j, columns [0, t), and cache_row_batch[b * k + j][t] = b * k + p_j.  Columns past s (t) are not touched.
+ * Tie order is fixed, so every output is bitwise reproducible and independent of the workgroups' timing.  Initial state (HF's):
+ * running_scores [0, -1e9, ...], finished_scores -1e9, flags 0, heuristic 1, sequences and tables 0 (column 0: the start token).
+ * Rejected with FAT5_EINVAL before anything is launched: k outside [2, 16], V outside [2, 2^20] (V = 1 leaves fewer than K
+ * candidates), B outside [1, 65535], dtype outside {FAT5_F32, FAT5_F16, FAT5_BF16}, row_stride < V, seq_len < 2, capacity < 1,
+ * tables past 2^31 entries, max_length < 1, a non-finite length_penalty, early_stopping outside {0, 1, 2}, NULL or misaligned
+ * pointers; FAT5_EWORKSPACE when the workspace is missing, misaligned or smaller than fat5_beam_step_workspace_bytes().
+ */
+typedef struct fat5_beam_params {
+  int32_t B, k, V;            /* batch items, beams (2..16), vocabulary (2..2^20) */
+  int32_t dtype;              /* logits: FAT5_F32 | FAT5_F16 | FAT5_BF16 */
+  const void* logits;         /* (B * k, V), row stride row_stride elements */
+  int64_t row_stride;
+  float* running_scores;      /* (B, k) fp32, in / out */
+  int64_t* running_seqs;      /* (B, k, seq_len) int64, in / out */
+  int32_t* cache_row_batch;   /* (B * k, capacity) int32, in / out (fat5_decode_params.cache_row_batch) */
+  int64_t* finished_seqs;     /* (B, k, seq_len) int64, in / out */
+  float* finished_scores;     /* (B, k) fp32, in / out */
+  uint8_t* finished_flags;    /* (B, k), in / out */
+  int32_t* finished_lens;     /* (B, k) generated tokens of each finished entry, in / out */
+  uint8_t* heuristic;         /* (B,) early-stop heuristic "improvement still possible", in / out */
+  int32_t* status;            /* (B,) out */
+  int64_t* tokens;            /* (B * k,) next decoder tokens, out */
+  const int32_t* step;        /* device int32, read at [b * k] */
+  int32_t seq_len, capacity;  /* sequence columns (max_length + 1), cache positions */
+  int32_t max_length;         /* new tokens at most */
+  int32_t early_stopping;     /* 0 False, 1 True, 2 "never" */
+  float length_penalty;
+  void* workspace;            /* fat5_beam_step_workspace_bytes(); 16-byte aligned */
+  size_t workspace_bytes;
+} fat5_beam_params;
+size_t fat5_sizeof_beam_params(void);
+size_t fat5_beam_step_workspace_bytes(const fat5_beam_params* p);
+int fat5_beam_step(const fat5_beam_params* p, void* hip_stream);
 
 /*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
