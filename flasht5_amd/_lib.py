@@ -107,6 +107,18 @@ class BeamParams(ctypes.Structure):
         ("heuristic", ctypes.c_void_p), ("status", ctypes.c_void_p), ("tokens", ctypes.c_void_p), ("step", ctypes.c_void_p),
         ("seq_len", ctypes.c_int32), ("capacity", ctypes.c_int32), ("max_length", ctypes.c_int32), ("early_stopping", ctypes.c_int32),
         ("length_penalty", ctypes.c_float), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+        ("logits_normalized", ctypes.c_int32),
+    ]
+
+
+class LogitsParams(ctypes.Structure):
+    """Mirror of `fat5_logits_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("rows", ctypes.c_int32), ("V", ctypes.c_int32), ("dtype", ctypes.c_int32), ("log_softmax", ctypes.c_int32),
+        ("logits", ctypes.c_void_p), ("row_stride", ctypes.c_int64), ("out", ctypes.c_void_p), ("out_stride", ctypes.c_int64),
+        ("sequences", ctypes.c_void_p), ("seq_stride", ctypes.c_int64), ("lengths", ctypes.c_void_p), ("seq_len", ctypes.c_int32),
+        ("repetition_penalty", ctypes.c_float), ("no_repeat_ngram_size", ctypes.c_int32), ("min_length", ctypes.c_int32),
+        ("eos_token_id", ctypes.c_int32), ("n_suppress", ctypes.c_int32), ("suppress_tokens", ctypes.c_void_p),
     ]
 
 
@@ -121,6 +133,7 @@ EXPORTS = (
     "fat5_attn_decode", "fat5_attn_decode_workspace_bytes", "fat5_sizeof_decode_params",
     "fat5_sample_logits", "fat5_sizeof_sample_params",
     "fat5_beam_step", "fat5_beam_step_workspace_bytes", "fat5_sizeof_beam_params",
+    "fat5_process_logits", "fat5_sizeof_logits_params",
 )
 
 _lib = None
@@ -230,6 +243,12 @@ def load():
     if lib.fat5_sizeof_beam_params() != ctypes.sizeof(BeamParams):
         raise ImportError(f"fat5_beam_params layout mismatch: library {lib.fat5_sizeof_beam_params()} B, "
                           f"binding {ctypes.sizeof(BeamParams)} B")
+    lib.fat5_process_logits.restype = ctypes.c_int
+    lib.fat5_process_logits.argtypes = [ctypes.POINTER(LogitsParams), ctypes.c_void_p]
+    lib.fat5_sizeof_logits_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_logits_params() != ctypes.sizeof(LogitsParams):
+        raise ImportError(f"fat5_logits_params layout mismatch: library {lib.fat5_sizeof_logits_params()} B, "
+                          f"binding {ctypes.sizeof(LogitsParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

@@ -118,7 +118,7 @@ def _check(logits, running_scores, running_seqs, cache_row_batch, finished_seqs,
 def beam_step_op(logits: torch.Tensor, running_scores: torch.Tensor, running_seqs: torch.Tensor, cache_row_batch: torch.Tensor,
                  finished_seqs: torch.Tensor, finished_scores: torch.Tensor, finished_flags: torch.Tensor, finished_lens: torch.Tensor,
                  heuristic: torch.Tensor, status: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, num_beams: int,
-                 max_length: int, length_penalty: float, early_stopping: int) -> None:
+                 max_length: int, length_penalty: float, early_stopping: int, logits_normalized: bool = False) -> None:
     _check(logits, running_scores, running_seqs, cache_row_batch, finished_seqs, finished_scores, finished_flags, finished_lens,
            heuristic, status, tokens, step, num_beams)
     if logits.stride(-1) != 1:
@@ -134,6 +134,7 @@ def beam_step_op(logits: torch.Tensor, running_scores: torch.Tensor, running_seq
     p.heuristic, p.status, p.tokens, p.step = heuristic.data_ptr(), status.data_ptr(), tokens.data_ptr(), step.data_ptr()
     p.seq_len, p.capacity = running_seqs.shape[2], cache_row_batch.shape[1]
     p.max_length, p.early_stopping, p.length_penalty = int(max_length), int(early_stopping), float(length_penalty)
+    p.logits_normalized = int(bool(logits_normalized))
     lib = _lib.load()
     need = lib.fat5_beam_step_workspace_bytes(p)
     ws = torch.empty(need, dtype=torch.uint8, device=logits.device)
@@ -144,13 +145,16 @@ def beam_step_op(logits: torch.Tensor, running_scores: torch.Tensor, running_seq
 
 @beam_step_op.register_fake
 def _beam_step_fake(logits, running_scores, running_seqs, cache_row_batch, finished_seqs, finished_scores, finished_flags,
-                    finished_lens, heuristic, status, tokens, step, num_beams, max_length, length_penalty, early_stopping):
+                    finished_lens, heuristic, status, tokens, step, num_beams, max_length, length_penalty, early_stopping,
+                    logits_normalized=False):
     return None
 
 
-def beam_step(logits, st, step, max_length, length_penalty=1.0, early_stopping=False):
+def beam_step(logits, st, step, max_length, length_penalty=1.0, early_stopping=False, logits_normalized=False):
     """one beam-search step over logits (B * k, V) into the BeamState `st`; `step` is the device int32 count of tokens fed so far
-    (cache_seqlens after the decode step's increment), read at [b * k]"""
+    (cache_seqlens after the decode step's increment), read at [b * k].  logits_normalized=True: the rows are log-probabilities
+    already (`process_logits(..., log_softmax=True)`, bans included) and are scored as they are, without a renormalisation --
+    HF's order, processors on log_softmax(logits)"""
     k = st.running_scores.shape[1]
     if not math.isfinite(float(length_penalty)):
         raise ValueError(f"length_penalty must be finite, got {length_penalty}")
@@ -158,4 +162,4 @@ def beam_step(logits, st, step, max_length, length_penalty=1.0, early_stopping=F
         raise ValueError(f"max_length must be >= 1, got {max_length}")
     beam_step_op(logits, st.running_scores, st.running_seqs, st.cache_row_batch, st.finished_seqs, st.finished_scores,
                  st.finished_flags, st.finished_lens, st.heuristic, st.status, st.tokens, step, k, int(max_length),
-                 float(length_penalty), early_code(early_stopping))
+                 float(length_penalty), early_code(early_stopping), bool(logits_normalized))

@@ -6,7 +6,8 @@
 // Two launches, no float atomics, no cross-workgroup flags:
 //   1. beam_topk_kernel, grid (B * k), 512 threads: row r's lse = max + log(sum exp(x - max)) (fp32, fixed reduction order), then
 //      its top Kr = min(K, V) candidates by score = running_score[r] + (x - lse) (fp32), ties to the lower token.  Selection by
-//      score, not by logit: fp32 rounding can give two logits one score, and the global order breaks that tie by index.  Any
+//      score, not by logit: fp32 rounding can give two logits one score, and the global order breaks that tie by index.  With
+//      `norm` (rows processed by process_logits_kernel: log-probabilities with -inf bans) both lse passes are skipped, lse = 0.  Any
 //      candidate of the global top K of a batch item is in its own row's top K, so the per-row lists hold the answer exactly.
 //      The K-th largest score key comes from the sampler's three-pass radix select (sample_kernels.h: order-preserving keys, LDS
 //      histograms with integer atomics); the candidates are then collected in vocabulary order by a block scan of per-thread
@@ -51,6 +52,7 @@ struct BeamArgs {
   int32_t B, k, V, K, Kr, Lseq, cap, max_length, early;  // early: 0 False, 1 True, 2 "never"
   float lp;
   int32_t vec;
+  int32_t norm;             // the rows are log-probabilities already: lse = 0
 };
 
 // ---- stage 1: per row lse and top Kr candidates ----
@@ -108,25 +110,28 @@ __global__ __launch_bounds__(BEAM_TOPK_THREADS) void beam_topk_kernel(BeamArgs a
     return r;
   };
 
-  float mx = -INFINITY;
-  for (int i = 0; i < ntiles; ++i) {
-    float x[8];
-    load(i, x);
+  float lse = 0.f;
+  if (!a.norm) {
+    float mx = -INFINITY;
+    for (int i = 0; i < ntiles; ++i) {
+      float x[8];
+      load(i, x);
 #pragma unroll
-    for (int c = 0; c < 8; ++c) mx = fmaxf(mx, x[c]);  // (NaN: fmaxf skips it; the sum below turns NaN)
-  }
-  mx = block_max(mx);
-  float sum = 0.f;
-  for (int i = 0; i < ntiles; ++i) {
-    float x[8];
-    load(i, x);
-    const int j0 = i * BEAM_TILE + tid * 8;
+      for (int c = 0; c < 8; ++c) mx = fmaxf(mx, x[c]);  // (NaN: fmaxf skips it; the sum below turns NaN)
+    }
+    mx = block_max(mx);
+    float sum = 0.f;
+    for (int i = 0; i < ntiles; ++i) {
+      float x[8];
+      load(i, x);
+      const int j0 = i * BEAM_TILE + tid * 8;
 #pragma unroll
-    for (int c = 0; c < 8; ++c)
-      if (j0 + c < V) sum += expf(x[c] - mx);
+      for (int c = 0; c < 8; ++c)
+        if (j0 + c < V) sum += expf(x[c] - mx);
+    }
+    sum = block_sum(sum);
+    lse = mx + logf(sum);
   }
-  sum = block_sum(sum);
-  const float lse = mx + logf(sum);
 
   // f(keys[8], j0) over the row's tiles in order: keys of the candidate scores rs + (x - lse)
   auto tiles = [&](auto&& f) {

@@ -21,6 +21,7 @@
 #include "decode_kernels.h"
 #include "sample_kernels.h"
 #include "beam_kernels.h"
+#include "logits_kernels.h"
 
 using namespace fat5;
 
@@ -1721,6 +1722,7 @@ int fat5_beam_step(const fat5_beam_params* p, void* stream_) {
   a.ws_tok = reinterpret_cast<int32_t*>(a.ws_score + (size_t)p->B * p->k * a.K);
   a.Lseq = p->seq_len, a.cap = p->capacity, a.max_length = p->max_length, a.early = p->early_stopping;
   a.lp = p->length_penalty;
+  a.norm = p->logits_normalized != 0;
   a.vec = aligned16(p->logits) && p->row_stride % 8 == 0;
   hipStream_t stream = (hipStream_t)stream_;
   const dim3 rows(p->B * p->k);
@@ -1732,6 +1734,63 @@ int fat5_beam_step(const fat5_beam_params* p, void* stream_) {
   hipLaunchKernelGGL(beam_update_kernel, dim3(p->B), dim3(BEAM_THREADS), 0, stream, a);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "beam_step update launch");
+  return FAT5_OK;
+}
+
+// ---- logits processors (logits_kernels.h) ----
+size_t fat5_sizeof_logits_params(void) { return sizeof(fat5_logits_params); }
+
+int fat5_process_logits(const fat5_logits_params* p, void* stream_) {
+  const char* what = "process_logits";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (p->rows < 0) return fail(FAT5_EINVAL, "%s: rows %d", what, p->rows);
+  if (p->V < 2 || p->V > LOGITS_MAX_V) return fail(FAT5_EINVAL, "%s: V %d outside [2, %d]", what, p->V, LOGITS_MAX_V);
+  if (p->dtype != FAT5_F32 && p->dtype != FAT5_F16 && p->dtype != FAT5_BF16) return fail(FAT5_EINVAL, "%s: dtype %d", what, p->dtype);
+  if (p->row_stride < p->V) return fail(FAT5_EINVAL, "%s: row_stride %lld < V %d", what, (long long)p->row_stride, p->V);
+  if (p->out_stride < p->V) return fail(FAT5_EINVAL, "%s: out_stride %lld < V %d", what, (long long)p->out_stride, p->V);
+  if (p->seq_len < 1 || p->seq_len > LOGITS_MAX_SEQ) return fail(FAT5_EINVAL, "%s: seq_len %d outside [1, %d]", what, p->seq_len, LOGITS_MAX_SEQ);
+  if (p->seq_stride < p->seq_len) return fail(FAT5_EINVAL, "%s: seq_stride %lld < seq_len %d", what, (long long)p->seq_stride, p->seq_len);
+  if (!std::isfinite(p->repetition_penalty) || !(p->repetition_penalty > 0.f))
+    return fail(FAT5_EINVAL, "%s: repetition_penalty %g (finite and > 0)", what, (double)p->repetition_penalty);
+  if (p->no_repeat_ngram_size < 0) return fail(FAT5_EINVAL, "%s: no_repeat_ngram_size %d (>= 0)", what, p->no_repeat_ngram_size);
+  if (p->min_length < 0) return fail(FAT5_EINVAL, "%s: min_length %d (>= 0)", what, p->min_length);
+  if (p->eos_token_id < 0 || p->eos_token_id >= p->V) return fail(FAT5_EINVAL, "%s: eos_token_id %d outside [0, V)", what, p->eos_token_id);
+  if (p->n_suppress < 0 || p->n_suppress > LOGITS_MAX_SUPPRESS)
+    return fail(FAT5_EINVAL, "%s: n_suppress %d outside [0, %d]", what, p->n_suppress, LOGITS_MAX_SUPPRESS);
+  const size_t es = p->dtype == FAT5_F32 ? 4 : 2;
+  if (!p->logits || (reinterpret_cast<uintptr_t>(p->logits) % es)) return fail(FAT5_EINVAL, "%s: logits: null or misaligned pointer", what);
+  if (!p->out || (reinterpret_cast<uintptr_t>(p->out) & 3)) return fail(FAT5_EINVAL, "%s: out: null or misaligned pointer", what);
+  if (!p->sequences || (reinterpret_cast<uintptr_t>(p->sequences) & 7)) return fail(FAT5_EINVAL, "%s: sequences: null or misaligned pointer", what);
+  if (!p->lengths || (reinterpret_cast<uintptr_t>(p->lengths) & 3)) return fail(FAT5_EINVAL, "%s: lengths: null or misaligned pointer", what);
+  if (p->n_suppress > 0 && (!p->suppress_tokens || (reinterpret_cast<uintptr_t>(p->suppress_tokens) & 3)))
+    return fail(FAT5_EINVAL, "%s: suppress_tokens: null or misaligned pointer", what);
+  const bool inplace = static_cast<const void*>(p->out) == p->logits;
+  if (inplace && (p->dtype != FAT5_F32 || p->out_stride != p->row_stride))
+    return fail(FAT5_EINVAL, "%s: in place (out == logits) needs fp32 logits and out_stride == row_stride", what);
+  if (p->rows == 0) return FAT5_OK;
+  LogitsArgs a = {};
+  a.logits = p->logits;
+  a.stride = p->row_stride;
+  a.out = p->out;
+  a.out_stride = p->out_stride;
+  a.seq = p->sequences;
+  a.seq_stride = p->seq_stride;
+  a.lengths = p->lengths;
+  a.suppress = p->n_suppress > 0 ? p->suppress_tokens : nullptr;
+  a.V = p->V, a.seq_len = p->seq_len, a.ngram = p->no_repeat_ngram_size, a.min_length = p->min_length, a.eos = p->eos_token_id;
+  a.n_suppress = p->n_suppress;
+  a.log_softmax = p->log_softmax != 0;
+  a.copy = !inplace || a.log_softmax;
+  a.penalty = p->repetition_penalty;
+  a.vec = aligned16(p->logits) && p->row_stride % 8 == 0;
+  a.vec_out = aligned16(p->out) && p->out_stride % 4 == 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 grid(p->rows);
+  if (p->dtype == FAT5_F32) hipLaunchKernelGGL((process_logits_kernel<FAT5_F32>), grid, dim3(LOGITS_THREADS), 0, stream, a);
+  else if (p->dtype == FAT5_F16) hipLaunchKernelGGL((process_logits_kernel<FAT5_F16>), grid, dim3(LOGITS_THREADS), 0, stream, a);
+  else hipLaunchKernelGGL((process_logits_kernel<FAT5_BF16>), grid, dim3(LOGITS_THREADS), 0, stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "process_logits launch");
   return FAT5_OK;
 }
 

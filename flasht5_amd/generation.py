@@ -21,6 +21,11 @@ Beam search (`num_beams=k > 1`) runs the encoder and the cross K / 
 B * k beam rows through the decode kernel's `cache_batch_idx`; the self-attention caches hold B * k rows and are never copied
 or reordered: each beam reads its history through the `cache_row_batch` table of parents, which the beam-step kernel
 (flasht5_amd/beam.py) reorders in place with the running and finished sequences.  Decode step plus beam step is one graph.
+
+Logits processors (`repetition_penalty`, `no_repeat_ngram_size`, `min_length`, `suppress_tokens`) are one more HIP
+launch between the decode step and the argmax / sampler / beam step (flasht5_amd/logits_process.py): it reads the running
+sequences (`labels`, `running_seqs`) and `cache_seqlens` on the device, so the step stays one graph.  With all of them at
+their defaults the launch is not made.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -126,10 +131,19 @@ def decode_step(model, state, token_ids):
     return model.lm_head(h)[:, 0]
 
 
-def _greedy_step(model, state, tok, labels, seen_eos):
+def _processed(logits, sequences, lengths, proc, log_softmax=False):
+    """the logits processors over the rows' running sequences (`proc`: None, or process_logits' keyword arguments with the
+    suppressed ids already on the device); lengths: cache_seqlens after the increment, the start token included"""
+    if proc is None:
+        return logits
+    from .logits_process import process_logits
+    return process_logits(logits, sequences, lengths, log_softmax=log_softmax, **proc)
+
+
+def _greedy_step(model, state, tok, labels, seen_eos, proc=None):
     """decode_step + argmax: the token goes to `tok` and to column cache_seqlens of `labels` (a device-side index), and rows that
     produced a 1 are marked in `seen_eos` -- nothing here reads the host, so the same code is captured as it is"""
-    logits = decode_step(model, state, tok)
+    logits = _processed(decode_step(model, state, tok), labels, state.cache_seqlens, proc)
     nxt = logits.argmax(-1)
     tok.copy_(nxt)
     col = state.cache_seqlens.long().unsqueeze(1)  # (already incremented: the new token's column)
@@ -137,12 +151,13 @@ def _greedy_step(model, state, tok, labels, seen_eos):
     seen_eos.logical_or_(nxt == 1)
 
 
-def _sample_step(model, state, tok, labels, seen_eos, sampling):
+def _sample_step(model, state, tok, labels, seen_eos, sampling, proc=None):
     """decode_step + sample_logits, with _greedy_step's bookkeeping; the Philox counter of row b is cache_seqlens[b] after the
-    increment (the new token's position), read on the device -- so the captured step draws a fresh uniform at every replay"""
+    increment (the new token's position), read on the device -- so the captured step draws a fresh uniform at every replay.
+    The processors run before the warpers, as in HF: the sampler gets the processed fp32 row"""
     from .sampling import sample_logits
     temperature, top_k, top_p, seed = sampling
-    logits = decode_step(model, state, tok)
+    logits = _processed(decode_step(model, state, tok), labels, state.cache_seqlens, proc)
     nxt = sample_logits(logits, temperature, top_k, top_p, seed=seed, offsets=state.cache_seqlens)
     tok.copy_(nxt)
     col = state.cache_seqlens.long().unsqueeze(1)
@@ -160,22 +175,27 @@ def finish_labels(labels):
     return labels.masked_fill(~keep, 0)
 
 
-def _beam_step(model, state, tok, bs, opts):
+def _beam_step(model, state, tok, bs, opts, proc=None):
     """decode_step + the beam-step kernel: the next tokens go straight into `tok`; the step count is cache_seqlens after the
-    increment, read on the device -- nothing here reads the host, so the same code is captured as it is"""
+    increment, read on the device -- nothing here reads the host, so the same code is captured as it is.  With processors the
+    B * k running sequences edit log_softmax(logits) and the beam step scores those rows without renormalising (HF's order)"""
     from .beam import beam_step
     max_length, length_penalty, early_stopping = opts
     logits = decode_step(model, state, tok)
+    if proc is not None:
+        logits = _processed(logits, bs.running_seqs.view(logits.shape[0], -1), state.cache_seqlens, proc, log_softmax=True)
     bs.tokens = tok
-    beam_step(logits, bs, state.cache_seqlens, max_length, length_penalty, early_stopping)
+    beam_step(logits, bs, state.cache_seqlens, max_length, length_penalty, early_stopping, logits_normalized=proc is not None)
 
 
-def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, length_penalty, early_stopping, return_scores):
+def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, length_penalty, early_stopping, return_scores,
+                   proc=None):
     from .beam import new_state, keep_going
     B = input_ids.shape[0]
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask, num_beams=k)
     bs = new_state(B, k, int(max_length) + 1, state.capacity, dev)
+    proc = _proc_on_device(proc, dev)
     bs.cache_row_batch = state.row_batch  # (one table: the decode kernel reads it, the beam step reorders it)
     tok = torch.zeros((B * k,), dtype=torch.long, device=dev)
     opts = (int(max_length), float(length_penalty), early_stopping)
@@ -186,12 +206,12 @@ def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, le
             if g is not None:
                 g.replay()
             else:
-                _beam_step(model, state, tok, bs, opts)
+                _beam_step(model, state, tok, bs, opts, proc)
             steps += 1
             if not bool(keep_going(bs.status, early_stopping)):
                 break
             if graph and g is None and steps < max_length:
-                g = _capture_call(lambda: _beam_step(model, state, tok, bs, opts))
+                g = _capture_call(lambda: _beam_step(model, state, tok, bs, opts, proc))
     finally:
         del g
     seqs = bs.finished_seqs[:, :R].reshape(B * R, -1)
@@ -205,7 +225,7 @@ def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, le
 @torch.no_grad()
 def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, *, do_sample=False, temperature=1.0, top_k=50,
              top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
-             return_scores=False):
+             return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -219,18 +239,31 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     token; the first step runs eagerly (it also builds what the step allocates lazily), so both modes run the same kernels with the
     same arguments and give the same tokens.
 
-    num_beams=k in [2, 16]: HF's beam search (transformers 5.x `_beam_search`, one EOS id 1, max_new_tokens = max_length, no logits
-    processors) with `num_return_sequences`, `length_penalty` and `early_stopping` (False, True or "never") as HF means them.
+    num_beams=k in [2, 16]: HF's beam search (transformers 5.x `_beam_search`, one EOS id 1, max_new_tokens = max_length) with `num_return_sequences`, `length_penalty` and `early_stopping` (False, True or "never") as HF means them.
     Returns (B * num_return_sequences, 1 + T) int64: column 0 is the start token 0, then each hypothesis's tokens including its
     EOS, 0 past its end; T is the longest returned hypothesis.  return_scores=True adds HF's `sequences_scores`
     (B * num_return_sequences,) fp32.  The beam arguments are checked on the host before the encoder runs; do_sample=True with
-    beams is rejected.  num_beams=1 is the greedy / sampled path above, unchanged."""
+    beams is rejected.  num_beams=1 is the greedy / sampled path above, unchanged.
+
+    Logits processors, as HF means them and in HF's order, in all three modes, eager and graph=True: `repetition_penalty`
+    (> 0, 1 = off; the start token counts as seen, as in HF), `no_repeat_ngram_size` (0 = off), `min_length` (EOS is banned while
+    the sequence, start token included, is shorter; 0 = off) and `suppress_tokens` (ids that are never produced, e.g. the
+    sentinels; a list of ints below the vocabulary size, moved to the device once per call).  Greedy takes the argmax of the
+    processed row, sampling hands it to `sample_logits` (processors before warpers), beam search processes log_softmax(logits)
+    and does not renormalise.  They are checked on the host before the encoder runs; with every one at its default no launch
+    is added and the step is the code path above.  The sequence buffer of a call with processors holds at most 4096 columns
+    (max_length <= 4095)."""
     from .beam import check_args as check_beam_args
     check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample)
+    proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens)
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
-                              early_stopping, return_scores)
+                              early_stopping, return_scores, proc)
+    proc = _proc_on_device(proc, input_ids.device)
     step = _greedy_step
+    if proc is not None:
+        def step(model, state, tok, labels, seen_eos):
+            _greedy_step(model, state, tok, labels, seen_eos, proc)
     if do_sample:
         from .sampling import check_args
         check_args(temperature, top_k, top_p)
@@ -239,7 +272,7 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
         sampling = (float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF)
 
         def step(model, state, tok, labels, seen_eos):
-            _sample_step(model, state, tok, labels, seen_eos, sampling)
+            _sample_step(model, state, tok, labels, seen_eos, sampling, proc)
     B = input_ids.shape[0]
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask)
@@ -262,6 +295,27 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     finally:
         del g
     return finish_labels(labels[:, :steps + 1])
+
+
+def _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens):
+    """host-side validation of the logits processors -> None when all of them are off, else process_logits' keyword arguments"""
+    from .logits_process import MAX_SEQ_LEN, active, check_args
+    check_args(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, model.lm_head.weight.shape[0])
+    if not active(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens):
+        return None
+    if int(max_length) + 1 > MAX_SEQ_LEN:
+        raise ValueError(f"max_length {max_length}: the logits processors hold at most {MAX_SEQ_LEN} sequence columns "
+                         f"(max_length <= {MAX_SEQ_LEN - 1})")
+    return dict(repetition_penalty=float(repetition_penalty), no_repeat_ngram_size=int(no_repeat_ngram_size),
+                min_length=int(min_length), eos_token_id=1, suppress_tokens=suppress_tokens)
+
+
+def _proc_on_device(proc, device):
+    """the suppressed ids moved to the device, once per call"""
+    if proc is None:
+        return None
+    from .logits_process import suppress_to_device
+    return dict(proc, suppress_tokens=suppress_to_device(proc["suppress_tokens"], device))
 
 
 def _capture(model, state, tok, labels, seen_eos, step=_greedy_step):

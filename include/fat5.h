@@ -453,7 +453,9 @@ int fat5_sample_logits(const fat5_sample_params* p, void* hip_stream);
  * updated in place, so a captured step reads nothing from the host.  With s = clamp(step[b * k], 1, min(seq_len - 1, capacity))
  * (the tokens fed so far: cache_seqlens after the increment) and t = s - 1 (the cache position this step's decode wrote):
  *   - Scores.  Candidate (beam i, token x) of batch item b scores running_scores[b, i] + (x_f - lse_i), in fp32 from the fp32
- *     value of the logit, lse_i = max + log(sum exp(x - max)) of row b * k + i.
+ *     value of the logit, lse_i = max + log(sum exp(x - max)) of row b * k + i.  With logits_normalized the rows are
+ *     log-probabilities already (fat5_process_logits with log_softmax: HF applies its logits processors to log_softmax(logits)
+ *     and does not renormalise): lse_i = 0 and the lse passes are not run.
  *   - Top K.  The K best candidates by score; on an equal score the lower flat index i * V + token wins.
  *   - Stopping.  A candidate hits the stopping criterion when its token is 1 (EOS) or when s >= max_length (it is the
  *     max_length-th generated token): HF with max_new_tokens = max_length.
@@ -500,10 +502,63 @@ typedef struct fat5_beam_params {
   float length_penalty;
   void* workspace;            /* fat5_beam_step_workspace_bytes(); 16-byte aligned */
   size_t workspace_bytes;
+  int32_t logits_normalized;  /* non-zero: the rows are log-probabilities already (fat5_process_logits with log_softmax): lse = 0,
+                                 score = running + x.  0: the rows are logits, as above (same launches, same bits) */
 } fat5_beam_params;
 size_t fat5_sizeof_beam_params(void);
 size_t fat5_beam_step_workspace_bytes(const fat5_beam_params* p);
 int fat5_beam_step(const fat5_beam_params* p, void* hip_stream);
+
+/*
+ * Logits processors: repetition penalty, no-repeat n-grams, minimum length and suppressed tokens over (rows, V) logits in one
+ * launch (logits_kernels.h), in HF's order and meaning (RepetitionPenaltyLogitsProcessor,
+ * NoRepeatNGramLogitsProcessor, MinLengthLogitsProcessor, SuppressTokensLogitsProcessor, transformers 5.x).  The running
+ * sequences and their lengths are read on the device, so the launch is captured with the decode step and sits in front of the
+ * argmax, fat5_sample_logits or fat5_beam_step (logits_normalized).
+ * Per row r: seq = sequences[r, 0:s), s = clamp(lengths[r], 0, seq_len).  s counts the start token in column 0: it is HF's
+ * input_ids.shape[-1] for an encoder-decoder model, and cache_seqlens after the decode step's increment.  x_j is the fp32 value
+ * of logits[r, j]; with log_softmax, x_j = fp32(logit) - lse_r, lse_r = max + log(sum exp(x - max)) as fat5_beam_step forms it
+ * (fp32, fixed reduction order).  Then
+ *   1. repetition_penalty = theta (1 = off): every token t that occurs in seq gets, once however often it occurs,
+ *      y_t = x_t < 0 ? x_t * theta : x_t / theta (fp32, IEEE division).  The start token is part of seq, as in HF.
+ *   2. no_repeat_ngram_size = n (0 = off): if s >= n, for every i in [0, s - n] with seq[i : i+n-1] == seq[s-n+1 : s],
+ *      y[seq[i+n-1]] = -inf (n = 1 bans every token seen).
+ *   3. min_length = m (0 = off): if s < m, y[eos_token_id] = -inf.
+ *   4. suppress_tokens (n_suppress device int32 ids): y[t] = -inf always.
+ * Every other y_j = x_j.  A ban wins over a penalty.  out is (rows, V) fp32; it may be `logits` itself when dtype is FAT5_F32
+ * and out_stride == row_stride (in place).  A sequence entry outside [0, V) is never used as an index: it counts as "no token",
+ * which is neither penalised nor banned and equals only another such entry in an n-gram comparison.  A suppressed id outside
+ * [0, V) is skipped.  A row's result depends on that row only and is bitwise reproducible (no float atomics); the launch reads
+ * no host value that changes between steps.  16-byte loads / stores on 16-byte aligned bases with row strides that are
+ * multiples of 8 (logits) / 4 (out) elements, element accesses otherwise.  rows == 0 is a no-op.
+ * Rejected with FAT5_EINVAL before anything is launched: rows < 0, V outside [2, 2^20], dtype outside {FAT5_F32, FAT5_F16,
+ * FAT5_BF16}, row_stride or out_stride < V, seq_len outside [1, 4096], seq_stride < seq_len, a non-finite or non-positive
+ * repetition_penalty, no_repeat_ngram_size < 0, min_length < 0, eos_token_id outside [0, V), n_suppress outside [0, 4096],
+ * NULL or misaligned logits / out / sequences / lengths (/ suppress_tokens with n_suppress > 0), out == logits with a 16-bit
+ * dtype or unequal strides.
+ */
+typedef struct fat5_logits_params {
+  int32_t rows, V;
+  int32_t dtype;                /* logits: FAT5_F32 | FAT5_F16 | FAT5_BF16 */
+  int32_t log_softmax;          /* non-zero: x = logit - lse */
+  const void* logits;           /* (rows, V), row stride row_stride elements, innermost stride 1 */
+  int64_t row_stride;
+  float* out;                   /* (rows, V) fp32, row stride out_stride elements */
+  int64_t out_stride;
+  const int64_t* sequences;     /* (rows, seq_len) int64 device array, row stride seq_stride elements */
+  int64_t seq_stride;
+  const int32_t* lengths;       /* (rows,) int32 device array */
+  int32_t seq_len;              /* 1..4096 */
+  float repetition_penalty;     /* > 0, finite; 1: off */
+  int32_t no_repeat_ngram_size; /* >= 0; 0: off */
+  int32_t min_length;           /* >= 0; 0: off */
+  int32_t eos_token_id;         /* [0, V) */
+  int32_t n_suppress;           /* 0..4096 */
+  const int32_t* suppress_tokens; /* (n_suppress,) int32 device array, or NULL when n_suppress is 0 */
+} fat5_logits_params;
+/* sizeof(fat5_logits_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_logits_params(void);
+int fat5_process_logits(const fat5_logits_params* p, void* hip_stream);
 
 /*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
