@@ -88,15 +88,15 @@ static hipError_t launch_kv64_mixed(const AttnArgs& a, int grid, hipStream_t s) 
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, as);
   return hipGetLastError();
 }
-// nw == 2: the half-length variant (128-key workgroups, two wave pairs each walking half of the query steps); nw == 3: both in one
+// kKv64Half: the half-length variant (128-key workgroups, two wave pairs each walking half of the query steps); kKv64Mixed: both in one
 // launch (a.mix_full pairs per XCD as 256-key workgroups, the others half-length); otherwise 256 keys
 hipError_t CAT(launch_bwd_kv64_d, FAT5_INST_D)(const AttnArgs& a, int bf16, int bias, int nw, int grid, hipStream_t s) {
-  if (nw == 3) {
+  if (nw == kKv64Mixed) {
     if (bias == FAT5_BIAS_RPE1D)
       return bf16 ? launch_kv64_mixed<FAT5_INST_D, true, FAT5_BIAS_RPE1D>(a, grid, s) : launch_kv64_mixed<FAT5_INST_D, false, FAT5_BIAS_RPE1D>(a, grid, s);
     return bf16 ? launch_kv64_mixed<FAT5_INST_D, true, FAT5_BIAS_NONE>(a, grid, s) : launch_kv64_mixed<FAT5_INST_D, false, FAT5_BIAS_NONE>(a, grid, s);
   }
-  return nw == 2 ? launch_kv64_bias<true>(a, bf16, bias, grid, s) : launch_kv64_bias<false>(a, bf16, bias, grid, s);
+  return nw == kKv64Half ? launch_kv64_bias<true>(a, bf16, bias, grid, s) : launch_kv64_bias<false>(a, bf16, bias, grid, s);
 }
 // dK/dV (self-sufficient 256-key form) and dQ in one launch: a.n_kv_blocks workgroups of the former, then the dQ workgroups
 template <int D, bool BF16, int BIAS, bool QDG = false>

@@ -27,9 +27,9 @@ static hipError_t launch_w1s(const AttnArgs& a, int grid, hipStream_t s) {
 }
 template <bool BF16, int BIAS>
 static hipError_t launch_w1(const AttnArgs& a, int nw, int grid, hipStream_t s) {
-  return nw == 5 ? launch_w1s<BF16, BIAS, true>(a, grid, s) : launch_w1s<BF16, BIAS, false>(a, grid, s);
+  return nw == kFwd64Spread ? launch_w1s<BF16, BIAS, true>(a, grid, s) : launch_w1s<BF16, BIAS, false>(a, grid, s);
 }
-// nw == 5: the ring requests spread over the MFMA gaps (grids of at most one round: see attn_fwd64_body)
+// kFwd64Spread: the ring requests spread over the MFMA gaps (grids of at most one round: see attn_fwd64_body)
 hipError_t launch_fwd64_d128(const AttnArgs& a, int bf16, int bias, int nw, int grid, hipStream_t s) {
   if (bias == FAT5_BIAS_RPE1D) return bf16 ? launch_w1<true, FAT5_BIAS_RPE1D>(a, nw, grid, s) : launch_w1<false, FAT5_BIAS_RPE1D>(a, nw, grid, s);
   if (bias == FAT5_BIAS_NONE) return bf16 ? launch_w1<true, FAT5_BIAS_NONE>(a, nw, grid, s) : launch_w1<false, FAT5_BIAS_NONE>(a, nw, grid, s);
@@ -79,7 +79,7 @@ static hipError_t launch64_bias(const AttnArgs& a, int bf16, int bias, int grid,
     return bf16 ? launch64<FAT5_INST_D, true, FAT5_BIAS_RPE1D, KSPLIT>(a, grid, s) : launch64<FAT5_INST_D, false, FAT5_BIAS_RPE1D, KSPLIT>(a, grid, s);
   return bf16 ? launch64<FAT5_INST_D, true, FAT5_BIAS_NONE, KSPLIT>(a, grid, s) : launch64<FAT5_INST_D, false, FAT5_BIAS_NONE, KSPLIT>(a, grid, s);
 }
-// nw == 3: both workgroup forms in one launch (a.mix_*; grid = 256-row + 128-row workgroups)
+// kFwd64Mixed: both workgroup forms in one launch (a.mix_*; grid = 256-row + 128-row workgroups)
 template <bool BF16, int BIAS>
 static hipError_t launch64_mixed(const AttnArgs& a, int grid, hipStream_t s) {
   const size_t smem = std::max(Fwd64Cfg<FAT5_INST_D, false>::smem(a.R, BIAS), Fwd64Cfg<FAT5_INST_D, true>::smem(a.R, BIAS));
@@ -97,13 +97,13 @@ static hipError_t launch64_mixed(const AttnArgs& a, int grid, hipStream_t s) {
   return hipGetLastError();
 }
 
-// nw == 2: the key-split variant (two waves per 64 query rows, 128-row workgroups); otherwise 256-row workgroups
+// kFwd64KSplit: the key-split variant (two waves per 64 query rows, 128-row workgroups); otherwise 256-row workgroups
 hipError_t CAT(launch_fwd64_d, FAT5_INST_D)(const AttnArgs& a, int bf16, int bias, int nw, int grid, hipStream_t s) {
-  if (nw == 3) {
+  if (nw == kFwd64Mixed) {
     if (bias == FAT5_BIAS_RPE1D) return bf16 ? launch64_mixed<true, FAT5_BIAS_RPE1D>(a, grid, s) : launch64_mixed<false, FAT5_BIAS_RPE1D>(a, grid, s);
     return bf16 ? launch64_mixed<true, FAT5_BIAS_NONE>(a, grid, s) : launch64_mixed<false, FAT5_BIAS_NONE>(a, grid, s);
   }
-  return nw == 2 ? launch64_bias<true>(a, bf16, bias, grid, s) : launch64_bias<false>(a, bf16, bias, grid, s);
+  return nw == kFwd64KSplit ? launch64_bias<true>(a, bf16, bias, grid, s) : launch64_bias<false>(a, bf16, bias, grid, s);
 }
 
 #endif

@@ -48,7 +48,7 @@ static hipError_t launch_split(const AttnArgs& a, int grid, hipStream_t s) {
 
 template <int D, bool BF16, int BIAS, bool BDMA = false>
 static hipError_t launch_nw(const AttnArgs& a, int nw, int grid, hipStream_t s) {
-  if (nw == -4) return launch_split<D, BF16, BIAS, BDMA>(a, grid, s);  // two waves per 32 query rows (short sequences)
+  if (nw == kFwdSplit) return launch_split<D, BF16, BIAS, BDMA>(a, grid, s);  // two waves per 32 query rows (short sequences)
   if (nw == 2) return launch_one<D, BF16, BIAS, 2, BDMA>(a, grid, s);
   if (nw == 8) return launch_one<D, BF16, BIAS, 8, BDMA>(a, grid, s);
   return launch_one<D, BF16, BIAS, 4, BDMA>(a, grid, s);
