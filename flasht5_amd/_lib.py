@@ -87,6 +87,20 @@ class DecodeParams(ctypes.Structure):
     ]
 
 
+class DecodeChunkParams(ctypes.Structure):
+    """Mirror of `fat5_decode_chunk_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("M", ctypes.c_int32), ("D", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("capacity", ctypes.c_int32), ("N", ctypes.c_int32), ("causal", ctypes.c_int32), ("cache_seqlens", ctypes.c_void_p),
+        ("sm_scale", ctypes.c_float), ("bias_mode", ctypes.c_int32), ("rpe_radius", ctypes.c_int32), ("rpe1d", ctypes.c_void_p),
+        ("q", ctypes.c_void_p), ("k_cache", ctypes.c_void_p), ("v_cache", ctypes.c_void_p), ("k_new", ctypes.c_void_p),
+        ("v_new", ctypes.c_void_p), ("o", ctypes.c_void_p), ("lse", ctypes.c_void_p),
+        ("q_stride", c_i64x3), ("k_cache_stride", c_i64x3), ("v_cache_stride", c_i64x3),
+        ("k_new_stride", c_i64x3), ("v_new_stride", c_i64x3), ("o_stride", c_i64x3),
+        ("num_splits", ctypes.c_int32), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 class SampleParams(ctypes.Structure):
     """Mirror of `fat5_sample_params` (include/fat5.h) -- field order must match exactly."""
     _fields_ = [
@@ -131,6 +145,7 @@ EXPORTS = (
     "fat5_rope_apply", "fat5_sizeof_rope_params",
     "fat5_fire_fwd", "fat5_fire_bwd", "fat5_fire_bwd_workspace_bytes", "fat5_sizeof_fire_params",
     "fat5_attn_decode", "fat5_attn_decode_workspace_bytes", "fat5_sizeof_decode_params",
+    "fat5_attn_decode_chunk", "fat5_attn_decode_chunk_workspace_bytes", "fat5_sizeof_decode_chunk_params",
     "fat5_sample_logits", "fat5_sizeof_sample_params",
     "fat5_beam_step", "fat5_beam_step_workspace_bytes", "fat5_sizeof_beam_params",
     "fat5_process_logits", "fat5_sizeof_logits_params",
@@ -229,6 +244,14 @@ def load():
     if lib.fat5_sizeof_decode_params() != ctypes.sizeof(DecodeParams):
         raise ImportError(f"fat5_decode_params layout mismatch: library {lib.fat5_sizeof_decode_params()} B, "
                           f"binding {ctypes.sizeof(DecodeParams)} B")
+    lib.fat5_attn_decode_chunk.restype = ctypes.c_int
+    lib.fat5_attn_decode_chunk.argtypes = [ctypes.POINTER(DecodeChunkParams), ctypes.c_void_p]
+    lib.fat5_attn_decode_chunk_workspace_bytes.restype = ctypes.c_size_t
+    lib.fat5_attn_decode_chunk_workspace_bytes.argtypes = [ctypes.POINTER(DecodeChunkParams)]
+    lib.fat5_sizeof_decode_chunk_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_decode_chunk_params() != ctypes.sizeof(DecodeChunkParams):
+        raise ImportError(f"fat5_decode_chunk_params layout mismatch: library {lib.fat5_sizeof_decode_chunk_params()} B, "
+                          f"binding {ctypes.sizeof(DecodeChunkParams)} B")
     lib.fat5_sample_logits.restype = ctypes.c_int
     lib.fat5_sample_logits.argtypes = [ctypes.POINTER(SampleParams), ctypes.c_void_p]
     lib.fat5_sizeof_sample_params.restype = ctypes.c_size_t

@@ -186,10 +186,18 @@ class FlashT5Attention(nn.Module):
         RoPE: `position` is a (1,) int64 device tensor (the step's position, shared by the batch); q is rotated with row `position`
         of (cos, sin), the new k and v with that row of (cos_k, sin_k).  Forward only; nothing of the training path changes.
         Beam search: `cache_batch_idx` (B,) int32 lets B * k beam rows read B cross-attention caches; `cache_row_batch`
-        (B, L_cap) int32 reads each self-attention key row from the cache row of the beam that wrote it (decode.py)."""
+        (B, L_cap) int32 reads each self-attention key row from the cache row of the beam that wrote it (decode.py).
+
+        A chunk of M > 1 tokens (`hidden_states` (B, M, d_model); returns (B, M, d_model)) goes through
+        flash_attn_with_kvcache_chunk: self-attention appends the M rows and is causal inside the chunk, row i at position
+        cache_seqlens[b] + i; cross-attention is not causal and has no bias.  RoPE uses rows position + arange(M) of the tables,
+        selected and clamped on the device.  The cache maps are for one row only."""
         self.decode_supported()
         from .decode import flash_attn_with_kvcache
-        B = hidden_states.shape[0]
+        B, M = hidden_states.shape[:2]
+        if M > 1:
+            return self._forward_decode_chunk(hidden_states, k_cache, v_cache, cache_seqlens, position_bias, position,
+                                              cache_batch_idx, cache_row_batch)
         H, Dh = self.n_heads, self.key_value_proj_dim
         q = self.Wq(hidden_states).view(B, 1, H, Dh)
         is_self = cache_seqlens is not None
@@ -216,6 +224,41 @@ class FlashT5Attention(nn.Module):
         out = flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, self.softmax_scale, rpe1d, radius,
                                       cache_batch_idx=cache_batch_idx, cache_row_batch=cache_row_batch)
         return self.o(out.reshape(B, 1, self.inner_dim))
+
+    def _forward_decode_chunk(self, hidden_states, k_cache, v_cache, cache_seqlens, position_bias, position, cache_batch_idx,
+                              cache_row_batch):
+        """forward_decode for M > 1 rows: the same projections, rotation and bias rule on the chunk kernel"""
+        from .decode import flash_attn_with_kvcache_chunk
+        if cache_batch_idx is not None or cache_row_batch is not None:
+            raise ValueError("forward_decode: cache_batch_idx / cache_row_batch take one query row per step (beam search has no chunks)")
+        B, M = hidden_states.shape[:2]
+        H, Dh = self.n_heads, self.key_value_proj_dim
+        q = self.Wq(hidden_states).view(B, M, H, Dh)
+        is_self = cache_seqlens is not None
+        k = v = None
+        if is_self:
+            k = self.Wk(hidden_states).view(B, M, H, Dh)
+            v = self.Wv(hidden_states).view(B, M, H, Dh)
+        rpe1d, radius = None, 0
+        if self.rotary:
+            if position is None:
+                raise ValueError("forward_decode with RoPE needs the step's position (a (1,) int64 device tensor)")
+            cos, sin, cos_k, sin_k = self.pe_encoding.tables(q.device, q.dtype)
+            idx = (position + torch.arange(M, device=position.device)).clamp(0, cos.shape[0] - 1)  # (device-side: capturable)
+            rows = lambda t: None if t is None else t.index_select(0, idx)  # noqa: E731
+            if is_self:
+                q, k, v = apply_rotary_emb_qkv(q, k, v, rows(cos), rows(sin), rows(cos_k), rows(sin_k), self.pe_encoding.interleaved)
+            else:
+                q = apply_rotary_emb(q, rows(cos), rows(sin), self.pe_encoding.interleaved)
+        elif is_self:
+            if position_bias is None:
+                raise ValueError("forward_decode: T5 self-attention needs position_bias=(rpe1d, radius) from block 0's forward_1d()")
+            rpe1d, radius = position_bias
+            if self.attention_type == "triton":  # (the dense path adds the bias after a cast to the activation dtype)
+                rpe1d = rpe1d.to(q.dtype).float()
+        out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, cache_seqlens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
+                                            rpe_radius=radius)
+        return self.o(out.reshape(B, M, self.inner_dim))
 
     def project_kv(self, key_value_states):
         """the cross-attention K / V of an encoder output (B, L_enc, d_model) as (B, L_enc, H, D) caches for `forward_decode`:

@@ -20,6 +20,7 @@
 #include "rope_kernels.h"
 #include "fire_kernels.h"
 #include "decode_kernels.h"
+#include "decode_chunk_kernels.h"
 #include "sample_kernels.h"
 #include "beam_kernels.h"
 #include "logits_kernels.h"
@@ -1087,6 +1088,129 @@ int fat5_attn_decode(const fat5_decode_params* p, void* stream_) {
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "attn_decode launch");
+  return FAT5_OK;
+}
+
+// ---- chunked decode attention: M query rows per (b, h) against a KV cache (decode_chunk_kernels.h) ----
+size_t fat5_sizeof_decode_chunk_params(void) { return sizeof(fat5_decode_chunk_params); }
+
+// key-range splits per tile of CHUNK_TQ query rows, from host-known arguments only (decode_splits' rule with the tiles counted
+// as workgroups): two workgroups per CU of a 256-CU chip, no more splits than whole workgroup passes fit into the capacity
+static int chunk_splits(const fat5_decode_chunk_params* p) {
+  if (p->num_splits > 0) return p->num_splits;
+  const long wgs = (long)p->B * p->H * ((p->M + CHUNK_TQ - 1) / CHUNK_TQ);
+  const long pass = (long)(DEC_THREADS / (p->D / 8)) * DEC_UNROLL;
+  const long by_cap = std::max<long>(1, (p->capacity + pass - 1) / pass);
+  const long want = std::max<long>(1, (512 + wgs - 1) / wgs);
+  return (int)std::min<long>(DEC_MAX_SPLITS, std::min(want, by_cap));
+}
+
+static bool chunk_shape_ok(const fat5_decode_chunk_params* p) {
+  return p->B >= 1 && p->B <= 65535 && p->H >= 1 && p->H <= 65535 && p->M >= 1 && p->M <= CHUNK_MAX_M && (p->D == 64 || p->D == 128) &&
+         p->capacity >= 0 && p->num_splits >= 0 && p->num_splits <= DEC_MAX_SPLITS;
+}
+
+size_t fat5_attn_decode_chunk_workspace_bytes(const fat5_decode_chunk_params* p) {
+  if (!p || !chunk_shape_ok(p)) return 0;
+  const int s = chunk_splits(p);
+  if (s <= 1) return 0;
+  return align_up((size_t)p->B * p->H * p->M * s * (p->D + 2) * sizeof(float), 16);
+}
+
+static int chunk_check(const fat5_decode_chunk_params* p) {
+  const char* what = "attn_decode_chunk";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (p->D != 64 && p->D != 128) return fail(FAT5_EINVAL, "%s: head_dim %d (64 or 128)", what, p->D);
+  if (p->dtype != FAT5_F16 && p->dtype != FAT5_BF16) return fail(FAT5_EINVAL, "%s: dtype %d (FAT5_F16 or FAT5_BF16)", what, p->dtype);
+  if (p->B < 1 || p->B > 65535 || p->H < 1 || p->H > 65535)
+    return fail(FAT5_EINVAL, "%s: B %d / H %d outside [1, 65535]", what, p->B, p->H);
+  if (p->M < 1 || p->M > CHUNK_MAX_M) return fail(FAT5_EINVAL, "%s: M %d outside [1, %d]", what, p->M, CHUNK_MAX_M);
+  if (p->capacity < 0) return fail(FAT5_EINVAL, "%s: capacity %d", what, p->capacity);
+  if (p->causal != 0 && p->causal != 1) return fail(FAT5_EINVAL, "%s: causal %d (0 or 1)", what, p->causal);
+  if (p->num_splits < 0 || p->num_splits > DEC_MAX_SPLITS)
+    return fail(FAT5_EINVAL, "%s: num_splits %d (0 for the library's choice, or 1 to %d)", what, p->num_splits, DEC_MAX_SPLITS);
+  if (!p->cache_seqlens && (p->N < 0 || p->N > p->capacity))
+    return fail(FAT5_EINVAL, "%s: N %d outside [0, capacity %d] without cache_seqlens", what, p->N, p->capacity);
+  if (p->cache_seqlens && (reinterpret_cast<uintptr_t>(p->cache_seqlens) & 3))
+    return fail(FAT5_EINVAL, "%s: cache_seqlens misaligned", what);
+  if (p->bias_mode != FAT5_BIAS_NONE && p->bias_mode != FAT5_BIAS_RPE1D)
+    return fail(FAT5_EINVAL, "%s: bias_mode %d (FAT5_BIAS_NONE or FAT5_BIAS_RPE1D)", what, p->bias_mode);
+  if (p->bias_mode == FAT5_BIAS_RPE1D) {
+    if (p->rpe_radius < 1 || p->rpe_radius > 2048) return fail(FAT5_EINVAL, "%s: rpe_radius %d outside 1..2048", what, p->rpe_radius);
+    if (!p->rpe1d || (reinterpret_cast<uintptr_t>(p->rpe1d) & 3)) return fail(FAT5_EINVAL, "%s: RPE1D needs rpe1d (fp32, aligned)", what);
+  }
+  if ((p->k_new == nullptr) != (p->v_new == nullptr)) return fail(FAT5_EINVAL, "%s: k_new and v_new must both be given or both be NULL", what);
+  if (p->k_new && !p->cache_seqlens) return fail(FAT5_EINVAL, "%s: appending k_new / v_new needs cache_seqlens", what);
+  if (!std::isfinite(p->sm_scale)) return fail(FAT5_EINVAL, "%s: sm_scale must be finite", what);
+  struct { const void* ptr; const int64_t* st; const char* name; } t[] = {
+      {p->q, p->q_stride, "q"}, {p->k_cache, p->k_cache_stride, "k_cache"}, {p->v_cache, p->v_cache_stride, "v_cache"},
+      {p->k_new, p->k_new_stride, "k_new"}, {p->v_new, p->v_new_stride, "v_new"}, {p->o, p->o_stride, "o"}};
+  for (int k = 0; k < 6; ++k) {
+    const auto& e = t[k];
+    if ((k == 3 || k == 4) && !p->k_new) continue;  // (no append)
+    if (!e.ptr || !aligned16(e.ptr)) return fail(FAT5_EINVAL, "%s: %s: null or unaligned pointer (16-byte aligned base)", what, e.name);
+    for (int i = 0; i < 3; ++i)
+      if (e.st[i] % 8) return fail(FAT5_EINVAL, "%s: %s strides must be multiples of 8 elements (innermost stride 1)", what, e.name);
+  }
+  if (p->lse && (reinterpret_cast<uintptr_t>(p->lse) & 3)) return fail(FAT5_EINVAL, "%s: lse misaligned", what);
+  const size_t need = fat5_attn_decode_chunk_workspace_bytes(p);
+  if (need && (!p->workspace || !aligned16(p->workspace) || p->workspace_bytes < need))
+    return fail(FAT5_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", what, need, p->workspace_bytes);
+  return FAT5_OK;
+}
+
+extern "C++" template <int DT, int D, bool APPEND, bool BIAS>
+static void chunk_launch(const ChunkArgs& a, hipStream_t stream) {
+  const dim3 grid(((a.M + CHUNK_TQ - 1) / CHUNK_TQ) * a.splits, a.H, a.B);
+  if (a.splits == 1) {
+    hipLaunchKernelGGL((chunk_attn_kernel<DT, D, APPEND, BIAS, true>), grid, dim3(DEC_THREADS), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL((chunk_attn_kernel<DT, D, APPEND, BIAS, false>), grid, dim3(DEC_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((chunk_combine_kernel<DT, D>), dim3(a.M, a.H, a.B), dim3(D), 0, stream, a);
+  }
+}
+
+int fat5_attn_decode_chunk(const fat5_decode_chunk_params* p, void* stream_) {
+  if (int rc = chunk_check(p)) return rc;
+  ChunkArgs a = {};
+  a.q = p->q;
+  a.kc = p->k_cache;
+  a.vc = p->v_cache;
+  a.kn = p->k_new;
+  a.vn = p->v_new;
+  a.o = p->o;
+  a.lse = p->lse;
+  a.seqlens = p->cache_seqlens;
+  a.rpe1d = p->bias_mode == FAT5_BIAS_RPE1D ? p->rpe1d : nullptr;
+  a.ws = static_cast<float*>(p->workspace);
+  for (int i = 0; i < 3; ++i) {
+    a.q_s[i] = p->q_stride[i], a.o_s[i] = p->o_stride[i], a.kn_s[i] = p->k_new_stride[i], a.vn_s[i] = p->v_new_stride[i];
+    a.kc_s[i] = p->k_cache_stride[i], a.vc_s[i] = p->v_cache_stride[i];
+  }
+  a.B = p->B, a.H = p->H, a.M = p->M, a.cap = p->capacity, a.N = p->N, a.R = p->rpe_radius, a.causal = p->causal;
+  a.splits = chunk_splits(p);
+  a.scale_log2 = p->sm_scale * kLog2e;
+  const bool append = p->k_new != nullptr, bias = a.rpe1d != nullptr;
+  hipStream_t stream = (hipStream_t)stream_;
+  auto go = [&](auto dt_, auto d_) {
+    constexpr int DT = decltype(dt_)::value, D = decltype(d_)::value;
+    if (append) {
+      if (bias) chunk_launch<DT, D, true, true>(a, stream);
+      else chunk_launch<DT, D, true, false>(a, stream);
+    } else {
+      if (bias) chunk_launch<DT, D, false, true>(a, stream);
+      else chunk_launch<DT, D, false, false>(a, stream);
+    }
+  };
+  if (p->dtype == FAT5_F16) {
+    if (p->D == 64) go(IC<FAT5_F16>{}, IC<64>{});
+    else go(IC<FAT5_F16>{}, IC<128>{});
+  } else {
+    if (p->D == 64) go(IC<FAT5_BF16>{}, IC<64>{});
+    else go(IC<FAT5_BF16>{}, IC<128>{});
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "attn_decode_chunk launch");
   return FAT5_OK;
 }
 

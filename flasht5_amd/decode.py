@@ -8,6 +8,10 @@ row (B, 1, H, D) or None.  `cache_seqlens` holds each batch element's length BEF
 advances it.  With k / v the row is written into the caches at index cache_seqlens[b] inside the same launch.  The optional T5 bias
 is the (H, 2R+1) fp32 generator of the linear-memory mode, bottom-right aligned: the query sits at position L_b - 1.
 
+`flash_attn_with_kvcache_chunk` is the same call at seqlen_q = M (prompt prefill, speculative-decoding verification, M decoder rows
+against the encoder's K / V): q (B, M, H, D), k / v (B, M, H, D) or None, on the chunk kernel behind `fat5_attn_decode_chunk`
+(csrc/decode_chunk_kernels.h), causal inside the chunk with `causal=True`, the T5 bias bottom-right aligned per row.
+
 Forward only: inputs that require grad under grad mode are rejected.  There is no eager fallback: CPU tensors are rejected."""
 import math
 from typing import List, Optional
@@ -200,4 +204,141 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     else:
         o, lse = attn_decode(q, k_cache, v_cache, k, v, lens, scale, rpe1d, int(rpe_radius), bool(return_lse), int(num_splits),
                              cache_batch_idx, cache_row_batch)
+    return (o, lse) if return_lse else o
+
+
+# ------------------------------------------------------------------------------------------------ M query rows per (batch, head)
+def _chunk_params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse, sm_scale, causal, rpe1d, radius, num_splits):
+    B, M, H, D = q.shape
+    p = _lib.DecodeChunkParams()
+    p.B, p.H, p.M, p.D = B, H, M, D
+    p.dtype = _lib.dtype_code(q.dtype)
+    p.capacity = k_cache.shape[1]
+    p.N = k_cache.shape[1] if cache_seqlens is None else 0
+    p.causal = int(bool(causal))
+    p.cache_seqlens = cache_seqlens.data_ptr() if cache_seqlens is not None else None
+    p.sm_scale = float(sm_scale)
+    if rpe1d is not None:
+        p.bias_mode, p.rpe_radius, p.rpe1d = _lib.BIAS_RPE1D, int(radius), rpe1d.data_ptr()
+    p.q, p.k_cache, p.v_cache, p.o = q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr()
+    for name, t in (("q", q), ("o", o), ("k_cache", k_cache), ("v_cache", v_cache)):
+        getattr(p, name + "_stride")[:] = t.stride()[:3]
+    if k is not None:
+        p.k_new, p.v_new = k.data_ptr(), v.data_ptr()
+        p.k_new_stride[:] = k.stride()[:3]
+        p.v_new_stride[:] = v.stride()[:3]
+    p.lse = lse.data_ptr() if lse is not None else None
+    p.num_splits = int(num_splits)
+    return p
+
+
+MAX_CHUNK = 1024  # (CHUNK_MAX_M, csrc/decode_chunk_kernels.h)
+
+
+def _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius):
+    """everything the host can check without touching a device"""
+    what = "flash_attn_with_kvcache_chunk"
+    if q.dim() != 4 or not 1 <= q.shape[1] <= MAX_CHUNK:
+        raise ValueError(f"{what}: q must be (B, M, H, D) with 1 <= M <= {MAX_CHUNK}, got {tuple(q.shape)}")
+    B, M, H, D = q.shape
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dim() != 4 or t.shape[0] != B or t.shape[2] != H or t.shape[3] != D:
+            raise ValueError(f"{what}: {name} must be (B, L_cap, H, D) = ({B}, L_cap, {H}, {D}), got {tuple(t.shape)}")
+    if k_cache.shape[1] != v_cache.shape[1]:
+        raise ValueError(f"{what}: k_cache and v_cache have different capacities")
+    if (k is None) != (v is None):
+        raise ValueError(f"{what}: pass both k and v, or neither")
+    if k is not None:
+        for name, t in (("k", k), ("v", v)):
+            if tuple(t.shape) != (B, M, H, D):
+                raise ValueError(f"{what}: {name} must be ({B}, {M}, {H}, {D}), got {tuple(t.shape)}")
+        if cache_seqlens is None:
+            raise ValueError(f"{what}: appending k / v needs cache_seqlens")
+    for t in [q, k_cache, v_cache] + ([k, v] if k is not None else []):
+        if t.dtype != q.dtype:
+            raise ValueError(f"{what}: dtype mismatch ({t.dtype} vs q {q.dtype})")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{what}: dtype {q.dtype} (fp16 or bf16)")
+    if D not in (64, 128):
+        raise ValueError(f"{what}: head_dim {D} (64 or 128)")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not _lib.kernel_ready(t):
+            raise ValueError(f"{what}: {name} needs innermost stride 1, a 16-byte aligned base and strides that are multiples of 8 "
+                             "elements (it is written in place, so it cannot be copied)")
+    if cache_seqlens is not None and (cache_seqlens.dim() != 1 or cache_seqlens.numel() != B):
+        raise ValueError(f"{what}: cache_seqlens must hold {B} lengths, got shape {tuple(cache_seqlens.shape)}")
+    if rpe1d is not None:
+        if not 1 <= int(radius) <= 2048:
+            raise ValueError(f"{what}: rpe_radius {radius} outside 1..2048")
+        if rpe1d.dtype != torch.float32 or tuple(rpe1d.shape) != (H, 2 * int(radius) + 1) or not rpe1d.is_contiguous():
+            raise ValueError(f"{what}: rpe1d must be a contiguous fp32 ({H}, 2 * rpe_radius + 1) = ({H}, {2 * int(radius) + 1}) tensor, "
+                             f"got {rpe1d.dtype} {tuple(rpe1d.shape)}")
+
+
+def _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d):
+    for t in (q, k_cache, v_cache, k, v, rpe1d):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise ValueError("flash_attn_with_kvcache_chunk: tensors must be on the GPU (there is no CPU path)")
+        if t.device != q.device:
+            raise ValueError("flash_attn_with_kvcache_chunk: tensors on different devices")
+
+
+@torch.library.custom_op("fat5::attn_decode_chunk", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def attn_decode_chunk(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor],
+                      v: Optional[torch.Tensor], cache_seqlens: Optional[torch.Tensor], sm_scale: float, causal: bool,
+                      rpe1d: Optional[torch.Tensor], rpe_radius: int, return_lse: bool, num_splits: int) -> List[torch.Tensor]:
+    """[o (B, M, H, D) contiguous, lse (B, H, M) fp32 (empty (0,) when return_lse is False)]; appends k / v to the caches"""
+    _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius)
+    _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d)
+    if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or cache_seqlens.device != q.device or
+                                      not cache_seqlens.is_contiguous()):
+        raise ValueError(f"fat5::attn_decode_chunk: cache_seqlens must be a contiguous int32 tensor on {q.device}")
+    q, k, v = _ready(q), _ready(k), _ready(v)
+    B, M, H, D = q.shape
+    o = torch.empty((B, M, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, M), dtype=torch.float32, device=q.device) if return_lse else q.new_empty((0,), dtype=torch.float32)
+    p = _chunk_params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse if return_lse else None, sm_scale, causal, rpe1d, rpe_radius,
+                      num_splits)
+    lib = _lib.load()
+    ws = None
+    need = lib.fat5_attn_decode_chunk_workspace_bytes(p)
+    if need:
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        p.workspace, p.workspace_bytes = ws.data_ptr(), need
+    with _lib.on_device(q.device):
+        _lib.check(lib.fat5_attn_decode_chunk(p, _lib.stream_ptr(q.device)), "fat5_attn_decode_chunk")
+    return [o, lse]
+
+
+@attn_decode_chunk.register_fake
+def _attn_decode_chunk_fake(q, k_cache, v_cache, k, v, cache_seqlens, sm_scale, causal, rpe1d, rpe_radius, return_lse, num_splits):
+    B, M, H, D = q.shape
+    o = q.new_empty((B, M, H, D))
+    lse = q.new_empty((B, H, M), dtype=torch.float32) if return_lse else q.new_empty((0,), dtype=torch.float32)
+    return [o, lse]
+
+
+def flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, softmax_scale=None, causal=False, rpe1d=None,
+                                  rpe_radius=0, return_lse=False, num_splits=0):
+    """flash_attn's `flash_attn_with_kvcache` for M query rows: returns o (B, M, H, D), or (o, lse (B, H, M) fp32) with return_lse.
+
+    With k / v (B, M, H, D) the rows are written into the caches at cache_seqlens[b] .. cache_seqlens[b] + M - 1 inside the launch
+    and query row i sits at position cache_seqlens[b] + i; without them the rows are bottom-right aligned, row i at
+    L_b - M + i.  `causal=True`: row i sees the keys up to its own position.  The T5 bias is aligned per row:
+    rpe1d[h][clamp(j - p_i, -R, R) + R].  Rows that no longer fit into the caches are not appended and sit at the last key;
+    a row that sees no key gives o = 0, lse = -inf.  cache_seqlens is not incremented: the caller advances it by M.  An int
+    cache_seqlens broadcasts over the batch.  num_splits 0 lets the library pick the key-range split from B, H, M and the capacity
+    (never from the lengths: a captured graph stays valid while they grow)."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v, rpe1d)):
+        raise RuntimeError("flash_attn_with_kvcache_chunk is forward only: call it under torch.no_grad() / inference_mode(), or detach")
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32)
+    _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius)  # (before the device checks)
+    _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d)
+    lens = _as_seqlens(cache_seqlens, q.device)
+    scale = 1.0 / math.sqrt(q.shape[-1]) if softmax_scale is None else float(softmax_scale)
+    o, lse = attn_decode_chunk(q, k_cache, v_cache, k, v, lens, scale, bool(causal), rpe1d, int(rpe_radius), bool(return_lse),
+                               int(num_splits))
     return (o, lse) if return_lse else o

@@ -26,6 +26,10 @@ Logits processors (`repetition_penalty`, `no_repeat_ngram_size`, `min_length`, `
 launch between the decode step and the argmax / sampler / beam step (flasht5_amd/logits_process.py): it reads the running
 sequences (`labels`, `running_seqs`) and `cache_seqlens` on the device, so the step stays one graph.  With all of them at
 their defaults the launch is not made.
+
+Decoder prompts (`decoder_input_ids` (B, P)): the first P - 1 prompt tokens go through the decoder in ONE chunk step
+(`decode_chunk`: M tokens per row, M key / value rows appended per layer by the chunk decode kernel, causal inside the chunk), the
+loop then starts from the prompt's last token.  `decode_chunk` is also the verification step of speculative decoding.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -70,19 +74,19 @@ def _check_supported(model):
 
 
 @torch.no_grad()
-def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1):
+def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1, prompt_length=1):
     """Run the encoder, project every decoder layer's cross-attention K / V once and allocate self-attention caches of capacity
-    `max_length + 1`.  `attention_mask` is accepted and not applied, as the reference does with use_masking=False.
+    `max_length + prompt_length` (a decoder prompt of `prompt_length` tokens, the start token included, then max_length new ones).  `attention_mask` is accepted and not applied, as the reference does with use_masking=False.
     num_beams > 1: the encoder and the cross K / V stay at B rows; the self-attention caches, the lengths and the history table
     get B * num_beams rows (row b * k + j: beam j of input b)."""
     _check_supported(model)
     first = model.decoder.block[0].self_attention_layer.self_attention
-    cap = int(max_length) + 1
+    cap = int(max_length) + int(prompt_length)
     if first.rotary and cap > first.pe_encoding.max_sequence_length:
         # (step t reads row t of the rotary tables; the full forward refuses positions past them the same way)
         raise ValueError(f"max_length {max_length}: the cache of {cap} positions exceeds the rotary tables' "
                          f"{first.pe_encoding.max_sequence_length} rows (max_sequence_length); use max_length <= "
-                         f"{first.pe_encoding.max_sequence_length - 1}")
+                         f"{first.pe_encoding.max_sequence_length - int(prompt_length)}")
     B = input_ids.shape[0]
     Bk = B * int(num_beams)
     enc = model.encoder(input_ids)
@@ -129,6 +133,64 @@ def decode_step(model, state, token_ids):
     h = model.decoder.final_layer_norm(h)
     state.cache_seqlens.add_(1)
     return model.lm_head(h)[:, 0]
+
+
+@torch.no_grad()
+def decode_chunk(model, state, token_ids, logits="all"):
+    """M tokens per batch row (B, M) through the decoder against the caches in one step: every self-attention layer appends its M
+    key / value rows with the chunk decode kernel (causal inside the chunk, row i at position cache_seqlens + i), and
+    cache_seqlens advances by M on the device.  Returns the logits of all M next positions (B, M, vocab) for logits="all", of the
+    last one (B, vocab) for "last" (the final norm and lm_head run on that row only), or None for "none" (both are skipped: a
+    prefill that only fills the caches)."""
+    if logits not in ("all", "last", "none"):
+        raise ValueError(f"decode_chunk: logits {logits!r} ('all', 'last' or 'none')")
+    B = state.cache_seqlens.shape[0]
+    if token_ids.dim() != 2 or token_ids.shape[0] != B or token_ids.shape[1] < 1:
+        raise ValueError(f"decode_chunk: token_ids must be (B, M) = ({B}, M >= 1), got {tuple(token_ids.shape)}")
+    if state.row_batch is not None or state.cross_batch_idx is not None:
+        raise ValueError("decode_chunk: a beam-search state takes one token per step (the cache maps are per row)")
+    M = token_ids.shape[1]
+    if state.steps + M > state.capacity:
+        raise ValueError(f"decode_chunk: the caches hold {state.capacity} positions, {state.steps} are used and the chunk brings {M} "
+                         "(init_decode_state with a larger max_length or prompt_length)")
+    state.steps += M
+    h = _embed(model, token_ids)
+    pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
+    for i, blk in enumerate(model.decoder.block):
+        sa = blk.self_attention_layer
+        h = h + sa.self_attention.forward_decode(sa.layer_norm(h), state.self_k[i], state.self_v[i], state.cache_seqlens,
+                                                 position_bias=state.position_bias, position=pos)
+        ca = blk.cross_attention_layer
+        h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos)
+        h = blk.ff_layer(h)
+    state.cache_seqlens.add_(M)
+    if logits == "none":
+        return None
+    if logits == "last":
+        return model.lm_head(model.decoder.final_layer_norm(h[:, -1:]))[:, 0]
+    return model.lm_head(model.decoder.final_layer_norm(h))
+
+
+def _check_prompt(model, input_ids, decoder_input_ids, num_beams):
+    """host-side validation of a decoder prompt -> its length P (1 without one)"""
+    if decoder_input_ids is None:
+        return 1
+    if num_beams > 1:
+        raise ValueError("generate: decoder_input_ids with num_beams > 1 is not supported (beam search starts from the start token)")
+    p = decoder_input_ids
+    if not torch.is_tensor(p) or p.dtype != torch.int64 or p.dim() != 2 or p.shape[1] < 1:
+        raise ValueError("generate: decoder_input_ids must be a (B, P) int64 tensor with P >= 1 (the start token included), got "
+                         f"{tuple(p.shape) if torch.is_tensor(p) else type(p).__name__}"
+                         f"{' ' + str(p.dtype) if torch.is_tensor(p) else ''}")
+    if p.shape[0] != input_ids.shape[0]:
+        raise ValueError(f"generate: decoder_input_ids holds {p.shape[0]} rows, input_ids {input_ids.shape[0]}")
+    V = model.lm_head.weight.shape[0]
+    lo, hi = int(p.min()), int(p.max())
+    if lo < 0 or hi >= V:
+        raise ValueError(f"generate: decoder_input_ids holds ids outside the vocabulary [0, {V}) (min {lo}, max {hi})")
+    if bool((p == 1).any()):
+        raise ValueError("generate: decoder_input_ids holds the EOS id 1 (a finished row cannot be continued)")
+    return int(p.shape[1])
 
 
 def _processed(logits, sequences, lengths, proc, log_softmax=False):
@@ -225,7 +287,8 @@ def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, le
 @torch.no_grad()
 def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, *, do_sample=False, temperature=1.0, top_k=50,
              top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
-             return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None):
+             return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None,
+             decoder_input_ids=None):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -252,10 +315,19 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     processed row, sampling hands it to `sample_logits` (processors before warpers), beam search processes log_softmax(logits)
     and does not renormalise.  They are checked on the host before the encoder runs; with every one at its default no launch
     is added and the step is the code path above.  The sequence buffer of a call with processors holds at most 4096 columns
-    (max_length <= 4095)."""
+    (max_length <= 4095).
+
+    `decoder_input_ids` (B, P) int64, P >= 1: a decoder prompt as HF takes it, the start token included (None is [[0]]).  Up to
+    max_length new tokens follow it; the result is (B, P + steps): the prompt, then the new tokens, with the same ending.  The
+    first P - 1 prompt tokens fill the caches in one `decode_chunk` step (eagerly, also with graph=True; none with P = 1), then
+    the loop above runs from the prompt's last token.  Greedy decoding, sampling and the logits processors work with it; the
+    processors see the prompt, as HF's do, and their 4096-column limit and the rotary tables' limit count it.  The prompt is
+    checked on the host before the encoder runs: its shape and batch, ids inside the vocabulary, no EOS id 1; with
+    num_beams > 1 it is rejected."""
     from .beam import check_args as check_beam_args
     check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample)
-    proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens)
+    P = _check_prompt(model, input_ids, decoder_input_ids, num_beams)
+    proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, P)
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
                               early_stopping, return_scores, proc)
@@ -275,10 +347,16 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
             _sample_step(model, state, tok, labels, seen_eos, sampling, proc)
     B = input_ids.shape[0]
     dev = input_ids.device
-    state = init_decode_state(model, input_ids, max_length, attention_mask)
+    state = init_decode_state(model, input_ids, max_length, attention_mask, prompt_length=P)
     labels = torch.zeros((B, state.capacity), dtype=torch.long, device=dev)
     tok = torch.zeros((B,), dtype=torch.long, device=dev)
     seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)
+    if decoder_input_ids is not None:
+        prompt = decoder_input_ids.to(dev)
+        labels[:, :P] = prompt
+        tok.copy_(prompt[:, P - 1])
+        if P > 1:
+            decode_chunk(model, state, prompt[:, :P - 1], logits="none")
     steps = 0
     g = None
     try:
@@ -294,18 +372,18 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
                 g = _capture(model, state, tok, labels, seen_eos, step)
     finally:
         del g
-    return finish_labels(labels[:, :steps + 1])
+    return finish_labels(labels[:, :steps + P])
 
 
-def _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens):
+def _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompt_length=1):
     """host-side validation of the logits processors -> None when all of them are off, else process_logits' keyword arguments"""
     from .logits_process import MAX_SEQ_LEN, active, check_args
     check_args(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, model.lm_head.weight.shape[0])
     if not active(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens):
         return None
-    if int(max_length) + 1 > MAX_SEQ_LEN:
+    if int(max_length) + int(prompt_length) > MAX_SEQ_LEN:
         raise ValueError(f"max_length {max_length}: the logits processors hold at most {MAX_SEQ_LEN} sequence columns "
-                         f"(max_length <= {MAX_SEQ_LEN - 1})")
+                         f"(max_length <= {MAX_SEQ_LEN - int(prompt_length)})")
     return dict(repetition_penalty=float(repetition_penalty), no_repeat_ngram_size=int(no_repeat_ngram_size),
                 min_length=int(min_length), eos_token_id=1, suppress_tokens=suppress_tokens)
 

@@ -408,6 +408,65 @@ size_t fat5_attn_decode_workspace_bytes(const fat5_decode_params* p);
 int fat5_attn_decode(const fat5_decode_params* p, void* hip_stream);
 
 /*
+ * Chunked decode attention: M query rows per (batch, head) against a KV cache, their M key / value rows appended in the same launch
+ * (decode_chunk_kernels.h).  flash_attn's `flash_attn_with_kvcache` at seqlen_q = M: prompt prefill, speculative-decoding
+ * verification, and cross-attention of M decoder rows against the encoder's K / V.  The reference has no cached decoding.
+ *   o[b,i,h] = softmax(q[b,i,h] . K[b,h,visible_i]^T * sm_scale + bias_i) . V[b,h,visible_i],  fp32 accumulation;
+ *   lse[b,h,i] (optional) natural-log LSE, fp32, (B, H, M) contiguous.
+ * Inputs: q, o (B, M, H, D) views with element strides [b, m, h]; k_new / v_new the same shape, or both NULL; the caches
+ * (B, capacity, H, D) views with strides [b, l, h]; D in {64, 128}; FAT5_F16 / FAT5_BF16; 1 <= M <= 1024.  Innermost stride 1, every
+ * base 16-byte aligned, every stride a multiple of 8 elements.
+ *   Lengths.     len_b = clamp(cache_seqlens[b], 0, capacity), or N for every b when cache_seqlens is NULL.
+ *   Append.      With k_new / v_new (needs cache_seqlens), a_b = min(M, capacity - len_b) rows are written at rows
+ *                len_b .. len_b + a_b - 1 and L_b = len_b + a_b.  Without them L_b = len_b.
+ *   Positions.   With an append p_i = min(len_b + i, L_b - 1): fat5_attn_decode's rule per row; a row that no longer fits is not
+ *                appended and sits at the last key.  Without one p_i = L_b - M + i (flash_attn's bottom-right alignment; it may be
+ *                negative).
+ *   Visibility.  With `causal`, key j is seen iff j < L_b and j <= p_i; without it iff j < L_b.  A row that sees no key gives
+ *                o = 0 and lse = -inf.
+ *   Bias.        FAT5_BIAS_NONE, or FAT5_BIAS_RPE1D: bias_i[j] = rpe1d[h][clamp(j - p_i, -R, R) + R].
+ *   Safety.      A new row is always read from k_new / v_new, never from the cache, so no workgroup depends on another's store;
+ *                each new row is written to the cache by exactly one workgroup; no row at or beyond L_b is read; nothing outside
+ *                rows [0, capacity) is read or written, whatever cache_seqlens holds; cache_seqlens is never written.
+ * The grid, the split count and the workspace size depend on B, H, M, capacity and num_splits only, so a captured graph stays valid
+ * while the lengths grow.  All merges run in a fixed order without float atomics: results are bitwise identical run to run.
+ * M = 1 means what fat5_attn_decode means.  There are no cache maps here (cache_batch_idx / cache_row_batch).
+ * Rejected with FAT5_EINVAL before anything is launched: D outside {64, 128}, dtype outside {FAT5_F16, FAT5_BF16}, B / H out of range,
+ * M outside [1, 1024], a negative capacity, N outside [0, capacity] without lengths, num_splits outside [0, 128], a radius outside
+ * 1..2048 or a NULL rpe1d with RPE1D, exactly one of k_new / v_new, an append without cache_seqlens, a non-finite sm_scale,
+ * NULL / misaligned pointers or strides; FAT5_EWORKSPACE when the workspace is missing, misaligned or smaller than
+ * fat5_attn_decode_chunk_workspace_bytes().
+ */
+typedef struct fat5_decode_chunk_params {
+  int32_t B, H, M, D;         /* M query rows per (b, h), 1..1024; D in {64, 128} */
+  int32_t dtype;              /* FAT5_F16 | FAT5_BF16: q, caches, k_new, v_new, o */
+  int32_t capacity;           /* cache rows per (b, h) */
+  int32_t N;                  /* key count of every batch element when cache_seqlens is NULL (0..capacity) */
+  int32_t causal;             /* 0 | 1 */
+  const int32_t* cache_seqlens; /* (B,) int32 device array, or NULL */
+  float sm_scale;
+  int32_t bias_mode;          /* FAT5_BIAS_NONE | FAT5_BIAS_RPE1D */
+  int32_t rpe_radius;         /* R, 1..2048 with RPE1D */
+  const float* rpe1d;         /* (H, 2R + 1) fp32 contiguous */
+  const void* q;              /* (B, M, H, D): q_stride [b, m, h] */
+  void* k_cache;              /* (B, capacity, H, D): k_cache_stride [b, l, h] */
+  void* v_cache;
+  const void* k_new;          /* (B, M, H, D) or NULL (then v_new NULL too) */
+  const void* v_new;
+  void* o;                    /* (B, M, H, D) */
+  float* lse;                 /* (B, H, M) contiguous fp32, or NULL */
+  int64_t q_stride[3], k_cache_stride[3], v_cache_stride[3], k_new_stride[3], v_new_stride[3], o_stride[3];
+  int32_t num_splits;         /* key-range splits per tile of query rows, 1..128; 0 = the library's choice from B, H, M, capacity */
+  void* workspace;            /* fat5_attn_decode_chunk_workspace_bytes(); 16-byte aligned; may be NULL when that is 0 */
+  size_t workspace_bytes;
+} fat5_decode_chunk_params;
+/* sizeof(fat5_decode_chunk_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_decode_chunk_params(void);
+/* workspace fat5_attn_decode_chunk needs for these host-known arguments (bytes; 0 when one split is used) */
+size_t fat5_attn_decode_chunk_workspace_bytes(const fat5_decode_chunk_params* p);
+int fat5_attn_decode_chunk(const fat5_decode_chunk_params* p, void* hip_stream);
+
+/*
  * Temperature / top-k / top-p sampling: one token per logits row in one launch (sample_kernels.h), HF's warper order
  * (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper, then a draw).  The reference's generate has no sampling.
  *   x_j = float(logits[b, j]) / temperature (an fp32 division);
