@@ -136,6 +136,19 @@ class LogitsParams(ctypes.Structure):
     ]
 
 
+class SpecParams(ctypes.Structure):
+    """Mirror of `fat5_spec_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("M", ctypes.c_int32), ("V", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("logits", ctypes.c_void_p), ("batch_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64),
+        ("draft", ctypes.c_void_p), ("draft_stride", ctypes.c_int64), ("cache_seqlens", ctypes.c_void_p),
+        ("draft_seqlens", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("labels_stride", ctypes.c_int64),
+        ("ncols", ctypes.c_int32), ("eos_token_id", ctypes.c_int32), ("tok", ctypes.c_void_p), ("seen_eos", ctypes.c_void_p),
+        ("limit", ctypes.c_void_p), ("limit_scalar", ctypes.c_int32), ("n_accepted", ctypes.c_void_p), ("n_new", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 EXPORTS = (
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
@@ -149,6 +162,7 @@ EXPORTS = (
     "fat5_sample_logits", "fat5_sizeof_sample_params",
     "fat5_beam_step", "fat5_beam_step_workspace_bytes", "fat5_sizeof_beam_params",
     "fat5_process_logits", "fat5_sizeof_logits_params",
+    "fat5_spec_accept", "fat5_spec_accept_workspace_bytes", "fat5_sizeof_spec_params",
 )
 
 _lib = None
@@ -272,6 +286,14 @@ def load():
     if lib.fat5_sizeof_logits_params() != ctypes.sizeof(LogitsParams):
         raise ImportError(f"fat5_logits_params layout mismatch: library {lib.fat5_sizeof_logits_params()} B, "
                           f"binding {ctypes.sizeof(LogitsParams)} B")
+    lib.fat5_spec_accept.restype = ctypes.c_int
+    lib.fat5_spec_accept.argtypes = [ctypes.POINTER(SpecParams), ctypes.c_void_p]
+    lib.fat5_spec_accept_workspace_bytes.restype = ctypes.c_size_t
+    lib.fat5_spec_accept_workspace_bytes.argtypes = [ctypes.POINTER(SpecParams)]
+    lib.fat5_sizeof_spec_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_spec_params() != ctypes.sizeof(SpecParams):
+        raise ImportError(f"fat5_spec_params layout mismatch: library {lib.fat5_sizeof_spec_params()} B, "
+                          f"binding {ctypes.sizeof(SpecParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

@@ -24,6 +24,7 @@
 #include "sample_kernels.h"
 #include "beam_kernels.h"
 #include "logits_kernels.h"
+#include "spec_kernels.h"
 
 using namespace fat5;
 
@@ -1390,6 +1391,78 @@ int fat5_process_logits(const fat5_logits_params* p, void* stream_) {
   else hipLaunchKernelGGL((process_logits_kernel<FAT5_BF16>), grid, dim3(LOGITS_THREADS), 0, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "process_logits launch");
+  return FAT5_OK;
+}
+
+// ---- draft verification of speculative greedy decoding (spec_kernels.h) ----
+size_t fat5_sizeof_spec_params(void) { return sizeof(fat5_spec_params); }
+
+static bool spec_shape_ok(const fat5_spec_params* p) {
+  return p->B >= 0 && p->B <= 65535 && p->M >= 2 && p->M <= SPEC_MAX_M && p->V >= 1 && p->V <= SPEC_MAX_V;
+}
+static int spec_slices(const fat5_spec_params* p) { return (p->V + SPEC_SLICE - 1) / SPEC_SLICE; }
+
+size_t fat5_spec_accept_workspace_bytes(const fat5_spec_params* p) {
+  if (!p || !spec_shape_ok(p)) return 0;
+  return align_up((size_t)p->B * p->M * spec_slices(p) * sizeof(uint64_t), 16);
+}
+
+int fat5_spec_accept(const fat5_spec_params* p, void* stream_) {
+  const char* what = "spec_accept";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (p->B < 0 || p->B > 65535) return fail(FAT5_EINVAL, "%s: B %d outside [0, 65535]", what, p->B);
+  if (p->M < 2 || p->M > SPEC_MAX_M) return fail(FAT5_EINVAL, "%s: M %d outside [2, %d] (gamma + 1)", what, p->M, SPEC_MAX_M);
+  if (p->V < 1 || p->V > SPEC_MAX_V) return fail(FAT5_EINVAL, "%s: V %d outside [1, %d]", what, p->V, SPEC_MAX_V);
+  if (p->dtype != FAT5_F32 && p->dtype != FAT5_F16 && p->dtype != FAT5_BF16) return fail(FAT5_EINVAL, "%s: dtype %d", what, p->dtype);
+  if (p->row_stride < p->V) return fail(FAT5_EINVAL, "%s: row_stride %lld < V %d", what, (long long)p->row_stride, p->V);
+  if (p->B > 1 && p->batch_stride < (int64_t)(p->M - 1) * p->row_stride + p->V)
+    return fail(FAT5_EINVAL, "%s: batch_stride %lld: the rows of two batch elements overlap", what, (long long)p->batch_stride);
+  if (p->draft_stride < p->M - 1) return fail(FAT5_EINVAL, "%s: draft_stride %lld < gamma %d", what, (long long)p->draft_stride, p->M - 1);
+  if (p->ncols < 2) return fail(FAT5_EINVAL, "%s: ncols %d (>= 2)", what, p->ncols);
+  if (p->labels_stride < p->ncols) return fail(FAT5_EINVAL, "%s: labels_stride %lld < ncols %d", what, (long long)p->labels_stride, p->ncols);
+  if (p->eos_token_id < 0) return fail(FAT5_EINVAL, "%s: eos_token_id %d (>= 0)", what, p->eos_token_id);
+  const size_t es = p->dtype == FAT5_F32 ? 4 : 2;
+  struct { const void* ptr; size_t al; const char* name; bool need; } t[] = {
+      {p->logits, es, "logits", true}, {p->draft, 8, "draft", true}, {p->cache_seqlens, 4, "cache_seqlens", true},
+      {p->labels, 8, "labels", true}, {p->tok, 8, "tok", true}, {p->seen_eos, 1, "seen_eos", true},
+      {p->draft_seqlens, 4, "draft_seqlens", false}, {p->limit, 4, "limit", false}, {p->n_accepted, 4, "n_accepted", false},
+      {p->n_new, 4, "n_new", false}};
+  for (const auto& e : t)
+    if ((e.need && !e.ptr) || (reinterpret_cast<uintptr_t>(e.ptr) % e.al))
+      return fail(FAT5_EINVAL, "%s: %s: %smisaligned pointer", what, e.name, e.need ? "null or " : "");
+  if (p->B == 0) return FAT5_OK;
+  const size_t need = fat5_spec_accept_workspace_bytes(p);
+  if (!p->workspace || !aligned16(p->workspace) || p->workspace_bytes < need)
+    return fail(FAT5_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", what, need, p->workspace_bytes);
+  SpecArgs a = {};
+  a.logits = p->logits;
+  a.bstride = p->B > 1 ? p->batch_stride : 0;
+  a.stride = p->row_stride;
+  a.draft = p->draft;
+  a.draft_stride = p->draft_stride;
+  a.cache_seqlens = p->cache_seqlens;
+  a.draft_seqlens = p->draft_seqlens;
+  a.labels = p->labels;
+  a.labels_stride = p->labels_stride;
+  a.tok = p->tok;
+  a.seen_eos = p->seen_eos;
+  a.limit = p->limit;
+  a.n_accepted = p->n_accepted;
+  a.n_new = p->n_new;
+  a.ws = static_cast<uint64_t*>(p->workspace);
+  a.B = p->B, a.M = p->M, a.V = p->V, a.ncols = p->ncols, a.slices = spec_slices(p), a.limit_scalar = p->limit_scalar;
+  a.eos = p->eos_token_id;
+  a.vec = aligned16(p->logits) && p->row_stride % 8 == 0 && (p->B == 1 || p->batch_stride % 8 == 0);
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 grid(p->B * p->M, a.slices);
+  if (p->dtype == FAT5_F32) hipLaunchKernelGGL((spec_argmax_kernel<FAT5_F32>), grid, dim3(SPEC_THREADS), 0, stream, a);
+  else if (p->dtype == FAT5_F16) hipLaunchKernelGGL((spec_argmax_kernel<FAT5_F16>), grid, dim3(SPEC_THREADS), 0, stream, a);
+  else hipLaunchKernelGGL((spec_argmax_kernel<FAT5_BF16>), grid, dim3(SPEC_THREADS), 0, stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "spec_accept argmax launch");
+  hipLaunchKernelGGL(spec_accept_kernel, dim3(p->B), dim3(64), 0, stream, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "spec_accept launch");
   return FAT5_OK;
 }
 

@@ -30,6 +30,10 @@ their defaults the launch is not made.
 Decoder prompts (`decoder_input_ids` (B, P)): the first P - 1 prompt tokens go through the decoder in ONE chunk step
 (`decode_chunk`: M tokens per row, M key / value rows appended per layer by the chunk decode kernel, causal inside the chunk), the
 loop then starts from the prompt's last token.  `decode_chunk` is also the verification step of speculative decoding.
+
+Speculative greedy decoding (`assistant_model`; flasht5_amd/speculative.py): a second, cheaper model drafts gamma
+tokens per round, one `decode_chunk` step of gamma + 1 rows checks them, and the verification kernel accepts, rolls the per-row
+lengths back and does the step's bookkeeping on the device.  Without an assistant none of it runs: the code path above is unchanged.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -288,7 +292,7 @@ def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, le
 def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, *, do_sample=False, temperature=1.0, top_k=50,
              top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
              return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None,
-             decoder_input_ids=None):
+             decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -323,11 +327,30 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     the loop above runs from the prompt's last token.  Greedy decoding, sampling and the logits processors work with it; the
     processors see the prompt, as HF's do, and their 4096-column limit and the rotary tables' limit count it.  The prompt is
     checked on the host before the encoder runs: its shape and batch, ids inside the vocabulary, no EOS id 1; with
-    num_beams > 1 it is rejected."""
+    num_beams > 1 it is rejected.
+
+    `assistant_model` (a second FAT5ForConditionalGeneration with the same vocabulary size; None: everything above, unchanged):
+    speculative greedy decoding (flasht5_amd/speculative.py).  The assistant runs its own encoder once on input_ids
+    and drafts `num_assistant_tokens` = gamma in [1, 15] tokens per round with gamma + 1 one-token steps; the model checks them in
+    one `decode_chunk` step of gamma + 1 rows, and the verification kernel keeps the agreeing prefix plus the model's own next
+    token and rolls both models' lengths back, per row, on the device.  One host read per round; graph=True captures one whole
+    round (both models, one stream) after the first eager round and replays it.  The result is what the call returns without an
+    assistant -- the drafts only decide how many model steps it takes -- up to the rounding of a chunk step against a one-row
+    step where two logits are within it.  decoder_input_ids works as above.  return_stats=True returns
+    (labels, {"rounds", "drafted", "accepted"}) with host ints: the rounds run, the tokens drafted for unfinished rows and how many
+    of them were accepted.  Rejected on the host before either encoder runs: do_sample=True, num_beams > 1, any active logits
+    processor, num_assistant_tokens outside [1, 15], a vocabulary mismatch, a model the decode path refuses, and RoPE models
+    with more than one batch row (rows advance raggedly; the decode path keeps one rotary position for the batch)."""
     from .beam import check_args as check_beam_args
     check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample)
     P = _check_prompt(model, input_ids, decoder_input_ids, num_beams)
     proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, P)
+    if assistant_model is not None:
+        from .speculative import check_generate_args, speculative_generate
+        check_generate_args(model, assistant_model, input_ids, max_length, num_assistant_tokens, P, do_sample, num_beams,
+                            proc is not None)
+        return speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, P,
+                                    decoder_input_ids, bool(return_stats))
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
                               early_stopping, return_scores, proc)

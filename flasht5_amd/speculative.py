@@ -1,0 +1,264 @@
+"""Speculative greedy decoding: a cheap drafter proposes gamma tokens per row, the target model checks all of them
+in ONE chunk step (`decode_chunk`, gamma + 1 rows), and the HIP verification kernel (`fat5_spec_accept`, csrc/spec_kernels.h)
+accepts the longest agreeing prefix plus the target's own next token, rolls the lengths back and does the bookkeeping of every
+row on the device.  The output is what greedy decoding without a drafter gives.
+
+    n_accepted, n_new = speculative_accept(logits, draft, cache_seqlens, labels, tok, seen_eos, limit, draft_seqlens=None)
+    n_accepted, n_new = speculative_round(model, state, tok, draft, labels, seen_eos, limit, draft_state=None)
+    labels = model.generate(input_ids, max_length=64, assistant_model=small, num_assistant_tokens=4, graph=True)
+
+The invariant at every round boundary, per row b with len_b = cache_seqlens[b]: the self-attention caches of both models hold the
+K / V of labels[b, :len_b], and tok[b] = labels[b, len_b] is pending (decided, not yet run through either decoder).  A round
+feeds [tok, d_0 .. d_{gamma-1}]; whatever n of the drafts the target agrees with, the first n + 1 rows the chunk appended are the
+K / V of tokens that stay, so the roll-back is the write of one length per row -- which is why `cache_seqlens` is per row: rows
+advance raggedly.  The model drafter runs gamma + 1 one-token steps (tok, then d_0 .. d_{gamma-1}; the last step's logits are not
+used), so its cache is valid for every n as well and its length vector takes the same value.
+
+Nothing here reads the host; `generate(graph=True)` captures one whole round (both models, one stream) and replays it.
+Forward only, no CPU path."""
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+
+MAX_ASSISTANT_TOKENS = 15  # (SPEC_MAX_M - 1, csrc/spec_kernels.h)
+MAX_V = 1 << 20
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def check_args(num_assistant_tokens=4, eos_token_id=1):
+    """host-side validation shared with `generate` (before any device work)"""
+    if not _is_int(num_assistant_tokens) or not 1 <= num_assistant_tokens <= MAX_ASSISTANT_TOKENS:
+        raise ValueError(f"num_assistant_tokens must be an int in [1, {MAX_ASSISTANT_TOKENS}], got {num_assistant_tokens!r}")
+    if not _is_int(eos_token_id) or eos_token_id < 0:
+        raise ValueError(f"eos_token_id must be an int >= 0, got {eos_token_id!r}")
+
+
+def _check_tensors(logits, draft, cache_seqlens, labels, tok, seen_eos, limit, draft_seqlens):
+    if not torch.is_tensor(logits) or logits.dim() != 3:
+        raise ValueError(f"speculative_accept: logits must be (B, gamma + 1, V), got {tuple(logits.shape) if torch.is_tensor(logits) else type(logits).__name__}")
+    B, M, V = logits.shape
+    if logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"speculative_accept: dtype {logits.dtype} (fp32, fp16 or bf16)")
+    if not 2 <= M <= MAX_ASSISTANT_TOKENS + 1:
+        raise ValueError(f"speculative_accept: logits holds {M} rows per batch element; gamma + 1 must be in [2, {MAX_ASSISTANT_TOKENS + 1}]")
+    if not 1 <= V <= MAX_V:
+        raise ValueError(f"speculative_accept: V {V} outside [1, {MAX_V}]")
+    if B > 65535:
+        raise ValueError(f"speculative_accept: B {B} (at most 65535)")
+    if draft.dim() != 2 or tuple(draft.shape) != (B, M - 1) or draft.dtype != torch.int64:
+        raise ValueError(f"speculative_accept: draft must be ({B}, {M - 1}) int64, got {draft.dtype} {tuple(draft.shape)}")
+    if draft.stride(1) != 1 and M - 1 > 1:
+        raise ValueError("speculative_accept: draft needs innermost stride 1")
+    for name, t in (("cache_seqlens", cache_seqlens), ("draft_seqlens", draft_seqlens)):
+        if t is not None and (t.dim() != 1 or t.shape[0] != B or t.dtype != torch.int32 or not t.is_contiguous()):
+            raise ValueError(f"speculative_accept: {name} must be a contiguous ({B},) int32 tensor, got {t.dtype} {tuple(t.shape)}")
+    if labels.dim() != 2 or labels.shape[0] != B or labels.dtype != torch.int64 or labels.shape[1] < 2:
+        raise ValueError(f"speculative_accept: labels must be ({B}, ncols >= 2) int64, got {labels.dtype} {tuple(labels.shape)}")
+    if labels.stride(1) != 1 or (B > 1 and labels.stride(0) < labels.shape[1]):
+        raise ValueError("speculative_accept: labels needs innermost stride 1 and non-overlapping rows")
+    if tok.dim() != 1 or tok.shape[0] != B or tok.dtype != torch.int64 or not tok.is_contiguous():
+        raise ValueError(f"speculative_accept: tok must be a contiguous ({B},) int64 tensor, got {tok.dtype} {tuple(tok.shape)}")
+    if seen_eos.dim() != 1 or seen_eos.shape[0] != B or seen_eos.dtype != torch.bool or not seen_eos.is_contiguous():
+        raise ValueError(f"speculative_accept: seen_eos must be a contiguous ({B},) bool tensor, got {seen_eos.dtype} {tuple(seen_eos.shape)}")
+    if torch.is_tensor(limit):
+        if limit.dim() != 1 or limit.shape[0] != B or limit.dtype != torch.int32 or not limit.is_contiguous():
+            raise ValueError(f"speculative_accept: limit must be an int or a contiguous ({B},) int32 tensor, got {limit.dtype} {tuple(limit.shape)}")
+    elif not _is_int(limit) or not -2 ** 31 <= limit < 2 ** 31:
+        raise ValueError(f"speculative_accept: limit must be an int or a ({B},) int32 tensor, got {limit!r}")
+
+
+def _check_devices(logits, draft, cache_seqlens, labels, tok, seen_eos, limit, draft_seqlens):
+    if not logits.is_cuda:
+        raise ValueError("speculative_accept: logits must be on the GPU (there is no CPU path)")
+    for name, t in (("draft", draft), ("cache_seqlens", cache_seqlens), ("labels", labels), ("tok", tok), ("seen_eos", seen_eos),
+                    ("limit", limit if torch.is_tensor(limit) else None), ("draft_seqlens", draft_seqlens)):
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"speculative_accept: {name} must be on {logits.device}, got {t.device}")
+
+
+@torch.library.custom_op("fat5::spec_accept", mutates_args=("cache_seqlens", "labels", "tok", "seen_eos", "draft_seqlens"),
+                         device_types="cuda")
+def spec_accept_op(logits: torch.Tensor, draft: torch.Tensor, cache_seqlens: torch.Tensor, labels: torch.Tensor, tok: torch.Tensor,
+                   seen_eos: torch.Tensor, limit: Optional[torch.Tensor], limit_scalar: int, draft_seqlens: Optional[torch.Tensor],
+                   eos_token_id: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(n_accepted, n_new), each (B,) int32; cache_seqlens, labels, tok, seen_eos and draft_seqlens are written in place
+    (include/fat5.h, fat5_spec_accept)"""
+    lim = limit if limit is not None else int(limit_scalar)
+    _check_tensors(logits, draft, cache_seqlens, labels, tok, seen_eos, lim, draft_seqlens)
+    _check_devices(logits, draft, cache_seqlens, labels, tok, seen_eos, lim, draft_seqlens)
+    check_args(logits.shape[1] - 1, eos_token_id)
+    B, M, V = logits.shape
+    if logits.stride(2) != 1 or logits.stride(1) < V or (B > 1 and logits.stride(0) < (M - 1) * logits.stride(1) + V):
+        logits = logits.contiguous()
+    dev = logits.device
+    n_accepted = torch.empty((B,), dtype=torch.int32, device=dev)
+    n_new = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B == 0:
+        return n_accepted, n_new
+    p = _lib.SpecParams()
+    p.B, p.M, p.V, p.dtype = B, M, V, _lib.dtype_code(logits.dtype)
+    p.logits, p.batch_stride, p.row_stride = logits.data_ptr(), logits.stride(0), logits.stride(1)
+    p.draft, p.draft_stride = draft.data_ptr(), draft.stride(0) if B > 1 else M - 1
+    p.cache_seqlens = cache_seqlens.data_ptr()
+    p.draft_seqlens = draft_seqlens.data_ptr() if draft_seqlens is not None else None
+    p.labels, p.labels_stride, p.ncols = labels.data_ptr(), labels.stride(0) if B > 1 else labels.shape[1], labels.shape[1]
+    p.eos_token_id = int(eos_token_id)
+    p.tok, p.seen_eos = tok.data_ptr(), seen_eos.data_ptr()
+    p.limit, p.limit_scalar = (limit.data_ptr(), 0) if limit is not None else (None, int(limit_scalar))
+    p.n_accepted, p.n_new = n_accepted.data_ptr(), n_new.data_ptr()
+    lib = _lib.load()
+    need = lib.fat5_spec_accept_workspace_bytes(p)
+    ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), need
+    with _lib.on_device(dev):
+        _lib.check(lib.fat5_spec_accept(p, _lib.stream_ptr(dev)), "fat5_spec_accept")
+    return n_accepted, n_new
+
+
+@spec_accept_op.register_fake
+def _spec_accept_fake(logits, draft, cache_seqlens, labels, tok, seen_eos, limit, limit_scalar, draft_seqlens, eos_token_id):
+    B = logits.shape[0]
+    return logits.new_empty((B,), dtype=torch.int32), logits.new_empty((B,), dtype=torch.int32)
+
+
+def speculative_accept(logits, draft, cache_seqlens, labels, tok, seen_eos, limit, draft_seqlens=None, eos_token_id=1):
+    """Verify one round for all B rows on the device (one call, two launches, nothing read back).
+
+    logits (B, gamma + 1, V) fp32 / bf16 / fp16: the target's logits of the chunk [tok, d_0 .. d_{gamma-1}]; draft (B, gamma) int64;
+    cache_seqlens (B,) int32, ALREADY advanced by gamma + 1 by the chunk step; labels (B, ncols) int64, tok (B,) int64 and seen_eos
+    (B,) bool: the running sequences, the pending tokens and the finished rows; limit: the last column of labels a row may write
+    (prompt length - 1 + max_length), an int or a (B,) int32 device tensor; draft_seqlens: the drafter's length vector, set to the
+    same value as cache_seqlens.  The rule per row is stated in include/fat5.h (fat5_spec_accept) and restated in tests/spec_ref.py.
+    Returns (n_accepted, n_new), both (B,) int32: the drafts that became output, and the tokens the row gained."""
+    check_args(logits.shape[1] - 1 if torch.is_tensor(logits) and logits.dim() == 3 else 1, eos_token_id)
+    _check_tensors(logits, draft, cache_seqlens, labels, tok, seen_eos, limit, draft_seqlens)
+    _check_devices(logits, draft, cache_seqlens, labels, tok, seen_eos, limit, draft_seqlens)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        logits = logits.detach()
+    lim_t, lim_s = (limit, 0) if torch.is_tensor(limit) else (None, int(limit))
+    return spec_accept_op(logits, draft, cache_seqlens, labels, tok, seen_eos, lim_t, lim_s, draft_seqlens, int(eos_token_id))
+
+
+@torch.no_grad()
+def speculative_round(model, state, tok, draft, labels, seen_eos, limit, draft_state=None):
+    """One verification round: `decode_chunk(model, state, cat(tok, draft), logits="all")`, then `speculative_accept`.  `draft`
+    (B, gamma) int64 may come from anywhere (a model drafter, a script, an n-gram table); `draft_state` is the model drafter's
+    DecodeState, whose lengths are rolled back with the target's.  The caches need room for limit + gamma + 1 positions.
+    Returns (n_accepted, n_new)."""
+    from .generation import decode_chunk
+    # the rows' lengths live on the device and roll back every round: the host-side count of appended positions does not bound
+    # this path (the kernel never moves a row past `limit`, and the chunk kernel drops rows past the capacity)
+    state.steps = 0
+    logits = decode_chunk(model, state, torch.cat((tok.unsqueeze(1), draft), 1), logits="all")
+    return speculative_accept(logits, draft, state.cache_seqlens, labels, tok, seen_eos, limit,
+                              draft_seqlens=None if draft_state is None else draft_state.cache_seqlens)
+
+
+@torch.no_grad()
+def draft_tokens(assistant, draft_state, tok, draft):
+    """the model drafter: gamma + 1 one-token steps from `tok`, the greedy tokens of the first gamma written to `draft` (B, gamma)
+    in place; the last step only appends d_{gamma-1}'s K / V, so that the cache is valid when every draft is accepted"""
+    from .generation import decode_step
+    gamma = draft.shape[1]
+    t = tok
+    for i in range(gamma + 1):
+        draft_state.steps = 0  # (as in speculative_round)
+        lg = decode_step(assistant, draft_state, t)
+        if i < gamma:
+            t = draft[:, i]
+            t.copy_(lg.argmax(-1))
+
+
+def check_generate_args(model, assistant_model, input_ids, max_length, num_assistant_tokens, prompt_length, do_sample, num_beams,
+                        processors_active):
+    """`generate(assistant_model=...)`'s host-side rejections, before either encoder runs"""
+    from .generation import _check_supported
+    what = "generate: assistant_model (speculative decoding)"
+    if do_sample:
+        raise ValueError(f"{what} with do_sample=True is not supported: the verification is greedy (argmax against argmax)")
+    if num_beams > 1:
+        raise ValueError(f"{what} with num_beams > 1 is not supported")
+    if processors_active:
+        raise ValueError(f"{what} with logits processors (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens) "
+                         "is not supported: the chunk's rows would each need the sequence up to their own position")
+    check_args(num_assistant_tokens)
+    for m in (model, assistant_model):
+        if not all(hasattr(m, a) for a in ("encoder", "decoder", "shared", "lm_head")):
+            raise ValueError(f"{what} must be a FAT5ForConditionalGeneration, got {type(m).__name__}")
+    V, Va = model.lm_head.weight.shape[0], assistant_model.lm_head.weight.shape[0]
+    if V != Va:
+        raise ValueError(f"{what}: vocabulary mismatch, the model has {V} ids and the assistant {Va}")
+    _check_supported(model)
+    _check_supported(assistant_model)
+    cap = int(prompt_length) + int(max_length) + int(num_assistant_tokens) + 1
+    for name, m in (("the model", model), ("the assistant", assistant_model)):
+        first = m.decoder.block[0].self_attention_layer.self_attention
+        if not first.rotary:
+            continue
+        if input_ids.shape[0] > 1:
+            raise ValueError(f"{what}: {name} uses RoPE and the batch holds {input_ids.shape[0]} rows; rows advance raggedly and the "
+                             "decode path keeps one rotary position for the batch (B = 1 only)")
+        if cap > first.pe_encoding.max_sequence_length:
+            raise ValueError(f"{what}: the cache of {cap} positions (prompt + max_length + num_assistant_tokens + 1) exceeds the "
+                             f"rotary tables' {first.pe_encoding.max_sequence_length} rows of {name}")
+
+
+@torch.no_grad()
+def speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, prompt_length,
+                         decoder_input_ids, return_stats):
+    """`generate`'s speculative loop (the arguments are checked already): per round gamma + 1 draft steps, one chunk step of the
+    target and the verification kernel, then ONE host read (`seen_eos.all()`), as the plain loop does once per token"""
+    from .generation import _capture_call, decode_chunk, finish_labels, init_decode_state
+    gamma, P, T_max = int(num_assistant_tokens), int(prompt_length), int(max_length)
+    B, dev = input_ids.shape[0], input_ids.device
+    # capacity P + max_length + gamma + 1: a row at its last free column still appends a whole chunk before the roll-back
+    state = init_decode_state(model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P)
+    dstate = init_decode_state(assistant_model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P)
+    labels = torch.zeros((B, P + T_max), dtype=torch.long, device=dev)
+    limit = P - 1 + T_max
+    tok = torch.zeros((B,), dtype=torch.long, device=dev)
+    seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)
+    draft = torch.zeros((B, gamma), dtype=torch.long, device=dev)
+    stats = torch.zeros((2,), dtype=torch.long, device=dev) if return_stats else None  # (live rows, accepted drafts)
+    if decoder_input_ids is not None:
+        prompt = decoder_input_ids.to(dev)
+        labels[:, :P] = prompt
+        tok.copy_(prompt[:, P - 1])
+        if P > 1:
+            decode_chunk(model, state, prompt[:, :P - 1], logits="none")
+            decode_chunk(assistant_model, dstate, prompt[:, :P - 1], logits="none")
+
+    def one_round():
+        if stats is not None:
+            stats[0].add_((~seen_eos).sum())
+        draft_tokens(assistant_model, dstate, tok, draft)
+        n_acc, _ = speculative_round(model, state, tok, draft, labels, seen_eos, limit, draft_state=dstate)
+        if stats is not None:
+            stats[1].add_(n_acc.sum())
+
+    rounds = 0
+    g = None
+    try:
+        for _ in range(T_max):  # (every live row gains at least one token per round)
+            if g is not None:
+                g.replay()
+            else:
+                one_round()
+            rounds += 1
+            if bool(seen_eos.all()):
+                break
+            if graph and g is None and rounds < T_max:
+                g = _capture_call(one_round)
+    finally:
+        del g
+    T = int(state.cache_seqlens.max()) - (P - 1)  # the most new tokens any row produced
+    out = finish_labels(labels[:, :P + T])
+    if return_stats:
+        live, acc = stats.tolist()
+        return out, dict(rounds=rounds, drafted=live * gamma, accepted=acc)
+    return out

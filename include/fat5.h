@@ -620,6 +620,59 @@ size_t fat5_sizeof_logits_params(void);
 int fat5_process_logits(const fat5_logits_params* p, void* hip_stream);
 
 /*
+ * Draft verification of speculative greedy decoding: one round for all B rows on the device (spec_kernels.h).
+ * The target model has run the chunk [tok, d_0 .. d_{gamma-1}] (M = gamma + 1 rows) through fat5_attn_decode_chunk, so
+ * cache_seqlens is ALREADY advanced by M: old_len = cache_seqlens[b] - M.  logits[b, i, :] are the logits after chunk row i.
+ * Per row b, with a_i = argmax logits[b, i, :] (the lowest index among equal maxima; the first NaN wins, else the first +inf;
+ * -0 equals +0):
+ *   n = the largest value with a_i == draft[b, i] for all i < n (0 <= n <= gamma; a draft id outside [0, V) never matches);
+ *   the candidates are draft[b, 0 .. n-1] followed by a_n; they are cut after the first eos_token_id among them, and to the
+ *   room = lim - old_len columns still free, lim = min(limit, ncols - 1) (none when old_len is outside [0, lim));
+ *   with c kept: labels[b, old_len + 1 .. old_len + c] = the kept tokens, tok[b] = the last of them (unchanged when c = 0),
+ *   cache_seqlens[b] = old_len + c (draft_seqlens[b] likewise, when given), and seen_eos[b] is set when the kept tokens end in
+ *   eos_token_id, when old_len + c >= lim, or when old_len < 0;
+ *   a row whose seen_eos[b] is set on entry is frozen: only its lengths are written (restored to old_len), c = 0;
+ *   n_accepted[b] = min(n, c), n_new[b] = c (either may be NULL).
+ * No column of labels outside [1, ncols) is written, whatever cache_seqlens and limit hold.  All outputs are integers: the
+ * result is bitwise reproducible and does not depend on any order of evaluation (integer maxima, no atomics).  Two launches on
+ * `hip_stream`, grid and workspace a function of B, M and V only; nothing is read back by the host.  16-byte loads on a
+ * 16-byte aligned base with row and batch strides that are multiples of 8 elements, element loads otherwise.  B == 0 is a no-op.
+ * Rejected with FAT5_EINVAL before anything is launched: B < 0 or > 65535, M outside [2, 16], V outside [1, 2^20], dtype outside
+ * {FAT5_F32, FAT5_F16, FAT5_BF16}, row_stride < V, batch_stride < (M - 1) * row_stride + V, draft_stride < M - 1, ncols < 2,
+ * labels_stride < ncols, eos_token_id < 0, NULL or misaligned logits / draft / cache_seqlens / labels / tok / seen_eos,
+ * misaligned draft_seqlens / limit / n_accepted / n_new; FAT5_EWORKSPACE when the workspace is missing, misaligned (16 bytes) or
+ * smaller than fat5_spec_accept_workspace_bytes().
+ */
+typedef struct fat5_spec_params {
+  int32_t B, M, V;              /* M = gamma + 1 chunk rows */
+  int32_t dtype;                /* logits: FAT5_F32 | FAT5_F16 | FAT5_BF16 */
+  const void* logits;           /* (B, M, V), innermost stride 1 */
+  int64_t batch_stride;         /* elements */
+  int64_t row_stride;           /* elements */
+  const int64_t* draft;         /* (B, M - 1) int64 device array, row stride draft_stride elements */
+  int64_t draft_stride;
+  int32_t* cache_seqlens;       /* (B,) int32 device array, advanced by M on entry */
+  int32_t* draft_seqlens;       /* (B,) int32 device array or NULL: the drafter's lengths, set to the same value */
+  int64_t* labels;              /* (B, ncols) int64 device array, row stride labels_stride elements */
+  int64_t labels_stride;
+  int32_t ncols;
+  int32_t eos_token_id;
+  int64_t* tok;                 /* (B,) int64 device array: the pending token of every row */
+  uint8_t* seen_eos;            /* (B,) one byte per row (torch.bool) */
+  const int32_t* limit;         /* (B,) int32 device array, or NULL: limit_scalar for every row */
+  int32_t limit_scalar;
+  int32_t* n_accepted;          /* (B,) int32 device array or NULL */
+  int32_t* n_new;               /* (B,) int32 device array or NULL */
+  void* workspace;              /* fat5_spec_accept_workspace_bytes() bytes, 16-byte aligned */
+  size_t workspace_bytes;
+} fat5_spec_params;
+/* sizeof(fat5_spec_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_spec_params(void);
+/* bytes of workspace for (B, M, V); 0 for a NULL pointer or a shape fat5_spec_accept rejects */
+size_t fat5_spec_accept_workspace_bytes(const fat5_spec_params* p);
+int fat5_spec_accept(const fat5_spec_params* p, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)
