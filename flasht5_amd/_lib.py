@@ -98,6 +98,7 @@ class DecodeChunkParams(ctypes.Structure):
         ("q_stride", c_i64x3), ("k_cache_stride", c_i64x3), ("v_cache_stride", c_i64x3),
         ("k_new_stride", c_i64x3), ("v_new_stride", c_i64x3), ("o_stride", c_i64x3),
         ("num_splits", ctypes.c_int32), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+        ("chunk_seqlens", ctypes.c_void_p),
     ]
 
 

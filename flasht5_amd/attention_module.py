@@ -176,7 +176,7 @@ class FlashT5Attention(nn.Module):
             raise NotImplementedError(f"position_encoding_type {self.position_encoding_type!r} at decode time")
 
     def forward_decode(self, hidden_states, k_cache, v_cache, cache_seqlens=None, position_bias=None, position=None,
-                       cache_batch_idx=None, cache_row_batch=None):
+                       cache_batch_idx=None, cache_row_batch=None, cross_seqlens=None, chunk_seqlens=None):
         """One new token through this layer against a KV cache (flasht5_amd.decode.flash_attn_with_kvcache); returns (B, 1, d_model).
 
         Self-attention (`cache_seqlens` given): q, k and v are projected from `hidden_states` (B, 1, d_model), k and v are appended
@@ -191,13 +191,21 @@ class FlashT5Attention(nn.Module):
         A chunk of M > 1 tokens (`hidden_states` (B, M, d_model); returns (B, M, d_model)) goes through
         flash_attn_with_kvcache_chunk: self-attention appends the M rows and is causal inside the chunk, row i at position
         cache_seqlens[b] + i; cross-attention is not causal and has no bias.  RoPE uses rows position + arange(M) of the tables,
-        selected and clamped on the device.  The cache maps are for one row only."""
+        selected and clamped on the device.  The cache maps are for one row only.
+
+        Padding: `cross_seqlens` (B,) int32 (cross-attention only) is the number of valid encoder keys of each query row -- the
+        kernels' cache_seqlens without an append; with `cache_batch_idx` it is per query row, not per cache row.  `chunk_seqlens`
+        (B,) int32 (chunks only): the rows of the chunk each batch element brings (flash_attn_with_kvcache_chunk)."""
         self.decode_supported()
         from .decode import flash_attn_with_kvcache
         B, M = hidden_states.shape[:2]
         if M > 1:
             return self._forward_decode_chunk(hidden_states, k_cache, v_cache, cache_seqlens, position_bias, position,
-                                              cache_batch_idx, cache_row_batch)
+                                              cache_batch_idx, cache_row_batch, cross_seqlens, chunk_seqlens)
+        if chunk_seqlens is not None:
+            raise ValueError("forward_decode: chunk_seqlens needs a chunk of M > 1 rows")
+        if cross_seqlens is not None and cache_seqlens is not None:
+            raise ValueError("forward_decode: cross_seqlens is for cross-attention (cache_seqlens None)")
         H, Dh = self.n_heads, self.key_value_proj_dim
         q = self.Wq(hidden_states).view(B, 1, H, Dh)
         is_self = cache_seqlens is not None
@@ -221,16 +229,18 @@ class FlashT5Attention(nn.Module):
             rpe1d, radius = position_bias
             if self.attention_type == "triton":  # (the dense path adds the bias after a cast to the activation dtype)
                 rpe1d = rpe1d.to(q.dtype).float()
-        out = flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, self.softmax_scale, rpe1d, radius,
-                                      cache_batch_idx=cache_batch_idx, cache_row_batch=cache_row_batch)
+        out = flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens if is_self else cross_seqlens, self.softmax_scale,
+                                      rpe1d, radius, cache_batch_idx=cache_batch_idx, cache_row_batch=cache_row_batch)
         return self.o(out.reshape(B, 1, self.inner_dim))
 
     def _forward_decode_chunk(self, hidden_states, k_cache, v_cache, cache_seqlens, position_bias, position, cache_batch_idx,
-                              cache_row_batch):
+                              cache_row_batch, cross_seqlens=None, chunk_seqlens=None):
         """forward_decode for M > 1 rows: the same projections, rotation and bias rule on the chunk kernel"""
         from .decode import flash_attn_with_kvcache_chunk
         if cache_batch_idx is not None or cache_row_batch is not None:
             raise ValueError("forward_decode: cache_batch_idx / cache_row_batch take one query row per step (beam search has no chunks)")
+        if cross_seqlens is not None and cache_seqlens is not None:
+            raise ValueError("forward_decode: cross_seqlens is for cross-attention (cache_seqlens None)")
         B, M = hidden_states.shape[:2]
         H, Dh = self.n_heads, self.key_value_proj_dim
         q = self.Wq(hidden_states).view(B, M, H, Dh)
@@ -256,8 +266,13 @@ class FlashT5Attention(nn.Module):
             rpe1d, radius = position_bias
             if self.attention_type == "triton":  # (the dense path adds the bias after a cast to the activation dtype)
                 rpe1d = rpe1d.to(q.dtype).float()
-        out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, cache_seqlens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
-                                            rpe_radius=radius)
+        lens = cache_seqlens if is_self else cross_seqlens
+        if chunk_seqlens is None:
+            out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, lens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
+                                                rpe_radius=radius)
+        else:
+            out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, lens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
+                                                rpe_radius=radius, chunk_seqlens=chunk_seqlens)
         return self.o(out.reshape(B, M, self.inner_dim))
 
     def project_kv(self, key_value_states):

@@ -20,6 +20,10 @@
 //   The grid, the split count and the workspace size depend on B, H, M, capacity and num_splits only, so a captured graph stays valid
 //   while the lengths grow.  Every merge runs in a fixed order without float atomics: the bits are the same on every run.
 //   M = 1 means what fat5_attn_decode means.  cache_batch_idx / cache_row_batch are not taken here.
+//   Ragged chunks.  With chunk_seqlens, batch element b brings m_b = clamp(chunk_seqlens[b], 0, M) rows: m_b stands for M in every
+//                rule above (a_b = min(m_b, capacity - len_b); without an append p_i = L_b - m_b + i), query rows i >= m_b see no key
+//                (o = 0, lse = -inf) and new rows i >= m_b are neither read nor appended.  The lengths are read and clamped here, on
+//                the device; the grid and the workspace do not depend on them.  Null: m_b = M, the arithmetic above as it stands.
 //
 // Shape of the kernel.  A workgroup takes a tile of TQ = CHUNK_TQ consecutive query rows of one (b, h) and one split of the tile's key
 // range [0, kend), kend = min(L_b, p_last + 1) under `causal` (p_last: the tile's last row) and L_b otherwise; split s covers
@@ -47,6 +51,7 @@ struct ChunkArgs {
   void* o;                // (B, M, H, D)
   float* lse;             // (B, H, M) contiguous, or null
   const int32_t* seqlens; // (B,) or null: every batch element uses N
+  const int32_t* chunk_seqlens; // (B,) rows of the chunk each batch element brings, or null: M
   const float* rpe1d;     // (H, 2R + 1) or null
   float* ws;              // [B][H][M][S][2] (max, sum) then [B][H][M][S][D] o, fp32
   int64_t q_s[3], o_s[3], kn_s[3], vn_s[3], kc_s[3], vc_s[3];
@@ -67,17 +72,22 @@ __global__ __launch_bounds__(DEC_THREADS) void chunk_attn_kernel(ChunkArgs a) {
   const int i0 = tile * TQ;
   int len = a.seqlens ? a.seqlens[b] : a.N;
   len = len < 0 ? 0 : (len > a.cap ? a.cap : len);
-  const int napp = APPEND ? min(a.M, a.cap - len) : 0;   // a_b
+  int mb = a.M;                                          // m_b: the rows of the chunk this batch element brings
+  if (a.chunk_seqlens) {
+    mb = a.chunk_seqlens[b];
+    mb = mb < 0 ? 0 : (mb > a.M ? a.M : mb);
+  }
+  const int napp = APPEND ? min(mb, a.cap - len) : 0;    // a_b
   const int L = len + napp;
 
-  // per row of the tile: its position (the bias origin) and the last key it sees (-1: none; rows past M see nothing)
+  // per row of the tile: its position (the bias origin) and the last key it sees (-1: none; rows past m_b see nothing)
   int pos[TQ], lim[TQ];
   int kend = 0;
 #pragma unroll
   for (int r = 0; r < TQ; ++r) {
     const int i = i0 + r;
-    pos[r] = APPEND ? min(len + i, L - 1) : L - a.M + i;
-    lim[r] = i < a.M ? (a.causal ? min(pos[r], L - 1) : L - 1) : -1;
+    pos[r] = APPEND ? min(len + i, L - 1) : L - mb + i;
+    lim[r] = i < mb ? (a.causal ? min(pos[r], L - 1) : L - 1) : -1;
     kend = max(kend, lim[r] + 1);
   }
   const int chunk = (kend + a.splits - 1) / a.splits;
@@ -107,7 +117,7 @@ __global__ __launch_bounds__(DEC_THREADS) void chunk_attn_kernel(ChunkArgs a) {
     m[r] = -INFINITY, l[r] = 0.f;
 #pragma unroll
     for (int c = 0; c < 8; ++c) qf[r][c] = acc[r][c] = 0.f;
-    if (i0 + r < a.M) E::load(qbase + (int64_t)(i0 + r) * a.q_s[1], qf[r]);
+    if (i0 + r < mb) E::load(qbase + (int64_t)(i0 + r) * a.q_s[1], qf[r]);
   }
 
   for (int j0 = lo + g; j0 < hi; j0 += G * U) {

@@ -1134,6 +1134,8 @@ static int chunk_check(const fat5_decode_chunk_params* p) {
     return fail(FAT5_EINVAL, "%s: N %d outside [0, capacity %d] without cache_seqlens", what, p->N, p->capacity);
   if (p->cache_seqlens && (reinterpret_cast<uintptr_t>(p->cache_seqlens) & 3))
     return fail(FAT5_EINVAL, "%s: cache_seqlens misaligned", what);
+  if (p->chunk_seqlens && (reinterpret_cast<uintptr_t>(p->chunk_seqlens) & 3))
+    return fail(FAT5_EINVAL, "%s: chunk_seqlens misaligned", what);
   if (p->bias_mode != FAT5_BIAS_NONE && p->bias_mode != FAT5_BIAS_RPE1D)
     return fail(FAT5_EINVAL, "%s: bias_mode %d (FAT5_BIAS_NONE or FAT5_BIAS_RPE1D)", what, p->bias_mode);
   if (p->bias_mode == FAT5_BIAS_RPE1D) {
@@ -1182,6 +1184,7 @@ int fat5_attn_decode_chunk(const fat5_decode_chunk_params* p, void* stream_) {
   a.o = p->o;
   a.lse = p->lse;
   a.seqlens = p->cache_seqlens;
+  a.chunk_seqlens = p->chunk_seqlens;
   a.rpe1d = p->bias_mode == FAT5_BIAS_RPE1D ? p->rpe1d : nullptr;
   a.ws = static_cast<float*>(p->workspace);
   for (int i = 0; i < 3; ++i) {

@@ -166,7 +166,7 @@ def _attn_decode_fake(q, k_cache, v_cache, k, v, cache_seqlens, sm_scale, rpe1d,
     return [o, lse]
 
 
-def _as_seqlens(cache_seqlens, device):
+def _as_seqlens(cache_seqlens, device, name="cache_seqlens"):
     """int32 device lengths, converted the way `_as_cu` converts cu_seqlens -- except inside a graph capture, where a conversion
     would bake one value into the graph: there they must already be an int32 tensor on the device"""
     if cache_seqlens is None:
@@ -175,7 +175,7 @@ def _as_seqlens(cache_seqlens, device):
     if ok:
         return cache_seqlens
     if torch.cuda.is_current_stream_capturing():
-        raise ValueError("flash_attn_with_kvcache: inside a graph capture cache_seqlens must already be a contiguous int32 tensor on "
+        raise ValueError(f"flash_attn_with_kvcache: inside a graph capture {name} must already be a contiguous int32 tensor on "
                          f"{device} (a conversion would fix its current value in the graph)")
     return cache_seqlens.to(device=device, dtype=torch.int32).contiguous()
 
@@ -208,7 +208,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
 
 
 # ------------------------------------------------------------------------------------------------ M query rows per (batch, head)
-def _chunk_params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse, sm_scale, causal, rpe1d, radius, num_splits):
+def _chunk_params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse, sm_scale, causal, rpe1d, radius, num_splits, chunk_seqlens=None):
     B, M, H, D = q.shape
     p = _lib.DecodeChunkParams()
     p.B, p.H, p.M, p.D = B, H, M, D
@@ -229,13 +229,28 @@ def _chunk_params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse, sm_scale, ca
         p.v_new_stride[:] = v.stride()[:3]
     p.lse = lse.data_ptr() if lse is not None else None
     p.num_splits = int(num_splits)
+    p.chunk_seqlens = chunk_seqlens.data_ptr() if chunk_seqlens is not None else None
     return p
 
 
 MAX_CHUNK = 1024  # (CHUNK_MAX_M, csrc/decode_chunk_kernels.h)
 
 
-def _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius):
+def _check_chunk_seqlens(chunk_seqlens, B, device=None, what="flash_attn_with_kvcache_chunk"):
+    """chunk_seqlens' errors in their order: the shape, then the dtype, then (with `device`: the operator's strict form, which
+    converts nothing) int32 on that device"""
+    if chunk_seqlens is None:
+        return
+    if chunk_seqlens.dim() != 1 or chunk_seqlens.numel() != B:
+        raise ValueError(f"{what}: chunk_seqlens must hold {B} lengths, got shape {tuple(chunk_seqlens.shape)}")
+    if chunk_seqlens.dtype not in (torch.int32, torch.int64) or (device is not None and chunk_seqlens.dtype != torch.int32):
+        raise TypeError(f"{what}: chunk_seqlens must be an int32{'' if device is not None else ' (or int64)'} tensor, got "
+                        f"{chunk_seqlens.dtype}")
+    if device is not None and (chunk_seqlens.device != device or not chunk_seqlens.is_contiguous()):
+        raise ValueError(f"{what}: chunk_seqlens must be a contiguous int32 tensor on {device}, got one on {chunk_seqlens.device}")
+
+
+def _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius, chunk_seqlens=None):
     """everything the host can check without touching a device"""
     what = "flash_attn_with_kvcache_chunk"
     if q.dim() != 4 or not 1 <= q.shape[1] <= MAX_CHUNK:
@@ -273,6 +288,7 @@ def _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius)
         if rpe1d.dtype != torch.float32 or tuple(rpe1d.shape) != (H, 2 * int(radius) + 1) or not rpe1d.is_contiguous():
             raise ValueError(f"{what}: rpe1d must be a contiguous fp32 ({H}, 2 * rpe_radius + 1) = ({H}, {2 * int(radius) + 1}) tensor, "
                              f"got {rpe1d.dtype} {tuple(rpe1d.shape)}")
+    _check_chunk_seqlens(chunk_seqlens, B)
 
 
 def _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d):
@@ -288,10 +304,12 @@ def _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d):
 @torch.library.custom_op("fat5::attn_decode_chunk", mutates_args=("k_cache", "v_cache"), device_types="cuda")
 def attn_decode_chunk(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor],
                       v: Optional[torch.Tensor], cache_seqlens: Optional[torch.Tensor], sm_scale: float, causal: bool,
-                      rpe1d: Optional[torch.Tensor], rpe_radius: int, return_lse: bool, num_splits: int) -> List[torch.Tensor]:
+                      rpe1d: Optional[torch.Tensor], rpe_radius: int, return_lse: bool, num_splits: int,
+                      chunk_seqlens: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
     """[o (B, M, H, D) contiguous, lse (B, H, M) fp32 (empty (0,) when return_lse is False)]; appends k / v to the caches"""
-    _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius)
+    _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius, chunk_seqlens)
     _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d)
+    _check_chunk_seqlens(chunk_seqlens, q.shape[0], q.device, "fat5::attn_decode_chunk")
     if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or cache_seqlens.device != q.device or
                                       not cache_seqlens.is_contiguous()):
         raise ValueError(f"fat5::attn_decode_chunk: cache_seqlens must be a contiguous int32 tensor on {q.device}")
@@ -300,7 +318,7 @@ def attn_decode_chunk(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     o = torch.empty((B, M, H, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, M), dtype=torch.float32, device=q.device) if return_lse else q.new_empty((0,), dtype=torch.float32)
     p = _chunk_params(q, k_cache, v_cache, k, v, cache_seqlens, o, lse if return_lse else None, sm_scale, causal, rpe1d, rpe_radius,
-                      num_splits)
+                      num_splits, chunk_seqlens)
     lib = _lib.load()
     ws = None
     need = lib.fat5_attn_decode_chunk_workspace_bytes(p)
@@ -313,7 +331,8 @@ def attn_decode_chunk(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
 
 
 @attn_decode_chunk.register_fake
-def _attn_decode_chunk_fake(q, k_cache, v_cache, k, v, cache_seqlens, sm_scale, causal, rpe1d, rpe_radius, return_lse, num_splits):
+def _attn_decode_chunk_fake(q, k_cache, v_cache, k, v, cache_seqlens, sm_scale, causal, rpe1d, rpe_radius, return_lse, num_splits,
+                            chunk_seqlens=None):
     B, M, H, D = q.shape
     o = q.new_empty((B, M, H, D))
     lse = q.new_empty((B, H, M), dtype=torch.float32) if return_lse else q.new_empty((0,), dtype=torch.float32)
@@ -321,7 +340,7 @@ def _attn_decode_chunk_fake(q, k_cache, v_cache, k, v, cache_seqlens, sm_scale, 
 
 
 def flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, softmax_scale=None, causal=False, rpe1d=None,
-                                  rpe_radius=0, return_lse=False, num_splits=0):
+                                  rpe_radius=0, return_lse=False, num_splits=0, chunk_seqlens=None):
     """flash_attn's `flash_attn_with_kvcache` for M query rows: returns o (B, M, H, D), or (o, lse (B, H, M) fp32) with return_lse.
 
     With k / v (B, M, H, D) the rows are written into the caches at cache_seqlens[b] .. cache_seqlens[b] + M - 1 inside the launch
@@ -330,15 +349,24 @@ def flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k=None, v=None, cache_seq
     rpe1d[h][clamp(j - p_i, -R, R) + R].  Rows that no longer fit into the caches are not appended and sit at the last key;
     a row that sees no key gives o = 0, lse = -inf.  cache_seqlens is not incremented: the caller advances it by M.  An int
     cache_seqlens broadcasts over the batch.  num_splits 0 lets the library pick the key-range split from B, H, M and the capacity
-    (never from the lengths: a captured graph stays valid while they grow)."""
+    (never from the lengths: a captured graph stays valid while they grow).
+
+    `chunk_seqlens` (B,) int32: a ragged chunk.  Batch element b brings m_b = clamp(chunk_seqlens[b], 0, M) rows; m_b stands for M
+    above (m_b rows appended, the alignment without an append from L_b - m_b), query rows i >= m_b give o = 0 and lse = -inf and
+    nothing at or past cache_seqlens[b] + m_b is written.  Read and clamped on the device; inside a graph capture it must already
+    be a contiguous int32 tensor on the device, as cache_seqlens must.  None: every element brings M rows."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v, rpe1d)):
         raise RuntimeError("flash_attn_with_kvcache_chunk is forward only: call it under torch.no_grad() / inference_mode(), or detach")
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32)
-    _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius)  # (before the device checks)
+    _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius, chunk_seqlens)  # (before the device checks)
     _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d)
     lens = _as_seqlens(cache_seqlens, q.device)
     scale = 1.0 / math.sqrt(q.shape[-1]) if softmax_scale is None else float(softmax_scale)
-    o, lse = attn_decode_chunk(q, k_cache, v_cache, k, v, lens, scale, bool(causal), rpe1d, int(rpe_radius), bool(return_lse),
-                               int(num_splits))
+    if chunk_seqlens is None:
+        o, lse = attn_decode_chunk(q, k_cache, v_cache, k, v, lens, scale, bool(causal), rpe1d, int(rpe_radius), bool(return_lse),
+                                   int(num_splits))
+    else:
+        o, lse = attn_decode_chunk(q, k_cache, v_cache, k, v, lens, scale, bool(causal), rpe1d, int(rpe_radius), bool(return_lse),
+                                   int(num_splits), _as_seqlens(chunk_seqlens, q.device, "chunk_seqlens"))
     return (o, lse) if return_lse else o

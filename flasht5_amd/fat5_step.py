@@ -303,11 +303,11 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         from .generation import init_decode_state
         return init_decode_state(self, input_ids, max_length, attention_mask, prompt_length=prompt_length)
 
-    def decode_chunk(self, state, token_ids, logits="all"):
+    def decode_chunk(self, state, token_ids, logits="all", chunk_seqlens=None):
         """M tokens per row (B, M) through the cached decoder in one step -> logits (B, M, vocab) ("all"), (B, vocab) ("last") or
-        None ("none"); the caches and cache_seqlens advance by M (generation.decode_chunk)"""
+        None ("none"); the caches and cache_seqlens advance by M, or per row by chunk_seqlens (generation.decode_chunk)"""
         from .generation import decode_chunk
-        return decode_chunk(self, state, token_ids, logits)
+        return decode_chunk(self, state, token_ids, logits, chunk_seqlens)
 
     def decode_step(self, state, token_ids):
         """one token per row through the cached decoder -> logits (B, vocab) of the next position (generation.decode_step)"""
@@ -317,19 +317,21 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
     def generate(self, input_ids, attention_mask=None, max_length=32, graph=False, *, do_sample=False, temperature=1.0, top_k=50,
                  top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
                  return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None,
-                 decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False):
+                 decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
+                 decoder_attention_mask=None):
         """greedy (or, with do_sample=True, temperature / top-k / top-p sampled) decoding with a KV cache; returns what the
         reference's generate returns; num_beams > 1: HF's beam search; repetition_penalty / no_repeat_ngram_size / min_length /
         suppress_tokens: HF's logits processors in one HIP launch per step; decoder_input_ids (B, P): a decoder prompt, prefilled
         in one chunk step; assistant_model: speculative greedy decoding, num_assistant_tokens drafted per round and verified in one
-        chunk step (generation.generate)"""
+        chunk step; attention_mask / decoder_attention_mask: right-padded inputs and ragged decoder prompts (generation.generate)"""
         from .generation import generate
         return generate(self, input_ids, attention_mask, max_length, graph, do_sample=do_sample, temperature=temperature,
                         top_k=top_k, top_p=top_p, seed=seed, num_beams=num_beams, num_return_sequences=num_return_sequences,
                         length_penalty=length_penalty, early_stopping=early_stopping, return_scores=return_scores,
                         repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
                         suppress_tokens=suppress_tokens, decoder_input_ids=decoder_input_ids, assistant_model=assistant_model,
-                        num_assistant_tokens=num_assistant_tokens, return_stats=return_stats)
+                        num_assistant_tokens=num_assistant_tokens, return_stats=return_stats,
+                        decoder_attention_mask=decoder_attention_mask)
 
 
 def allreduce_gradients(model: nn.Module, group=None, average=True):

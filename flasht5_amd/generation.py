@@ -34,6 +34,12 @@ loop then starts from the prompt's last token.  `decode_chunk` is also the verif
 Speculative greedy decoding (`assistant_model`; flasht5_amd/speculative.py): a second, cheaper model drafts gamma
 tokens per round, one `decode_chunk` step of gamma + 1 rows checks them, and the verification kernel accepts, rolls the per-row
 lengths back and does the step's bookkeeping on the device.  Without an assistant none of it runs: the code path above is unchanged.
+
+Padding (`attention_mask`, `decoder_attention_mask`): right-padded masks are validated with one host read before an
+encoder runs (`check_padding`).  The encoder then sees only each row's valid keys (packed through `flash_attn_varlen_func` under
+fat5_rpe and RoPE, the mask folded into the dense bias otherwise), every cross-attention launch gets the row's encoder length as
+its `cache_seqlens`, and a ragged decoder prompt is prefilled by one chunk step with per-row `chunk_seqlens`.  All-ones masks and
+None take the code path above.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -56,6 +62,7 @@ class DecodeState:
     steps: int = 0                      # decode_step calls so far (host-side: decode_step refuses to run past the capacity)
     cross_batch_idx: Optional[torch.Tensor] = None  # beam search: (B * k,) int32, beam row -> encoder row (b // k)
     row_batch: Optional[torch.Tensor] = None        # beam search: (B * k, capacity) int32 history table (cache_row_batch)
+    cross_seqlens: Optional[torch.Tensor] = None    # padded inputs: (B,) / (B * k,) int32 valid encoder keys per decoding row
 
     @property
     def position(self):
@@ -77,10 +84,138 @@ def _check_supported(model):
         blk.cross_attention_layer.cross_attention.decode_supported()
 
 
+@dataclass
+class Padding:
+    """a validated right-padded mask: each row's length on the host (what the one host read brought) and on the device"""
+    lengths: List[int]
+    lengths_dev: torch.Tensor   # (B,) int32
+    mask: torch.Tensor          # (B, L) bool
+
+
+def _mask_shape_ok(name, mask, like, what):
+    if not torch.is_tensor(mask) or mask.dim() != 2 or tuple(mask.shape) != tuple(like.shape[:2]):
+        raise ValueError(f"{what}: {name} must be a (B, L) = {tuple(like.shape[:2])} tensor like the ids it masks, got "
+                         f"{tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
+    if mask.dtype.is_floating_point or mask.dtype.is_complex:
+        raise ValueError(f"{what}: {name} must be a bool or integer tensor, got {mask.dtype}")
+
+
+def check_padding(input_ids, attention_mask=None, decoder_input_ids=None, decoder_attention_mask=None, what="generate"):
+    """Validate the padding masks of a call with ONE host read -> (encoder Padding or None, decoder Padding or None).
+
+    A mask is (B, L) bool or integer, non-zero = valid, right-padded (row b valid at columns [0, len_b), len_b >= 1).  Holes, left
+    padding and an empty row raise ValueError.  None and an all-ones mask both give None: the unpadded code path.  An
+    already-validated `Padding` passes through unread."""
+    masks = []
+    for name, mask, ids in (("attention_mask", attention_mask, input_ids), ("decoder_attention_mask", decoder_attention_mask,
+                                                                           decoder_input_ids)):
+        if mask is None or isinstance(mask, Padding):
+            continue
+        if ids is None:
+            raise ValueError(f"{what}: {name} needs the ids it masks (decoder_input_ids)")
+        _mask_shape_ok(name, mask, ids, what)
+        masks.append((name, mask.to(input_ids.device) != 0))   # (both masks live where the model runs)
+    out = {"attention_mask": attention_mask if isinstance(attention_mask, Padding) else None,
+           "decoder_attention_mask": decoder_attention_mask if isinstance(decoder_attention_mask, Padding) else None}
+    if masks:
+        rows = []
+        for _, m in masks:   # per mask: the B lengths, then one flag (1: every row is a prefix of ones)
+            n = m.sum(1)
+            prefix = (m == (torch.arange(m.shape[1], device=m.device).unsqueeze(0) < n.unsqueeze(1))).all()
+            rows += [n, prefix.to(n.dtype).reshape(1)]
+        host = torch.cat(rows).tolist()   # the one host read
+        for name, m in masks:
+            B, L = m.shape
+            lens, ok = host[:B], host[B]
+            host = host[B + 1:]
+            if min(lens) < 1:
+                raise ValueError(f"{what}: {name} has an empty row (row {lens.index(min(lens))}): every row needs at least one "
+                                 "valid position")
+            if not ok:
+                raise ValueError(f"{what}: {name} must be right-padded (each row a run of valid positions, then padding): left "
+                                 "padding and masks with holes are not supported")
+            if min(lens) < L:
+                out[name] = Padding(lens, torch.tensor(lens, dtype=torch.int32).to(m.device), m)
+    return out["attention_mask"], out["decoder_attention_mask"]
+
+
+def _packed_encoder(stack, input_ids, pad):
+    """the encoder stack over the valid tokens only (fat5_rpe and RoPE): unpad with indices built from the host lengths, every
+    self-attention through flash_attn_varlen_func (the T5 generator or rotated q / k / v, positions local to each row), then the
+    rows scattered back into a zero (B, L, d_model) tensor"""
+    from .flash_attention_v2_bias import flash_attn_varlen_func
+    from .rotary import apply_rotary_emb_qkv
+    B, L = input_ids.shape
+    dev = input_ids.device
+    lens = pad.lengths
+    idx = torch.cat([torch.arange(n) + b * L for b, n in enumerate(lens)]).to(dev)
+    cu = torch.tensor([0] + [sum(lens[:b + 1]) for b in range(B)], dtype=torch.int32).to(dev)
+    mx, total = max(lens), sum(lens)
+    h = _embed_stack(stack, input_ids.reshape(-1).index_select(0, idx).unsqueeze(0))   # (1, total, d_model)
+    bias = None
+    for blk in stack.block:
+        sa = blk.self_attention_layer
+        att = sa.self_attention
+        H, D = att.n_heads, att.key_value_proj_dim
+        n = sa.layer_norm(h)
+        q, k, v = (w(n).view(total, H, D) for w in (att.Wq, att.Wk, att.Wv))
+        rpe1d, radius = None, 0
+        if att.rotary:
+            cos, sin, cos_k, sin_k = att.pe_encoding.tables(q.device, q.dtype)
+            q, k, v = apply_rotary_emb_qkv(q, k, v, cos, sin, cos_k, sin_k, att.pe_encoding.interleaved, cu_seqlens=cu, max_seqlen=mx)
+        else:
+            if bias is None:
+                bias = att.pe_encoding.forward_1d()   # (block 0 owns the generator; the others are handed it)
+            rpe1d, radius = bias
+        o = flash_attn_varlen_func(q, k, v, cu, cu, mx, mx, False, att.softmax_scale, rpe1d, radius)
+        h = h + att.o(o.reshape(1, total, att.inner_dim))
+        h = blk.ff_layer(h)
+    h = stack.final_layer_norm(h)
+    enc = h.new_zeros((B * L, h.shape[-1]))
+    enc.index_copy_(0, idx, h[0])
+    return enc.view(B, L, -1)
+
+
+def _embed_stack(stack, ids):
+    h = stack.embed_tokens(ids)
+    if torch.is_autocast_enabled() and h.is_cuda:  # (FAT5Stack.forward's rule)
+        h = h.to(torch.get_autocast_dtype("cuda"))
+    return h
+
+
+def _masked_bias_encoder(stack, input_ids, pad):
+    """the encoder stack under the dense-bias type: block 0's (1, H, L, L) bias with the padded key columns at the dtype's minimum,
+    as FlashT5Attention folds a mask in under use_masking, handed to every block; the padded rows of the result are zeroed"""
+    B, L = input_ids.shape
+    h = _embed_stack(stack, input_ids)
+    att = stack.block[0].self_attention_layer.self_attention
+    bias = att.pe_encoding.compute_bias(L, L, device=h.device).to(h.dtype)
+    bias = torch.where(pad.mask.view(B, 1, 1, L), bias, torch.finfo(h.dtype).min).contiguous()
+    for blk in stack.block:
+        h, bias = blk(h, bias, None)
+    return stack.final_layer_norm(h).masked_fill(~pad.mask.unsqueeze(-1), 0)
+
+
+def encode(model, input_ids, pad=None):
+    """the encoder's output (B, L, d_model); with a `Padding`, every row's self-attention sees its own valid keys only and the
+    padded rows come back as zeros"""
+    if pad is None:
+        return model.encoder(input_ids)
+    att = model.encoder.block[0].self_attention_layer.self_attention
+    if att.rotary or att.attention_type == "fat5_rpe":
+        return _packed_encoder(model.encoder, input_ids, pad)
+    if att.position_encoding_type != "t5":
+        raise NotImplementedError(f"attention_mask with position_encoding_type {att.position_encoding_type!r}")
+    return _masked_bias_encoder(model.encoder, input_ids, pad)
+
+
 @torch.no_grad()
 def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1, prompt_length=1):
     """Run the encoder, project every decoder layer's cross-attention K / V once and allocate self-attention caches of capacity
-    `max_length + prompt_length` (a decoder prompt of `prompt_length` tokens, the start token included, then max_length new ones).  `attention_mask` is accepted and not applied, as the reference does with use_masking=False.
+    `max_length + prompt_length` (a decoder prompt of `prompt_length` tokens, the start token included, then max_length new ones).
+    `attention_mask` (B, L), right-padded, is applied: it is validated with one host read before the encoder runs
+    (`check_padding`; a validated `Padding` is taken as it is), the encoder's self-attention sees each row's valid keys only, and
+    `cross_seqlens` carries the rows' encoder lengths to every cross-attention launch.  None and an all-ones mask change nothing.
     num_beams > 1: the encoder and the cross K / V stay at B rows; the self-attention caches, the lengths and the history table
     get B * num_beams rows (row b * k + j: beam j of input b)."""
     _check_supported(model)
@@ -93,7 +228,8 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
                          f"{first.pe_encoding.max_sequence_length - int(prompt_length)}")
     B = input_ids.shape[0]
     Bk = B * int(num_beams)
-    enc = model.encoder(input_ids)
+    pad, _ = check_padding(input_ids, attention_mask, what="init_decode_state")
+    enc = encode(model, input_ids, pad)
     dev = enc.device
     # (the projections' dtype: autocast's when it is on, the weights' otherwise -- the dtype of k and v in the training forward)
     dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else model.shared.weight.dtype
@@ -112,6 +248,8 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     if num_beams > 1:
         state.cross_batch_idx = torch.arange(Bk, dtype=torch.int32, device=dev) // int(num_beams)
         state.row_batch = torch.zeros((Bk, cap), dtype=torch.int32, device=dev)
+    if pad is not None:  # (per decoding row: beam row b * k + j reads encoder row b, so it gets that row's length)
+        state.cross_seqlens = pad.lengths_dev if num_beams == 1 else pad.lengths_dev.repeat_interleave(int(num_beams))
     return state
 
 
@@ -132,7 +270,7 @@ def decode_step(model, state, token_ids):
                                                  position_bias=state.position_bias, position=pos, cache_row_batch=state.row_batch)
         ca = blk.cross_attention_layer
         h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos,
-                                                  cache_batch_idx=state.cross_batch_idx)
+                                                  cache_batch_idx=state.cross_batch_idx, cross_seqlens=state.cross_seqlens)
         h = blk.ff_layer(h)
     h = model.decoder.final_layer_norm(h)
     state.cache_seqlens.add_(1)
@@ -140,12 +278,16 @@ def decode_step(model, state, token_ids):
 
 
 @torch.no_grad()
-def decode_chunk(model, state, token_ids, logits="all"):
+def decode_chunk(model, state, token_ids, logits="all", chunk_seqlens=None):
     """M tokens per batch row (B, M) through the decoder against the caches in one step: every self-attention layer appends its M
     key / value rows with the chunk decode kernel (causal inside the chunk, row i at position cache_seqlens + i), and
     cache_seqlens advances by M on the device.  Returns the logits of all M next positions (B, M, vocab) for logits="all", of the
     last one (B, vocab) for "last" (the final norm and lm_head run on that row only), or None for "none" (both are skipped: a
-    prefill that only fills the caches)."""
+    prefill that only fills the caches).
+
+    `chunk_seqlens` (B,) int32 on the device: a ragged chunk (right-padded token_ids).  Row b brings its first chunk_seqlens[b]
+    tokens: only those are appended, cache_seqlens[b] advances by that many, and "last" gathers row b's logits at its own last
+    token (on the device); the logits of rows past a row's length mean nothing."""
     if logits not in ("all", "last", "none"):
         raise ValueError(f"decode_chunk: logits {logits!r} ('all', 'last' or 'none')")
     B = state.cache_seqlens.shape[0]
@@ -157,27 +299,40 @@ def decode_chunk(model, state, token_ids, logits="all"):
     if state.steps + M > state.capacity:
         raise ValueError(f"decode_chunk: the caches hold {state.capacity} positions, {state.steps} are used and the chunk brings {M} "
                          "(init_decode_state with a larger max_length or prompt_length)")
+    if chunk_seqlens is not None:
+        if M == 1:
+            raise ValueError("decode_chunk: chunk_seqlens needs M > 1 columns (a one-token step has nothing to pad)")
+        if (not torch.is_tensor(chunk_seqlens) or chunk_seqlens.dtype != torch.int32 or tuple(chunk_seqlens.shape) != (B,) or
+                chunk_seqlens.device != state.cache_seqlens.device):
+            raise ValueError(f"decode_chunk: chunk_seqlens must be a ({B},) int32 tensor on {state.cache_seqlens.device}")
     state.steps += M
     h = _embed(model, token_ids)
     pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
     for i, blk in enumerate(model.decoder.block):
         sa = blk.self_attention_layer
         h = h + sa.self_attention.forward_decode(sa.layer_norm(h), state.self_k[i], state.self_v[i], state.cache_seqlens,
-                                                 position_bias=state.position_bias, position=pos)
+                                                 position_bias=state.position_bias, position=pos, chunk_seqlens=chunk_seqlens)
         ca = blk.cross_attention_layer
-        h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos)
+        h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos,
+                                                  cross_seqlens=state.cross_seqlens, chunk_seqlens=chunk_seqlens)
         h = blk.ff_layer(h)
-    state.cache_seqlens.add_(M)
+    state.cache_seqlens.add_(M if chunk_seqlens is None else chunk_seqlens.clamp(0, M))
     if logits == "none":
         return None
     if logits == "last":
+        if chunk_seqlens is not None:   # row b's own last token, selected on the device
+            at = (chunk_seqlens.long() - 1).clamp(0, M - 1).view(B, 1, 1).expand(B, 1, h.shape[-1])
+            return model.lm_head(model.decoder.final_layer_norm(h.gather(1, at)))[:, 0]
         return model.lm_head(model.decoder.final_layer_norm(h[:, -1:]))[:, 0]
     return model.lm_head(model.decoder.final_layer_norm(h))
 
 
-def _check_prompt(model, input_ids, decoder_input_ids, num_beams):
-    """host-side validation of a decoder prompt -> its length P (1 without one)"""
+def _check_prompt(model, input_ids, decoder_input_ids, num_beams, decoder_attention_mask=None):
+    """host-side validation of a decoder prompt -> its length P (1 without one); with a mask the ids under the padding are not
+    looked at (the mask's own validation is check_padding's)"""
     if decoder_input_ids is None:
+        if decoder_attention_mask is not None:
+            raise ValueError("generate: decoder_attention_mask needs decoder_input_ids")
         return 1
     if num_beams > 1:
         raise ValueError("generate: decoder_input_ids with num_beams > 1 is not supported (beam search starts from the start token)")
@@ -188,6 +343,9 @@ def _check_prompt(model, input_ids, decoder_input_ids, num_beams):
                          f"{' ' + str(p.dtype) if torch.is_tensor(p) else ''}")
     if p.shape[0] != input_ids.shape[0]:
         raise ValueError(f"generate: decoder_input_ids holds {p.shape[0]} rows, input_ids {input_ids.shape[0]}")
+    if decoder_attention_mask is not None and not isinstance(decoder_attention_mask, Padding):
+        _mask_shape_ok("decoder_attention_mask", decoder_attention_mask, p, "generate")
+        p = p.masked_fill(decoder_attention_mask.to(p.device) == 0, 0)
     V = model.lm_head.weight.shape[0]
     lo, hi = int(p.min()), int(p.max())
     if lo < 0 or hi >= V:
@@ -209,7 +367,12 @@ def _processed(logits, sequences, lengths, proc, log_softmax=False):
 def _greedy_step(model, state, tok, labels, seen_eos, proc=None):
     """decode_step + argmax: the token goes to `tok` and to column cache_seqlens of `labels` (a device-side index), and rows that
     produced a 1 are marked in `seen_eos` -- nothing here reads the host, so the same code is captured as it is"""
-    logits = _processed(decode_step(model, state, tok), labels, state.cache_seqlens, proc)
+    _greedy_pick(decode_step(model, state, tok), state, tok, labels, seen_eos, proc)
+
+
+def _greedy_pick(logits, state, tok, labels, seen_eos, proc=None):
+    """_greedy_step after the decoder: `logits` (B, vocab) of the position cache_seqlens (already incremented) points at"""
+    logits = _processed(logits, labels, state.cache_seqlens, proc)
     nxt = logits.argmax(-1)
     tok.copy_(nxt)
     col = state.cache_seqlens.long().unsqueeze(1)  # (already incremented: the new token's column)
@@ -221,9 +384,14 @@ def _sample_step(model, state, tok, labels, seen_eos, sampling, proc=None):
     """decode_step + sample_logits, with _greedy_step's bookkeeping; the Philox counter of row b is cache_seqlens[b] after the
     increment (the new token's position), read on the device -- so the captured step draws a fresh uniform at every replay.
     The processors run before the warpers, as in HF: the sampler gets the processed fp32 row"""
+    _sample_pick(decode_step(model, state, tok), state, tok, labels, seen_eos, sampling, proc)
+
+
+def _sample_pick(logits, state, tok, labels, seen_eos, sampling, proc=None):
+    """_sample_step after the decoder (see _greedy_pick)"""
     from .sampling import sample_logits
     temperature, top_k, top_p, seed = sampling
-    logits = _processed(decode_step(model, state, tok), labels, state.cache_seqlens, proc)
+    logits = _processed(logits, labels, state.cache_seqlens, proc)
     nxt = sample_logits(logits, temperature, top_k, top_p, seed=seed, offsets=state.cache_seqlens)
     tok.copy_(nxt)
     col = state.cache_seqlens.long().unsqueeze(1)
@@ -231,10 +399,14 @@ def _sample_step(model, state, tok, labels, seen_eos, sampling, proc=None):
     seen_eos.logical_or_(nxt == 1)
 
 
-def finish_labels(labels):
-    """the reference's ending (:682-688): the last column becomes 1, and everything after each row's first 1 becomes 0"""
+def finish_labels(labels, last=None):
+    """the reference's ending (:682-688): the last column becomes 1, and everything after each row's first 1 becomes 0.  `last`
+    (B,) int64 on the device: each row's own last column (ragged prompts: rows end at different columns)"""
     labels = labels.clone()
-    labels[:, -1] = 1
+    if last is None:
+        labels[:, -1] = 1
+    else:
+        labels.scatter_(1, last.view(-1, 1), 1)
     L = labels.shape[1]
     first = (labels == 1).long().argmax(-1, keepdim=True)
     keep = torch.arange(L, device=labels.device).unsqueeze(0) <= first
@@ -292,7 +464,8 @@ def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, le
 def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, *, do_sample=False, temperature=1.0, top_k=50,
              top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
              return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None,
-             decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False):
+             decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
+             decoder_attention_mask=None):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -340,10 +513,27 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     (labels, {"rounds", "drafted", "accepted"}) with host ints: the rounds run, the tokens drafted for unfinished rows and how many
     of them were accepted.  Rejected on the host before either encoder runs: do_sample=True, num_beams > 1, any active logits
     processor, num_assistant_tokens outside [1, 15], a vocabulary mismatch, a model the decode path refuses, and RoPE models
-    with more than one batch row (rows advance raggedly; the decode path keeps one rotary position for the batch)."""
+    with more than one batch row (rows advance raggedly; the decode path keeps one rotary position for the batch).
+
+    Padding.  `attention_mask` (B, L) and `decoder_attention_mask` (B, P), bool or integer, right-padded with at
+    least one valid position per row, are validated together with ONE host read before any encoder runs; holes, left padding
+    and an empty row raise ValueError, None and all-ones masks change nothing.  With `attention_mask` the encoder's
+    self-attention and every decoder cross-attention (greedy, sampled, beam, speculative -- both models --, eager and graph=True)
+    see only the valid keys of their row, so a row decodes what it decodes alone, unpadded.  With `decoder_attention_mask` row b's
+    prompt is its first P_b columns: ONE chunk step prefills all rows (per-row chunk lengths), row b's first new token comes
+    from the logits at its own last prompt row, and max_length new tokens follow each row's own prompt; the result is
+    (B, P + steps), rows with shorter prompts end earlier and are 0 from there.  Ragged prompts are rejected with RoPE at B > 1
+    (one rotary row per batch) and with an assistant model; beam search takes no decoder prompt at all."""
     from .beam import check_args as check_beam_args
     check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample)
-    P = _check_prompt(model, input_ids, decoder_input_ids, num_beams)
+    P = _check_prompt(model, input_ids, decoder_input_ids, num_beams, decoder_attention_mask)
+    attention_mask, dec_pad = check_padding(input_ids, attention_mask, decoder_input_ids, decoder_attention_mask)
+    if dec_pad is not None:
+        if assistant_model is not None:
+            raise ValueError("generate: decoder_attention_mask (a ragged decoder prompt) with assistant_model is not supported")
+        if model.decoder.block[0].self_attention_layer.self_attention.rotary and input_ids.shape[0] > 1:
+            raise ValueError("generate: a ragged decoder prompt with RoPE needs B = 1: the decode path keeps one rotary position "
+                             f"for the batch, and the rows of this one start at {dec_pad.lengths}")
     proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, P)
     if assistant_model is not None:
         from .speculative import check_generate_args, speculative_generate
@@ -356,6 +546,9 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
                               early_stopping, return_scores, proc)
     proc = _proc_on_device(proc, input_ids.device)
     step = _greedy_step
+
+    def pick(logits, state, tok, labels, seen_eos):
+        _greedy_pick(logits, state, tok, labels, seen_eos, proc)
     if proc is not None:
         def step(model, state, tok, labels, seen_eos):
             _greedy_step(model, state, tok, labels, seen_eos, proc)
@@ -368,22 +561,35 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
 
         def step(model, state, tok, labels, seen_eos):
             _sample_step(model, state, tok, labels, seen_eos, sampling, proc)
+
+        def pick(logits, state, tok, labels, seen_eos):  # noqa: F811
+            _sample_pick(logits, state, tok, labels, seen_eos, sampling, proc)
     B = input_ids.shape[0]
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask, prompt_length=P)
     labels = torch.zeros((B, state.capacity), dtype=torch.long, device=dev)
     tok = torch.zeros((B,), dtype=torch.long, device=dev)
     seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)
-    if decoder_input_ids is not None:
+    steps = 0
+    if decoder_input_ids is not None and dec_pad is None:
         prompt = decoder_input_ids.to(dev)
         labels[:, :P] = prompt
         tok.copy_(prompt[:, P - 1])
         if P > 1:
             decode_chunk(model, state, prompt[:, :P - 1], logits="none")
-    steps = 0
+    elif dec_pad is not None:
+        # ragged prompts: every row's whole prompt in ONE chunk step, its first new token from the logits at its own last prompt
+        # row; from here on row b sits at column P_b + steps, which the step reads from cache_seqlens on the device
+        prompt = decoder_input_ids.to(dev).masked_fill(~dec_pad.mask, 0)
+        labels[:, :P] = prompt
+    if dec_pad is not None and int(max_length) >= 1:
+        pick(decode_chunk(model, state, prompt, logits="last", chunk_seqlens=dec_pad.lengths_dev), state, tok, labels, seen_eos)
+        steps = 1
+    # (the prefill's token is a step like the others: the same stop check, one host read)
+    left = 0 if (steps and bool(seen_eos.all())) else int(max_length) - steps
     g = None
     try:
-        for _ in range(int(max_length)):
+        for _ in range(left):
             if g is not None:
                 g.replay()
             else:
@@ -395,6 +601,8 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
                 g = _capture(model, state, tok, labels, seen_eos, step)
     finally:
         del g
+    if dec_pad is not None and steps:  # (each row ends at its own last column: P_b + steps - 1)
+        return finish_labels(labels[:, :steps + P], last=dec_pad.lengths_dev.long() + (steps - 1))
     return finish_labels(labels[:, :steps + P])
 
 

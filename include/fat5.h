@@ -431,9 +431,16 @@ int fat5_attn_decode(const fat5_decode_params* p, void* hip_stream);
  * The grid, the split count and the workspace size depend on B, H, M, capacity and num_splits only, so a captured graph stays valid
  * while the lengths grow.  All merges run in a fixed order without float atomics: results are bitwise identical run to run.
  * M = 1 means what fat5_attn_decode means.  There are no cache maps here (cache_batch_idx / cache_row_batch).
+ *   Ragged chunks.  chunk_seqlens (optional, (B,) int32 on the device): batch element b brings m_b = clamp(chunk_seqlens[b], 0, M)
+ *                rows of the chunk, and m_b stands for M in the rules above: a_b = min(m_b, capacity - len_b) rows are appended at
+ *                len_b .. len_b + a_b - 1, without an append p_i = L_b - m_b + i, query rows i >= m_b give o = 0 and lse = -inf,
+ *                new rows i >= m_b are neither read nor appended, and no cache row at or past len_b + m_b is written.  The lengths
+ *                are read and clamped on the device, so no value of them (or of cache_seqlens) leads to an access outside the
+ *                caches, and the grid, the split count and the workspace do not depend on them: a captured graph stays valid while
+ *                they change.  NULL: m_b = M for every b, the same kernels, grid and workspace as before the field existed.
  * Rejected with FAT5_EINVAL before anything is launched: D outside {64, 128}, dtype outside {FAT5_F16, FAT5_BF16}, B / H out of range,
  * M outside [1, 1024], a negative capacity, N outside [0, capacity] without lengths, num_splits outside [0, 128], a radius outside
- * 1..2048 or a NULL rpe1d with RPE1D, exactly one of k_new / v_new, an append without cache_seqlens, a non-finite sm_scale,
+ * 1..2048 or a NULL rpe1d with RPE1D, a misaligned chunk_seqlens, exactly one of k_new / v_new, an append without cache_seqlens, a non-finite sm_scale,
  * NULL / misaligned pointers or strides; FAT5_EWORKSPACE when the workspace is missing, misaligned or smaller than
  * fat5_attn_decode_chunk_workspace_bytes().
  */
@@ -459,6 +466,7 @@ typedef struct fat5_decode_chunk_params {
   int32_t num_splits;         /* key-range splits per tile of query rows, 1..128; 0 = the library's choice from B, H, M, capacity */
   void* workspace;            /* fat5_attn_decode_chunk_workspace_bytes(); 16-byte aligned; may be NULL when that is 0 */
   size_t workspace_bytes;
+  const int32_t* chunk_seqlens; /* (B,) int32 device array of rows per batch element, each clamped to [0, M]; NULL: M for every b */
 } fat5_decode_chunk_params;
 /* sizeof(fat5_decode_chunk_params) as compiled into the library (bindings check their mirror against it). */
 size_t fat5_sizeof_decode_chunk_params(void);
