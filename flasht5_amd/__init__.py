@@ -26,7 +26,7 @@ from .rotary import (apply_rotary_emb, apply_rotary_emb_qkv, apply_rotary_emb_pa
 from .positional_encoding import (relative_position_bucket, compute_bias, rpe1d_from_table,  # noqa: E402
                                   RelativePositionalEncoding)
 
-from .decode import flash_attn_with_kvcache, flash_attn_with_kvcache_chunk  # noqa: E402
+from .decode import flash_attn_with_kvcache, flash_attn_with_kvcache_chunk, quantize_kv  # noqa: E402
 from .sampling import sample_logits  # noqa: E402
 from .logits_process import process_logits  # noqa: E402
 from .speculative import speculative_accept, speculative_round  # noqa: E402

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libfat5" + ("_" + _VAR if _VAR else "") +
 
 FAT5_F32, FAT5_F16, FAT5_BF16 = 0, 1, 2
 BIAS_NONE, BIAS_DENSE, BIAS_RPE1D = 0, 1, 2
+KV_NATIVE, KV_FP8_E4M3 = 0, 1  # fat5_kv_cache_dtype
 MAX_RPE_RADIUS = 1024  # forward alone takes 2048; the backward's per-wave diagonal accumulators must fit LDS (include/fat5.h)
 
 _DT = {torch.float32: FAT5_F32, torch.float16: FAT5_F16, torch.bfloat16: FAT5_BF16}
@@ -87,6 +88,17 @@ class DecodeParams(ctypes.Structure):
     ]
 
 
+class DecodeKV8Params(ctypes.Structure):
+    """Mirror of `fat5_decode_kv8_params` (include/fat5.h): `fat5_decode_params` followed by the FP8-cache fields.  The fields of
+    `base` are reachable on the instance itself (`p.B` is `p.base.B`)."""
+    _anonymous_ = ("base",)
+    _fields_ = [
+        ("base", DecodeParams),
+        ("cache_dtype", ctypes.c_int32), ("k_scale", ctypes.c_void_p), ("v_scale", ctypes.c_void_p),
+        ("k_scale_stride", c_i64x3), ("v_scale_stride", c_i64x3),
+    ]
+
+
 class DecodeChunkParams(ctypes.Structure):
     """Mirror of `fat5_decode_chunk_params` (include/fat5.h) -- field order must match exactly."""
     _fields_ = [
@@ -99,6 +111,17 @@ class DecodeChunkParams(ctypes.Structure):
         ("k_new_stride", c_i64x3), ("v_new_stride", c_i64x3), ("o_stride", c_i64x3),
         ("num_splits", ctypes.c_int32), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
         ("chunk_seqlens", ctypes.c_void_p),
+        ("cache_dtype", ctypes.c_int32), ("k_scale", ctypes.c_void_p), ("v_scale", ctypes.c_void_p),
+        ("k_scale_stride", c_i64x3), ("v_scale_stride", c_i64x3),
+    ]
+
+
+class KvQuantParams(ctypes.Structure):
+    """Mirror of `fat5_kv_quant_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("L", ctypes.c_int32), ("H", ctypes.c_int32), ("D", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("out", ctypes.c_void_p), ("scale", ctypes.c_void_p),
+        ("x_stride", c_i64x3), ("out_stride", c_i64x3), ("scale_stride", c_i64x3),
     ]
 
 
@@ -159,11 +182,13 @@ EXPORTS = (
     "fat5_rope_apply", "fat5_sizeof_rope_params",
     "fat5_fire_fwd", "fat5_fire_bwd", "fat5_fire_bwd_workspace_bytes", "fat5_sizeof_fire_params",
     "fat5_attn_decode", "fat5_attn_decode_workspace_bytes", "fat5_sizeof_decode_params",
+    "fat5_attn_decode_kv8", "fat5_sizeof_decode_kv8_params",
     "fat5_attn_decode_chunk", "fat5_attn_decode_chunk_workspace_bytes", "fat5_sizeof_decode_chunk_params",
     "fat5_sample_logits", "fat5_sizeof_sample_params",
     "fat5_beam_step", "fat5_beam_step_workspace_bytes", "fat5_sizeof_beam_params",
     "fat5_process_logits", "fat5_sizeof_logits_params",
     "fat5_spec_accept", "fat5_spec_accept_workspace_bytes", "fat5_sizeof_spec_params",
+    "fat5_kv_quantize", "fat5_sizeof_kv_quant_params",
 )
 
 _lib = None
@@ -259,6 +284,12 @@ def load():
     if lib.fat5_sizeof_decode_params() != ctypes.sizeof(DecodeParams):
         raise ImportError(f"fat5_decode_params layout mismatch: library {lib.fat5_sizeof_decode_params()} B, "
                           f"binding {ctypes.sizeof(DecodeParams)} B")
+    lib.fat5_attn_decode_kv8.restype = ctypes.c_int
+    lib.fat5_attn_decode_kv8.argtypes = [ctypes.POINTER(DecodeKV8Params), ctypes.c_void_p]
+    lib.fat5_sizeof_decode_kv8_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_decode_kv8_params() != ctypes.sizeof(DecodeKV8Params):
+        raise ImportError(f"fat5_decode_kv8_params layout mismatch: library {lib.fat5_sizeof_decode_kv8_params()} B, "
+                          f"binding {ctypes.sizeof(DecodeKV8Params)} B")
     lib.fat5_attn_decode_chunk.restype = ctypes.c_int
     lib.fat5_attn_decode_chunk.argtypes = [ctypes.POINTER(DecodeChunkParams), ctypes.c_void_p]
     lib.fat5_attn_decode_chunk_workspace_bytes.restype = ctypes.c_size_t
@@ -295,6 +326,12 @@ def load():
     if lib.fat5_sizeof_spec_params() != ctypes.sizeof(SpecParams):
         raise ImportError(f"fat5_spec_params layout mismatch: library {lib.fat5_sizeof_spec_params()} B, "
                           f"binding {ctypes.sizeof(SpecParams)} B")
+    lib.fat5_kv_quantize.restype = ctypes.c_int
+    lib.fat5_kv_quantize.argtypes = [ctypes.POINTER(KvQuantParams), ctypes.c_void_p]
+    lib.fat5_sizeof_kv_quant_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_kv_quant_params() != ctypes.sizeof(KvQuantParams):
+        raise ImportError(f"fat5_kv_quant_params layout mismatch: library {lib.fat5_sizeof_kv_quant_params()} B, "
+                          f"binding {ctypes.sizeof(KvQuantParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

@@ -176,7 +176,7 @@ class FlashT5Attention(nn.Module):
             raise NotImplementedError(f"position_encoding_type {self.position_encoding_type!r} at decode time")
 
     def forward_decode(self, hidden_states, k_cache, v_cache, cache_seqlens=None, position_bias=None, position=None,
-                       cache_batch_idx=None, cache_row_batch=None, cross_seqlens=None, chunk_seqlens=None):
+                       cache_batch_idx=None, cache_row_batch=None, cross_seqlens=None, chunk_seqlens=None, k_scale=None, v_scale=None):
         """One new token through this layer against a KV cache (flasht5_amd.decode.flash_attn_with_kvcache); returns (B, 1, d_model).
 
         Self-attention (`cache_seqlens` given): q, k and v are projected from `hidden_states` (B, 1, d_model), k and v are appended
@@ -195,13 +195,15 @@ class FlashT5Attention(nn.Module):
 
         Padding: `cross_seqlens` (B,) int32 (cross-attention only) is the number of valid encoder keys of each query row -- the
         kernels' cache_seqlens without an append; with `cache_batch_idx` it is per query row, not per cache row.  `chunk_seqlens`
-        (B,) int32 (chunks only): the rows of the chunk each batch element brings (flash_attn_with_kvcache_chunk)."""
+        (B,) int32 (chunks only): the rows of the chunk each batch element brings (flash_attn_with_kvcache_chunk).
+
+        FP8 caches: `k_scale` / `v_scale` (B, L_cap, H) fp32, the scales of float8_e4m3fn caches (decode.py); None: 16-bit caches."""
         self.decode_supported()
         from .decode import flash_attn_with_kvcache
         B, M = hidden_states.shape[:2]
         if M > 1:
             return self._forward_decode_chunk(hidden_states, k_cache, v_cache, cache_seqlens, position_bias, position,
-                                              cache_batch_idx, cache_row_batch, cross_seqlens, chunk_seqlens)
+                                              cache_batch_idx, cache_row_batch, cross_seqlens, chunk_seqlens, k_scale, v_scale)
         if chunk_seqlens is not None:
             raise ValueError("forward_decode: chunk_seqlens needs a chunk of M > 1 rows")
         if cross_seqlens is not None and cache_seqlens is not None:
@@ -229,12 +231,13 @@ class FlashT5Attention(nn.Module):
             rpe1d, radius = position_bias
             if self.attention_type == "triton":  # (the dense path adds the bias after a cast to the activation dtype)
                 rpe1d = rpe1d.to(q.dtype).float()
+        fp8 = {} if k_scale is None else dict(k_scale=k_scale, v_scale=v_scale)
         out = flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens if is_self else cross_seqlens, self.softmax_scale,
-                                      rpe1d, radius, cache_batch_idx=cache_batch_idx, cache_row_batch=cache_row_batch)
+                                      rpe1d, radius, cache_batch_idx=cache_batch_idx, cache_row_batch=cache_row_batch, **fp8)
         return self.o(out.reshape(B, 1, self.inner_dim))
 
     def _forward_decode_chunk(self, hidden_states, k_cache, v_cache, cache_seqlens, position_bias, position, cache_batch_idx,
-                              cache_row_batch, cross_seqlens=None, chunk_seqlens=None):
+                              cache_row_batch, cross_seqlens=None, chunk_seqlens=None, k_scale=None, v_scale=None):
         """forward_decode for M > 1 rows: the same projections, rotation and bias rule on the chunk kernel"""
         from .decode import flash_attn_with_kvcache_chunk
         if cache_batch_idx is not None or cache_row_batch is not None:
@@ -267,7 +270,10 @@ class FlashT5Attention(nn.Module):
             if self.attention_type == "triton":  # (the dense path adds the bias after a cast to the activation dtype)
                 rpe1d = rpe1d.to(q.dtype).float()
         lens = cache_seqlens if is_self else cross_seqlens
-        if chunk_seqlens is None:
+        if k_scale is not None:
+            out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, lens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
+                                                rpe_radius=radius, chunk_seqlens=chunk_seqlens, k_scale=k_scale, v_scale=v_scale)
+        elif chunk_seqlens is None:
             out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, lens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
                                                 rpe_radius=radius)
         else:

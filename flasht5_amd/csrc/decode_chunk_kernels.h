@@ -34,6 +34,11 @@
 // row-group order and the split merge through the fp32 workspace in split order (chunk_combine_kernel).  A query row that has no
 // visible key in a step keeps its running maximum at -inf; the step then subtracts 0 instead of that maximum, so exp2(-inf - (-inf))
 // is never formed and the row's state stays (max -inf, sum 0, acc 0).
+//
+// FP8 caches (the KV8 instantiation; decode_kernels.h states the reads, kv_quant_kernels.h the storage contract).  Cache rows are 8
+// bytes per lane plus the row's two scales; a key row j >= len_b still comes from k_new / v_new, and every workgroup that reads it
+// quantises it in registers and attends the quantised row read back -- the rule is a function of the row alone, so all readers see
+// the values that split 0 of the row's tile writes (bytes and scales).  Without KV8 nothing here is compiled in.
 #pragma once
 #include "decode_kernels.h"
 
@@ -57,9 +62,12 @@ struct ChunkArgs {
   int64_t q_s[3], o_s[3], kn_s[3], vn_s[3], kc_s[3], vc_s[3];
   int32_t B, H, M, cap, N, R, splits, causal;
   float scale_log2;       // sm_scale * log2(e)
+  float* ks;              // KV8 only: (B, cap, H) fp32 scales of the K cache rows, element strides ks_s = [b, l, h]
+  float* vs;
+  int64_t ks_s[3], vs_s[3];
 };
 
-template <int DT, int D, bool APPEND, bool BIAS, bool DIRECT>
+template <int DT, int D, bool APPEND, bool BIAS, bool DIRECT, bool KV8 = false>
 __global__ __launch_bounds__(DEC_THREADS) void chunk_attn_kernel(ChunkArgs a) {
   typedef Elem<DT> E;
   typedef typename E::T T;
@@ -94,8 +102,11 @@ __global__ __launch_bounds__(DEC_THREADS) void chunk_attn_kernel(ChunkArgs a) {
   const int lo = min(kend, split * chunk), hi = min(kend, lo + chunk);
 
   const T* qbase = reinterpret_cast<const T*>(a.q) + (int64_t)b * a.q_s[0] + (int64_t)h * a.q_s[2] + t * 8;
-  const T* kbase = reinterpret_cast<const T*>(a.kc) + (int64_t)b * a.kc_s[0] + (int64_t)h * a.kc_s[2] + t * 8;
-  const T* vbase = reinterpret_cast<const T*>(a.vc) + (int64_t)b * a.vc_s[0] + (int64_t)h * a.vc_s[2] + t * 8;
+  typedef typename std::conditional<KV8, uint8_t, T>::type C;   // a cache element
+  const C* kbase = reinterpret_cast<const C*>(a.kc) + (int64_t)b * a.kc_s[0] + (int64_t)h * a.kc_s[2] + t * 8;
+  const C* vbase = reinterpret_cast<const C*>(a.vc) + (int64_t)b * a.vc_s[0] + (int64_t)h * a.vc_s[2] + t * 8;
+  float* ksbase = KV8 ? a.ks + (int64_t)b * a.ks_s[0] + (int64_t)h * a.ks_s[2] : nullptr;
+  float* vsbase = KV8 ? a.vs + (int64_t)b * a.vs_s[0] + (int64_t)h * a.vs_s[2] : nullptr;
   const T* knbase = APPEND ? reinterpret_cast<const T*>(a.kn) + (int64_t)b * a.kn_s[0] + (int64_t)h * a.kn_s[2] + t * 8 : nullptr;
   const T* vnbase = APPEND ? reinterpret_cast<const T*>(a.vn) + (int64_t)b * a.vn_s[0] + (int64_t)h * a.vn_s[2] + t * 8 : nullptr;
   const float* bias_row = BIAS ? a.rpe1d + (int64_t)h * (2 * a.R + 1) + a.R : nullptr;
@@ -103,11 +114,26 @@ __global__ __launch_bounds__(DEC_THREADS) void chunk_attn_kernel(ChunkArgs a) {
   // the tile's new rows go into the cache by split 0 of the tile (they are read from k_new / v_new everywhere, never from the cache)
   if (APPEND && split == 0 && tid < TQ * TPR) {
     const int i = i0 + g;   // (tid / TPR < TQ)
-    if (i < napp) {
-      *reinterpret_cast<u32x4*>(const_cast<T*>(kbase) + (int64_t)(len + i) * a.kc_s[1]) =
-          *reinterpret_cast<const u32x4*>(knbase + (int64_t)i * a.kn_s[1]);
-      *reinterpret_cast<u32x4*>(const_cast<T*>(vbase) + (int64_t)(len + i) * a.vc_s[1]) =
-          *reinterpret_cast<const u32x4*>(vnbase + (int64_t)i * a.vn_s[1]);
+    if (i < napp) {   // (i depends on g alone: whole lane groups are here)
+      if constexpr (KV8) {
+        float f[8];
+        uint2 pk;
+        E::load(knbase + (int64_t)i * a.kn_s[1], f);
+        const float sk = kv8_quant_row<TPR>(f, pk);
+        *reinterpret_cast<uint2*>(const_cast<C*>(kbase) + (int64_t)(len + i) * a.kc_s[1]) = pk;
+        E::load(vnbase + (int64_t)i * a.vn_s[1], f);
+        const float sv = kv8_quant_row<TPR>(f, pk);
+        *reinterpret_cast<uint2*>(const_cast<C*>(vbase) + (int64_t)(len + i) * a.vc_s[1]) = pk;
+        if (t == 0) {
+          ksbase[(int64_t)(len + i) * a.ks_s[1]] = sk;
+          vsbase[(int64_t)(len + i) * a.vs_s[1]] = sv;
+        }
+      } else {
+        *reinterpret_cast<u32x4*>(const_cast<C*>(kbase) + (int64_t)(len + i) * a.kc_s[1]) =
+            *reinterpret_cast<const u32x4*>(knbase + (int64_t)i * a.kn_s[1]);
+        *reinterpret_cast<u32x4*>(const_cast<C*>(vbase) + (int64_t)(len + i) * a.vc_s[1]) =
+            *reinterpret_cast<const u32x4*>(vnbase + (int64_t)i * a.vn_s[1]);
+      }
     }
   }
 
@@ -122,12 +148,31 @@ __global__ __launch_bounds__(DEC_THREADS) void chunk_attn_kernel(ChunkArgs a) {
 
   for (int j0 = lo + g; j0 < hi; j0 += G * U) {
     float kf[U][8], vf[U][8];
+    float ksc[KV8 ? U : 1], vsc[KV8 ? U : 1];   // KV8: the rows' scales
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int j = j0 + u * G;
 #pragma unroll
       for (int c = 0; c < 8; ++c) kf[u][c] = vf[u][c] = 0.f;
-      if (j < hi) {
+      if constexpr (KV8) {
+        ksc[u] = vsc[u] = 0.f;
+        if (j < hi) {
+          uint2 kb, vb;
+          if (APPEND && j >= len) {   // (the whole lane group is here: j depends on g alone)
+            E::load(knbase + (int64_t)(j - len) * a.kn_s[1], kf[u]);
+            E::load(vnbase + (int64_t)(j - len) * a.vn_s[1], vf[u]);
+            ksc[u] = kv8_quant_row<TPR>(kf[u], kb);
+            vsc[u] = kv8_quant_row<TPR>(vf[u], vb);
+          } else {
+            kb = *reinterpret_cast<const uint2*>(kbase + (int64_t)j * a.kc_s[1]);
+            vb = *reinterpret_cast<const uint2*>(vbase + (int64_t)j * a.vc_s[1]);
+            ksc[u] = ksbase[(int64_t)j * a.ks_s[1]];
+            vsc[u] = vsbase[(int64_t)j * a.vs_s[1]];
+          }
+          kv8_decode8(kb, kf[u]);
+          kv8_decode8(vb, vf[u]);
+        }
+      } else if (j < hi) {
         if (APPEND && j >= len) {
           E::load(knbase + (int64_t)(j - len) * a.kn_s[1], kf[u]);
           E::load(vnbase + (int64_t)(j - len) * a.vn_s[1], vf[u]);
@@ -147,6 +192,7 @@ __global__ __launch_bounds__(DEC_THREADS) void chunk_attn_kernel(ChunkArgs a) {
         for (int c = 0; c < 8; ++c) d = fmaf(qf[r][c], kf[u][c], d);
 #pragma unroll
         for (int off = TPR / 2; off >= 1; off >>= 1) d += __shfl_xor(d, off, 64);
+        if constexpr (KV8) d *= ksc[u];
         const int j = j0 + u * G;
         const bool seen = j < hi && j <= lim[r];
         float sv = d * a.scale_log2;
@@ -171,8 +217,9 @@ __global__ __launch_bounds__(DEC_THREADS) void chunk_attn_kernel(ChunkArgs a) {
       for (int u = 0; u < U; ++u) {
         const float p = fast_exp2(s[u] - mref);
         l[r] += p;
+        const float pv = KV8 ? p * vsc[u] : p;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) acc[r][c] = fmaf(p, vf[u][c], acc[r][c]);
+        for (int c = 0; c < 8; ++c) acc[r][c] = fmaf(pv, vf[u][c], acc[r][c]);
       }
       m[r] = mx;
     }

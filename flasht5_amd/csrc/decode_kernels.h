@@ -25,10 +25,21 @@
 // history as a table of parents instead of a reordered cache); the appended row is still read from k_new / v_new and written to
 // batch element b.  Every map entry is clamped to [0, cacheB), as the lengths are clamped.  Without maps the code and the bits are
 // those of the plain kernel (cb = b).
+//
+// FP8 caches (the KV8 instantiation; the storage contract is at the head of kv_quant_kernels.h).  The caches hold e4m3fn bytes, one
+// fp32 scale per (batch element, row, head) beside them in ks / vs (element strides ks_s / vs_s = [b, l, h]).  The lane layout is
+// the same: a lane reads the 8 bytes of its 8 elements, converts them to fp32 (exact), and the row's K scale multiplies the finished
+// dot product, its V scale the softmax weight that goes into acc[] (the sum l takes the unscaled weight).  A scale is fetched from the
+// batch element its row is fetched from (cache_batch_idx, cache_row_batch).  The appended row is quantised in registers by the lane
+// group that owns it -- amax by shuffles, kv8_quant_row -- and what that group attends is the quantised row read back, not k_new /
+// v_new: the output is a function of the cache contents after the call.  The same group writes the row's bytes and scales.
+// Without KV8 nothing here is compiled in: the code and the bits are those of the kernel before the parameter existed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "rowwise_kernels.h"
+#include "kv_quant_kernels.h"
 
 namespace fat5 {
 
@@ -54,6 +65,9 @@ struct DecodeArgs {
   int32_t B, H, cap, N, R, splits;
   int32_t cacheB;         // batch elements of the caches (map entries are clamped to [0, cacheB))
   float scale_log2;       // sm_scale * log2(e)
+  float* ks;              // KV8 only: (cacheB, cap, H) fp32 scales of the K cache rows, element strides ks_s = [b, l, h]
+  float* vs;
+  int64_t ks_s[3], vs_s[3];
 };
 
 FAT5_DEV int decode_clamp_batch(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
@@ -66,7 +80,7 @@ FAT5_DEV int decode_len(const DecodeArgs& a, int b, bool append, bool& do_append
   return do_append ? len + 1 : len;
 }
 
-template <int DT, int D, bool APPEND, bool BIAS, bool DIRECT, bool ROWMAP = false>
+template <int DT, int D, bool APPEND, bool BIAS, bool DIRECT, bool ROWMAP = false, bool KV8 = false>
 __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) {
   typedef Elem<DT> E;
   typedef typename E::T T;
@@ -86,8 +100,11 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) 
   float qf[8];
   E::load(reinterpret_cast<const T*>(a.q) + (int64_t)b * a.q_sb + (int64_t)h * a.q_sh + t * 8, qf);
   const int cb = a.bidx ? decode_clamp_batch(a.bidx[b], a.cacheB) : b;  // (never with an append: rejected on the host)
-  const T* kbase = reinterpret_cast<const T*>(a.kc) + (int64_t)cb * a.kc_s[0] + (int64_t)h * a.kc_s[2] + t * 8;
-  const T* vbase = reinterpret_cast<const T*>(a.vc) + (int64_t)cb * a.vc_s[0] + (int64_t)h * a.vc_s[2] + t * 8;
+  typedef typename std::conditional<KV8, uint8_t, T>::type C;   // a cache element
+  const C* kbase = reinterpret_cast<const C*>(a.kc) + (int64_t)cb * a.kc_s[0] + (int64_t)h * a.kc_s[2] + t * 8;
+  const C* vbase = reinterpret_cast<const C*>(a.vc) + (int64_t)cb * a.vc_s[0] + (int64_t)h * a.vc_s[2] + t * 8;
+  const float* ksbase = KV8 ? a.ks + (int64_t)cb * a.ks_s[0] + (int64_t)h * a.ks_s[2] : nullptr;
+  const float* vsbase = KV8 ? a.vs + (int64_t)cb * a.vs_s[0] + (int64_t)h * a.vs_s[2] : nullptr;
   const int32_t* rmap = ROWMAP ? a.rowmap + (int64_t)b * a.cap : nullptr;
   const float* bias_row = BIAS ? a.rpe1d + (int64_t)h * (2 * a.R + 1) + a.R : nullptr;
 
@@ -97,12 +114,32 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) 
 
   for (int j0 = lo + g; j0 < hi; j0 += G * DEC_UNROLL) {
     float kf[DEC_UNROLL][8], vf[DEC_UNROLL][8], s[DEC_UNROLL];
+    float ksc[KV8 ? DEC_UNROLL : 1], vsc[KV8 ? DEC_UNROLL : 1];   // KV8: the rows' scales
 #pragma unroll
     for (int u = 0; u < DEC_UNROLL; ++u) {
       const int j = j0 + u * G;
 #pragma unroll
       for (int c = 0; c < 8; ++c) kf[u][c] = vf[u][c] = 0.f;
-      if (j < hi) {
+      if constexpr (KV8) {
+        ksc[u] = vsc[u] = 0.f;
+        if (j < hi) {
+          uint2 kb, vb;
+          if (APPEND && j == pnew) {   // (the whole lane group is here: j depends on g alone)
+            E::load(reinterpret_cast<const T*>(a.kn) + (int64_t)b * a.kn_sb + (int64_t)h * a.kn_sh + t * 8, kf[u]);
+            E::load(reinterpret_cast<const T*>(a.vn) + (int64_t)b * a.vn_sb + (int64_t)h * a.vn_sh + t * 8, vf[u]);
+            ksc[u] = kv8_quant_row<TPR>(kf[u], kb);
+            vsc[u] = kv8_quant_row<TPR>(vf[u], vb);
+          } else {
+            const int64_t db = ROWMAP ? (int64_t)(decode_clamp_batch(rmap[j], a.cacheB) - b) : 0;
+            kb = *reinterpret_cast<const uint2*>(kbase + db * a.kc_s[0] + (int64_t)j * a.kc_s[1]);
+            vb = *reinterpret_cast<const uint2*>(vbase + db * a.vc_s[0] + (int64_t)j * a.vc_s[1]);
+            ksc[u] = ksbase[db * a.ks_s[0] + (int64_t)j * a.ks_s[1]];
+            vsc[u] = vsbase[db * a.vs_s[0] + (int64_t)j * a.vs_s[1]];
+          }
+          kv8_decode8(kb, kf[u]);
+          kv8_decode8(vb, vf[u]);
+        }
+      } else if (j < hi) {
         if (APPEND && j == pnew) {
           E::load(reinterpret_cast<const T*>(a.kn) + (int64_t)b * a.kn_sb + (int64_t)h * a.kn_sh + t * 8, kf[u]);
           E::load(reinterpret_cast<const T*>(a.vn) + (int64_t)b * a.vn_sb + (int64_t)h * a.vn_sh + t * 8, vf[u]);
@@ -124,6 +161,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) 
 #pragma unroll
       for (int off = TPR / 2; off >= 1; off >>= 1) d += __shfl_xor(d, off, 64);
       const int j = j0 + u * G;
+      if constexpr (KV8) d *= ksc[u];
       float sv = d * a.scale_log2;
       if constexpr (BIAS) {
         if (j < hi) {
@@ -145,8 +183,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) 
     for (int u = 0; u < DEC_UNROLL; ++u) {
       const float p = fast_exp2(s[u] - mx);
       l += p;
+      const float pv = KV8 ? p * vsc[u] : p;
 #pragma unroll
-      for (int c = 0; c < 8; ++c) acc[c] = fmaf(p, vf[u][c], acc[c]);
+      for (int c = 0; c < 8; ++c) acc[c] = fmaf(pv, vf[u][c], acc[c]);
     }
     m = mx;
   }
@@ -154,8 +193,23 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) 
   // the appended row goes into the cache by the lanes that read it (rows >= L are never read, so no other workgroup can see it)
   if (APPEND && app && pnew >= lo && pnew < hi && g == (pnew - lo) % G) {
     const int64_t kofs = (int64_t)b * a.kn_sb + (int64_t)h * a.kn_sh + t * 8, vofs = (int64_t)b * a.vn_sb + (int64_t)h * a.vn_sh + t * 8;
-    *reinterpret_cast<u32x4*>(const_cast<T*>(kbase) + (int64_t)pnew * a.kc_s[1]) = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(a.kn) + kofs);
-    *reinterpret_cast<u32x4*>(const_cast<T*>(vbase) + (int64_t)pnew * a.vc_s[1]) = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(a.vn) + vofs);
+    if constexpr (KV8) {   // quantised again from k_new / v_new (the rule is deterministic: the bytes the loop above attended)
+      float f[8];
+      uint2 pk;
+      E::load(reinterpret_cast<const T*>(a.kn) + kofs, f);
+      const float sk = kv8_quant_row<TPR>(f, pk);
+      *reinterpret_cast<uint2*>(const_cast<C*>(kbase) + (int64_t)pnew * a.kc_s[1]) = pk;
+      E::load(reinterpret_cast<const T*>(a.vn) + vofs, f);
+      const float sv = kv8_quant_row<TPR>(f, pk);
+      *reinterpret_cast<uint2*>(const_cast<C*>(vbase) + (int64_t)pnew * a.vc_s[1]) = pk;
+      if (t == 0) {
+        const_cast<float*>(ksbase)[(int64_t)pnew * a.ks_s[1]] = sk;
+        const_cast<float*>(vsbase)[(int64_t)pnew * a.vs_s[1]] = sv;
+      }
+    } else {
+      *reinterpret_cast<u32x4*>(const_cast<C*>(kbase) + (int64_t)pnew * a.kc_s[1]) = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(a.kn) + kofs);
+      *reinterpret_cast<u32x4*>(const_cast<C*>(vbase) + (int64_t)pnew * a.vc_s[1]) = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(a.vn) + vofs);
+    }
   }
 
   // merge the G row groups in row-group order

@@ -951,8 +951,55 @@ int fat5_fire_bwd(const fat5_fire_params* p, void* workspace, size_t workspace_b
   return FAT5_OK;
 }
 
+// ---- FP8 KV cache: the row quantiser (kv_quant_kernels.h) ----
+size_t fat5_sizeof_kv_quant_params(void) { return sizeof(fat5_kv_quant_params); }
+
+int fat5_kv_quantize(const fat5_kv_quant_params* p, void* stream_) {
+  const char* what = "kv_quantize";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (p->D != 64 && p->D != 128) return fail(FAT5_EINVAL, "%s: head_dim %d (64 or 128)", what, p->D);
+  if (p->dtype != FAT5_F16 && p->dtype != FAT5_BF16) return fail(FAT5_EINVAL, "%s: dtype %d (FAT5_F16 or FAT5_BF16)", what, p->dtype);
+  if (p->B < 0 || p->L < 0 || p->H < 0) return fail(FAT5_EINVAL, "%s: B %d / L %d / H %d", what, p->B, p->L, p->H);
+  const int64_t rows = (int64_t)p->B * p->L * p->H;   // (< 2^93 / 2^31 ... three int32 factors: checked against the grid below)
+  const int G = KVQ_THREADS / (p->D / 8);
+  if ((double)p->B * p->L * p->H > 2147483647.0 * G) return fail(FAT5_EINVAL, "%s: %d x %d x %d rows exceed one launch", what, p->B, p->L, p->H);
+  if (rows == 0) return FAT5_OK;
+  if (!p->x || !aligned16(p->x)) return fail(FAT5_EINVAL, "%s: x: null or unaligned pointer (16-byte aligned base)", what);
+  if (!p->out || (reinterpret_cast<uintptr_t>(p->out) & 7)) return fail(FAT5_EINVAL, "%s: out: null or unaligned pointer (8-byte aligned base)", what);
+  if (!p->scale || (reinterpret_cast<uintptr_t>(p->scale) & 3)) return fail(FAT5_EINVAL, "%s: scale: null or unaligned pointer", what);
+  for (int i = 0; i < 3; ++i)
+    if (p->x_stride[i] % 8 || p->out_stride[i] % 8)
+      return fail(FAT5_EINVAL, "%s: x and out strides must be multiples of 8 elements (innermost stride 1)", what);
+  KvQuantArgs a = {};
+  a.x = p->x, a.out = static_cast<uint8_t*>(p->out), a.scale = p->scale;
+  for (int i = 0; i < 3; ++i) a.x_s[i] = p->x_stride[i], a.o_s[i] = p->out_stride[i], a.s_s[i] = p->scale_stride[i];
+  a.rows = rows, a.L = p->L, a.H = p->H;
+  const dim3 grid((unsigned)((rows + G - 1) / G));
+  hipStream_t stream = (hipStream_t)stream_;
+  if (p->dtype == FAT5_F16) {
+    if (p->D == 64) hipLaunchKernelGGL((kv_quantize_kernel<FAT5_F16, 64>), grid, dim3(KVQ_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((kv_quantize_kernel<FAT5_F16, 128>), grid, dim3(KVQ_THREADS), 0, stream, a);
+  } else {
+    if (p->D == 64) hipLaunchKernelGGL((kv_quantize_kernel<FAT5_BF16, 64>), grid, dim3(KVQ_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((kv_quantize_kernel<FAT5_BF16, 128>), grid, dim3(KVQ_THREADS), 0, stream, a);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "kv_quantize launch");
+  return FAT5_OK;
+}
+
+// the FP8-cache fields of both decode descriptors: a known cache dtype, and in FP8 mode both scale tensors
+static int kv8_check(const char* what, int32_t cache_dtype, const float* ks, const float* vs) {
+  if (cache_dtype != FAT5_KV_NATIVE && cache_dtype != FAT5_KV_FP8_E4M3)
+    return fail(FAT5_EINVAL, "%s: cache_dtype %d (FAT5_KV_NATIVE or FAT5_KV_FP8_E4M3)", what, cache_dtype);
+  if (cache_dtype == FAT5_KV_FP8_E4M3 && (!ks || !vs || (reinterpret_cast<uintptr_t>(ks) & 3) || (reinterpret_cast<uintptr_t>(vs) & 3)))
+    return fail(FAT5_EINVAL, "%s: an FP8 cache needs k_scale and v_scale (fp32, aligned)", what);
+  return FAT5_OK;
+}
+
 // ---- decode attention against a KV cache (decode_kernels.h) ----
 size_t fat5_sizeof_decode_params(void) { return sizeof(fat5_decode_params); }
+size_t fat5_sizeof_decode_kv8_params(void) { return sizeof(fat5_decode_kv8_params); }
 
 // key-range splits per (b, h) from host-known arguments only: enough workgroups for two per CU of a 256-CU chip, but no more
 // splits than whole workgroup passes (G * DEC_UNROLL rows) fit into the capacity.  Fixed, not queried from the device: the same
@@ -978,7 +1025,8 @@ size_t fat5_attn_decode_workspace_bytes(const fat5_decode_params* p) {
   return align_up((size_t)p->B * p->H * s * (p->D + 2) * sizeof(float), 16);
 }
 
-static int decode_check(const fat5_decode_params* p) {
+// `kv`: the FP8-cache fields behind the descriptor (fat5_attn_decode_kv8), or NULL (fat5_attn_decode: 16-bit caches)
+static int decode_check(const fat5_decode_params* p, const fat5_decode_kv8_params* kv) {
   const char* what = "attn_decode";
   if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
   if (p->D != 64 && p->D != 128) return fail(FAT5_EINVAL, "%s: head_dim %d (64 or 128)", what, p->D);
@@ -1018,6 +1066,8 @@ static int decode_check(const fat5_decode_params* p) {
   if ((reinterpret_cast<uintptr_t>(p->cache_batch_idx) & 3) || (reinterpret_cast<uintptr_t>(p->cache_row_batch) & 3))
     return fail(FAT5_EINVAL, "%s: cache_batch_idx / cache_row_batch misaligned", what);
   if (p->cache_B < 0) return fail(FAT5_EINVAL, "%s: cache_B %d", what, p->cache_B);
+  if (kv)
+    if (int rc = kv8_check(what, kv->cache_dtype, kv->k_scale, kv->v_scale)) return rc;
   const bool own_rows = !(p->cache_batch_idx || p->cache_row_batch) || (p->cache_row_batch && p->k_new);
   if (own_rows && p->cache_B != 0 && p->cache_B < p->B)
     return fail(FAT5_EINVAL, "%s: cache_B %d < B %d (rows read or written at their own batch element)", what, p->cache_B, p->B);
@@ -1027,25 +1077,30 @@ static int decode_check(const fat5_decode_params* p) {
   return FAT5_OK;
 }
 
-extern "C++" template <int DT, int D, bool APPEND, bool BIAS, bool ROWMAP>
+extern "C++" template <int DT, int D, bool APPEND, bool BIAS, bool ROWMAP, bool KV8>
 static void decode_launch_map(const DecodeArgs& a, hipStream_t stream) {
   const dim3 grid(a.splits, a.H, a.B);
   if (a.splits == 1) {
-    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, true, ROWMAP>), grid, dim3(DEC_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, true, ROWMAP, KV8>), grid, dim3(DEC_THREADS), 0, stream, a);
   } else {
-    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, false, ROWMAP>), grid, dim3(DEC_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((decode_attn_kernel<DT, D, APPEND, BIAS, false, ROWMAP, KV8>), grid, dim3(DEC_THREADS), 0, stream, a);
     hipLaunchKernelGGL((decode_combine_kernel<DT, D>), dim3(a.H, a.B), dim3(D), 0, stream, a);
   }
 }
 
 extern "C++" template <int DT, int D, bool APPEND, bool BIAS>
 static void decode_launch(const DecodeArgs& a, hipStream_t stream) {
-  if (a.rowmap) decode_launch_map<DT, D, APPEND, BIAS, true>(a, stream);
-  else decode_launch_map<DT, D, APPEND, BIAS, false>(a, stream);
+  if (a.ks) {   // FP8 caches
+    if (a.rowmap) decode_launch_map<DT, D, APPEND, BIAS, true, true>(a, stream);
+    else decode_launch_map<DT, D, APPEND, BIAS, false, true>(a, stream);
+  } else {
+    if (a.rowmap) decode_launch_map<DT, D, APPEND, BIAS, true, false>(a, stream);
+    else decode_launch_map<DT, D, APPEND, BIAS, false, false>(a, stream);
+  }
 }
 
-int fat5_attn_decode(const fat5_decode_params* p, void* stream_) {
-  if (int rc = decode_check(p)) return rc;
+static int decode_run(const fat5_decode_params* p, const fat5_decode_kv8_params* kv, void* stream_) {
+  if (int rc = decode_check(p, kv)) return rc;
   DecodeArgs a = {};
   a.q = p->q;
   a.kc = p->k_cache;
@@ -1068,6 +1123,10 @@ int fat5_attn_decode(const fat5_decode_params* p, void* stream_) {
   a.B = p->B, a.H = p->H, a.cap = p->capacity, a.N = p->N, a.R = p->rpe_radius;
   a.splits = decode_splits(p);
   a.scale_log2 = p->sm_scale * kLog2e;
+  if (kv && kv->cache_dtype == FAT5_KV_FP8_E4M3) {
+    a.ks = kv->k_scale, a.vs = kv->v_scale;
+    for (int i = 0; i < 3; ++i) a.ks_s[i] = kv->k_scale_stride[i], a.vs_s[i] = kv->v_scale_stride[i];
+  }
   const bool append = p->k_new != nullptr, bias = a.rpe1d != nullptr;
   hipStream_t stream = (hipStream_t)stream_;
   auto go = [&](auto dt_, auto d_) {
@@ -1090,6 +1149,13 @@ int fat5_attn_decode(const fat5_decode_params* p, void* stream_) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "attn_decode launch");
   return FAT5_OK;
+}
+
+int fat5_attn_decode(const fat5_decode_params* p, void* stream_) { return decode_run(p, nullptr, stream_); }
+
+int fat5_attn_decode_kv8(const fat5_decode_kv8_params* p, void* stream_) {
+  if (!p) return fail(FAT5_EINVAL, "attn_decode: null params");
+  return decode_run(&p->base, p, stream_);
 }
 
 // ---- chunked decode attention: M query rows per (b, h) against a KV cache (decode_chunk_kernels.h) ----
@@ -1156,6 +1222,7 @@ static int chunk_check(const fat5_decode_chunk_params* p) {
       if (e.st[i] % 8) return fail(FAT5_EINVAL, "%s: %s strides must be multiples of 8 elements (innermost stride 1)", what, e.name);
   }
   if (p->lse && (reinterpret_cast<uintptr_t>(p->lse) & 3)) return fail(FAT5_EINVAL, "%s: lse misaligned", what);
+  if (int rc = kv8_check(what, p->cache_dtype, p->k_scale, p->v_scale)) return rc;
   const size_t need = fat5_attn_decode_chunk_workspace_bytes(p);
   if (need && (!p->workspace || !aligned16(p->workspace) || p->workspace_bytes < need))
     return fail(FAT5_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", what, need, p->workspace_bytes);
@@ -1166,9 +1233,11 @@ extern "C++" template <int DT, int D, bool APPEND, bool BIAS>
 static void chunk_launch(const ChunkArgs& a, hipStream_t stream) {
   const dim3 grid(((a.M + CHUNK_TQ - 1) / CHUNK_TQ) * a.splits, a.H, a.B);
   if (a.splits == 1) {
-    hipLaunchKernelGGL((chunk_attn_kernel<DT, D, APPEND, BIAS, true>), grid, dim3(DEC_THREADS), 0, stream, a);
+    if (a.ks) hipLaunchKernelGGL((chunk_attn_kernel<DT, D, APPEND, BIAS, true, true>), grid, dim3(DEC_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((chunk_attn_kernel<DT, D, APPEND, BIAS, true>), grid, dim3(DEC_THREADS), 0, stream, a);
   } else {
-    hipLaunchKernelGGL((chunk_attn_kernel<DT, D, APPEND, BIAS, false>), grid, dim3(DEC_THREADS), 0, stream, a);
+    if (a.ks) hipLaunchKernelGGL((chunk_attn_kernel<DT, D, APPEND, BIAS, false, true>), grid, dim3(DEC_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((chunk_attn_kernel<DT, D, APPEND, BIAS, false>), grid, dim3(DEC_THREADS), 0, stream, a);
     hipLaunchKernelGGL((chunk_combine_kernel<DT, D>), dim3(a.M, a.H, a.B), dim3(D), 0, stream, a);
   }
 }
@@ -1194,6 +1263,10 @@ int fat5_attn_decode_chunk(const fat5_decode_chunk_params* p, void* stream_) {
   a.B = p->B, a.H = p->H, a.M = p->M, a.cap = p->capacity, a.N = p->N, a.R = p->rpe_radius, a.causal = p->causal;
   a.splits = chunk_splits(p);
   a.scale_log2 = p->sm_scale * kLog2e;
+  if (p->cache_dtype == FAT5_KV_FP8_E4M3) {
+    a.ks = p->k_scale, a.vs = p->v_scale;
+    for (int i = 0; i < 3; ++i) a.ks_s[i] = p->k_scale_stride[i], a.vs_s[i] = p->v_scale_stride[i];
+  }
   const bool append = p->k_new != nullptr, bias = a.rpe1d != nullptr;
   hipStream_t stream = (hipStream_t)stream_;
   auto go = [&](auto dt_, auto d_) {

@@ -40,6 +40,10 @@ encoder runs (`check_padding`).  The encoder then sees only each row's valid key
 fat5_rpe and RoPE, the mask folded into the dense bias otherwise), every cross-attention launch gets the row's encoder length as
 its `cache_seqlens`, and a ragged decoder prompt is prefilled by one chunk step with per-row `chunk_seqlens`.  All-ones masks and
 None take the code path above.
+
+FP8 KV caches (`kv_cache_dtype="fp8"`): the self-attention caches are allocated as e4m3fn bytes plus one fp32 scale
+per (row, position, head), the cross-attention K / V are quantised once by `quantize_kv`, and every decode launch reads bytes and
+scales and quantises the rows it appends: (D + 4) / (2 D) of the cache bytes, in every mode above.  None: nothing here runs.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -63,6 +67,18 @@ class DecodeState:
     cross_batch_idx: Optional[torch.Tensor] = None  # beam search: (B * k,) int32, beam row -> encoder row (b // k)
     row_batch: Optional[torch.Tensor] = None        # beam search: (B * k, capacity) int32 history table (cache_row_batch)
     cross_seqlens: Optional[torch.Tensor] = None    # padded inputs: (B,) / (B * k,) int32 valid encoder keys per decoding row
+    # FP8 caches (kv_cache_dtype="fp8"): per decoder layer the fp32 scales (B, capacity | L_enc, H) of the float8_e4m3fn caches
+    self_k_scale: Optional[List[torch.Tensor]] = None
+    self_v_scale: Optional[List[torch.Tensor]] = None
+    cross_k_scale: Optional[List[torch.Tensor]] = None
+    cross_v_scale: Optional[List[torch.Tensor]] = None
+
+    def scales(self, i):
+        """forward_decode's keywords for layer i -> (self-attention's, cross-attention's); empty without FP8 caches"""
+        if self.self_k_scale is None:
+            return {}, {}
+        return (dict(k_scale=self.self_k_scale[i], v_scale=self.self_v_scale[i]),
+                dict(k_scale=self.cross_k_scale[i], v_scale=self.cross_v_scale[i]))
 
     @property
     def position(self):
@@ -76,6 +92,15 @@ def _embed(model, ids):
     if torch.is_autocast_enabled() and h.is_cuda:  # (FAT5Stack.forward's rule)
         h = h.to(torch.get_autocast_dtype("cuda"))
     return h
+
+
+def check_kv_cache_dtype(kv_cache_dtype, what="generate"):
+    """None, or "fp8" / "fp8_e4m3" -> whether the caches are FP8"""
+    if kv_cache_dtype is None:
+        return False
+    if kv_cache_dtype in ("fp8", "fp8_e4m3"):
+        return True
+    raise ValueError(f"{what}: kv_cache_dtype {kv_cache_dtype!r} (None, 'fp8' or its alias 'fp8_e4m3')")
 
 
 def _check_supported(model):
@@ -210,14 +235,17 @@ def encode(model, input_ids, pad=None):
 
 
 @torch.no_grad()
-def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1, prompt_length=1):
+def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1, prompt_length=1, kv_cache_dtype=None):
     """Run the encoder, project every decoder layer's cross-attention K / V once and allocate self-attention caches of capacity
     `max_length + prompt_length` (a decoder prompt of `prompt_length` tokens, the start token included, then max_length new ones).
     `attention_mask` (B, L), right-padded, is applied: it is validated with one host read before the encoder runs
     (`check_padding`; a validated `Padding` is taken as it is), the encoder's self-attention sees each row's valid keys only, and
     `cross_seqlens` carries the rows' encoder lengths to every cross-attention launch.  None and an all-ones mask change nothing.
     num_beams > 1: the encoder and the cross K / V stay at B rows; the self-attention caches, the lengths and the history table
-    get B * num_beams rows (row b * k + j: beam j of input b)."""
+    get B * num_beams rows (row b * k + j: beam j of input b).
+    kv_cache_dtype="fp8" (alias "fp8_e4m3"): the self-attention caches are float8_e4m3fn bytes with zeroed fp32 scales beside them,
+    the cross-attention K / V are quantised once (`quantize_kv`); anything but these and None raises before the encoder runs."""
+    fp8 = check_kv_cache_dtype(kv_cache_dtype, "init_decode_state")
     _check_supported(model)
     first = model.decoder.block[0].self_attention_layer.self_attention
     cap = int(max_length) + int(prompt_length)
@@ -235,16 +263,30 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else model.shared.weight.dtype
     H, D = first.n_heads, first.key_value_proj_dim
     self_k, self_v, cross_k, cross_v = [], [], [], []
+    sks, svs, cks, cvs = [], [], [], []
     for blk in model.decoder.block:
-        self_k.append(torch.zeros((Bk, cap, H, D), dtype=dtype, device=dev))
-        self_v.append(torch.zeros((Bk, cap, H, D), dtype=dtype, device=dev))
+        if fp8:
+            from .decode import FP8, quantize_kv
+            self_k.append(torch.zeros((Bk, cap, H, D), dtype=torch.uint8, device=dev).view(FP8))
+            self_v.append(torch.zeros((Bk, cap, H, D), dtype=torch.uint8, device=dev).view(FP8))
+            sks.append(torch.zeros((Bk, cap, H), dtype=torch.float32, device=dev))
+            svs.append(torch.zeros((Bk, cap, H), dtype=torch.float32, device=dev))
+        else:
+            self_k.append(torch.zeros((Bk, cap, H, D), dtype=dtype, device=dev))
+            self_v.append(torch.zeros((Bk, cap, H, D), dtype=dtype, device=dev))
         k, v = blk.cross_attention_layer.cross_attention.project_kv(enc)
+        if fp8:   # (the 16-bit projections are dropped once their bytes and scales exist)
+            (k, ks), (v, vs) = quantize_kv(k), quantize_kv(v)
+            cks.append(ks)
+            cvs.append(vs)
         cross_k.append(k)
         cross_v.append(v)
     pb = None
     if not first.rotary:
         pb = first.pe_encoding.forward_1d()  # (the (H, 2R+1) generator, built once per generate as the training path builds it per step)
     state = DecodeState(enc, self_k, self_v, cross_k, cross_v, torch.zeros((Bk,), dtype=torch.int32, device=dev), pb, cap)
+    if fp8:
+        state.self_k_scale, state.self_v_scale, state.cross_k_scale, state.cross_v_scale = sks, svs, cks, cvs
     if num_beams > 1:
         state.cross_batch_idx = torch.arange(Bk, dtype=torch.int32, device=dev) // int(num_beams)
         state.row_batch = torch.zeros((Bk, cap), dtype=torch.int32, device=dev)
@@ -266,11 +308,13 @@ def decode_step(model, state, token_ids):
     pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
     for i, blk in enumerate(model.decoder.block):
         sa = blk.self_attention_layer
+        ssc, csc = state.scales(i)
         h = h + sa.self_attention.forward_decode(sa.layer_norm(h), state.self_k[i], state.self_v[i], state.cache_seqlens,
-                                                 position_bias=state.position_bias, position=pos, cache_row_batch=state.row_batch)
+                                                 position_bias=state.position_bias, position=pos, cache_row_batch=state.row_batch,
+                                                 **ssc)
         ca = blk.cross_attention_layer
         h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos,
-                                                  cache_batch_idx=state.cross_batch_idx, cross_seqlens=state.cross_seqlens)
+                                                  cache_batch_idx=state.cross_batch_idx, cross_seqlens=state.cross_seqlens, **csc)
         h = blk.ff_layer(h)
     h = model.decoder.final_layer_norm(h)
     state.cache_seqlens.add_(1)
@@ -310,11 +354,12 @@ def decode_chunk(model, state, token_ids, logits="all", chunk_seqlens=None):
     pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
     for i, blk in enumerate(model.decoder.block):
         sa = blk.self_attention_layer
+        ssc, csc = state.scales(i)
         h = h + sa.self_attention.forward_decode(sa.layer_norm(h), state.self_k[i], state.self_v[i], state.cache_seqlens,
-                                                 position_bias=state.position_bias, position=pos, chunk_seqlens=chunk_seqlens)
+                                                 position_bias=state.position_bias, position=pos, chunk_seqlens=chunk_seqlens, **ssc)
         ca = blk.cross_attention_layer
         h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos,
-                                                  cross_seqlens=state.cross_seqlens, chunk_seqlens=chunk_seqlens)
+                                                  cross_seqlens=state.cross_seqlens, chunk_seqlens=chunk_seqlens, **csc)
         h = blk.ff_layer(h)
     state.cache_seqlens.add_(M if chunk_seqlens is None else chunk_seqlens.clamp(0, M))
     if logits == "none":
@@ -427,11 +472,11 @@ def _beam_step(model, state, tok, bs, opts, proc=None):
 
 
 def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, length_penalty, early_stopping, return_scores,
-                   proc=None):
+                   proc=None, kv_cache_dtype=None):
     from .beam import new_state, keep_going
     B = input_ids.shape[0]
     dev = input_ids.device
-    state = init_decode_state(model, input_ids, max_length, attention_mask, num_beams=k)
+    state = init_decode_state(model, input_ids, max_length, attention_mask, num_beams=k, kv_cache_dtype=kv_cache_dtype)
     bs = new_state(B, k, int(max_length) + 1, state.capacity, dev)
     proc = _proc_on_device(proc, dev)
     bs.cache_row_batch = state.row_batch  # (one table: the decode kernel reads it, the beam step reorders it)
@@ -465,7 +510,7 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
              top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
              return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None,
              decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
-             decoder_attention_mask=None):
+             decoder_attention_mask=None, kv_cache_dtype=None):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -523,7 +568,15 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     prompt is its first P_b columns: ONE chunk step prefills all rows (per-row chunk lengths), row b's first new token comes
     from the logits at its own last prompt row, and max_length new tokens follow each row's own prompt; the result is
     (B, P + steps), rows with shorter prompts end earlier and are 0 from there.  Ragged prompts are rejected with RoPE at B > 1
-    (one rotary row per batch) and with an assistant model; beam search takes no decoder prompt at all."""
+    (one rotary row per batch) and with an assistant model; beam search takes no decoder prompt at all.
+
+    `kv_cache_dtype`: None (the caches in the activation dtype; everything above, unchanged) or "fp8" (alias
+    "fp8_e4m3"): every K / V cache of the call -- self-attention and cross-attention, the assistant's too -- is held as
+    float8_e4m3fn bytes with one fp32 scale per (row, position, head), (D + 4) / (2 D) of the bytes.  Rows are quantised as they
+    are appended, by the decode kernels; the encoder's K / V once.  All modes and graph=True work with it; the tokens can differ
+    from the default's where two logits are within the quantisation error.  Any other value raises ValueError before an
+    encoder runs."""
+    check_kv_cache_dtype(kv_cache_dtype)
     from .beam import check_args as check_beam_args
     check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample)
     P = _check_prompt(model, input_ids, decoder_input_ids, num_beams, decoder_attention_mask)
@@ -539,11 +592,14 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
         from .speculative import check_generate_args, speculative_generate
         check_generate_args(model, assistant_model, input_ids, max_length, num_assistant_tokens, P, do_sample, num_beams,
                             proc is not None)
+        if kv_cache_dtype is not None:
+            return speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, P,
+                                        decoder_input_ids, bool(return_stats), kv_cache_dtype)
         return speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, P,
                                     decoder_input_ids, bool(return_stats))
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
-                              early_stopping, return_scores, proc)
+                              early_stopping, return_scores, proc, kv_cache_dtype)
     proc = _proc_on_device(proc, input_ids.device)
     step = _greedy_step
 
@@ -566,7 +622,7 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
             _sample_pick(logits, state, tok, labels, seen_eos, sampling, proc)
     B = input_ids.shape[0]
     dev = input_ids.device
-    state = init_decode_state(model, input_ids, max_length, attention_mask, prompt_length=P)
+    state = init_decode_state(model, input_ids, max_length, attention_mask, prompt_length=P, kv_cache_dtype=kv_cache_dtype)
     labels = torch.zeros((B, state.capacity), dtype=torch.long, device=dev)
     tok = torch.zeros((B,), dtype=torch.long, device=dev)
     seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)

@@ -210,15 +210,16 @@ def check_generate_args(model, assistant_model, input_ids, max_length, num_assis
 
 @torch.no_grad()
 def speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, prompt_length,
-                         decoder_input_ids, return_stats):
+                         decoder_input_ids, return_stats, kv_cache_dtype=None):
     """`generate`'s speculative loop (the arguments are checked already): per round gamma + 1 draft steps, one chunk step of the
     target and the verification kernel, then ONE host read (`seen_eos.all()`), as the plain loop does once per token"""
     from .generation import _capture_call, decode_chunk, finish_labels, init_decode_state
     gamma, P, T_max = int(num_assistant_tokens), int(prompt_length), int(max_length)
     B, dev = input_ids.shape[0], input_ids.device
     # capacity P + max_length + gamma + 1: a row at its last free column still appends a whole chunk before the roll-back
-    state = init_decode_state(model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P)
-    dstate = init_decode_state(assistant_model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P)
+    kv = {} if kv_cache_dtype is None else dict(kv_cache_dtype=kv_cache_dtype)   # (both models' caches take the dtype)
+    state = init_decode_state(model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P, **kv)
+    dstate = init_decode_state(assistant_model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P, **kv)
     labels = torch.zeros((B, P + T_max), dtype=torch.long, device=dev)
     limit = P - 1 + T_max
     tok = torch.zeros((B,), dtype=torch.long, device=dev)

@@ -340,6 +340,43 @@ size_t fat5_fire_bwd_workspace_bytes(const fat5_fire_params* p);
 int fat5_fire_bwd(const fat5_fire_params* p, void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /*
+ * FP8 KV cache: the storage format of a cache whose cache_dtype is FAT5_KV_FP8_E4M3, written by fat5_kv_quantize and by
+ * the appends of fat5_attn_decode / fat5_attn_decode_chunk, read by those two.  tests/kvfp8_ref.py restates it in plain torch.
+ *   - The cache holds OCP e4m3fn bytes (torch.float8_e4m3fn; not the fnuz format), shape and strides as for the 16-bit caches:
+ *     (B, capacity, H, D) views with element (= byte) strides [b, l, h], so (B, L, H, D) and (B, H, L, D) storage both work.
+ *   - Beside each cache sits a scale tensor: fp32, (B, capacity, H), element strides [b, l, h] passed to the kernel.
+ *   - A row x of D elements (fp16 / bf16) is quantised as
+ *         a_d    = |fp32(x_d)|, a NaN counted as +inf;   amax = max_d a_d
+ *         s      = amax / 448.0f   (an fp32 IEEE division);   s = 1 when amax == 0
+ *         byte_d = RNE_e4m3fn(clamp(fp32(x_d) / s, -448, 448))   (again an fp32 IEEE division; round to nearest even, fp8
+ *                  subnormals included; the clamp makes the conversion saturating; NaN is stored as 0x7F and only NaN is)
+ *     i.e. (x.float() / s).clamp(-448, 448).to(torch.float8_e4m3fn).  Stored bytes and scales equal this bit for bit.
+ *   - A row with a non-finite element (inf or NaN) has amax = +inf, hence s = +inf: its finite elements are stored as 0, its
+ *     non-finite ones as NaN, and the whole row reads back as NaN (0 * inf), so poisoned input stays visible.  Nothing faults.
+ *   - The value read back is fp32(byte_d) * s.  The decode kernels apply s to the finished dot product (K) and to the softmax
+ *     weight (V) instead of to each element.
+ */
+enum fat5_kv_cache_dtype { FAT5_KV_NATIVE = 0, FAT5_KV_FP8_E4M3 = 1 };
+
+/*
+ * Row quantiser of the FP8 KV cache: x (B, L, H, D) fp16 / bf16, element strides [b, l, h], innermost stride 1 -> bytes (B, L, H, D)
+ * and scales (B, L, H) by the rule above, in one launch (graph-capturable); B * L * H == 0 is a no-op.  D in {64, 128}.  x: 16-byte
+ * aligned base, strides multiples of 8; out: 8-byte aligned base, strides multiples of 8; scale: 4-byte aligned.  Everything is
+ * checked before any device work: FAT5_EINVAL for a NULL params, D / dtype outside those sets, negative sizes, more than 2^31 - 1
+ * workgroups of rows, NULL or misaligned pointers or strides (with rows to write).
+ */
+typedef struct fat5_kv_quant_params {
+  int32_t B, L, H, D;
+  int32_t dtype;              /* FAT5_F16 | FAT5_BF16: x */
+  const void* x;
+  void* out;                  /* e4m3fn bytes */
+  float* scale;
+  int64_t x_stride[3], out_stride[3], scale_stride[3];
+} fat5_kv_quant_params;
+size_t fat5_sizeof_kv_quant_params(void);
+int fat5_kv_quantize(const fat5_kv_quant_params* p, void* hip_stream);
+
+/*
  * Decode attention against a KV cache: one query row per (batch, head), the key range split over several workgroups (split-KV)
  * and merged in a fixed order (decode_kernels.h).  Stands in for flash_attn's `flash_attn_with_kvcache` at seqlen_q = 1; the
  * reference has no cached decoding (its generate reruns the whole decoder per token, src/model/modeling_flash_t5.py:648-690).
@@ -374,6 +411,13 @@ int fat5_fire_bwd(const fat5_fire_params* p, void* workspace, size_t workspace_b
  * exactly one of k_new / v_new, an append without cache_seqlens, NULL / misaligned pointers or strides, cache_B < 0 or one
  * smaller than B where the rule above needs B, cache_batch_idx together with cache_row_batch or with an append, a misaligned
  * map; FAT5_EWORKSPACE when the workspace is missing, misaligned or smaller than fat5_attn_decode_workspace_bytes().
+ * FP8 caches (fat5_attn_decode_kv8 with cache_dtype FAT5_KV_FP8_E4M3; the format is stated above, the descriptor below): k_cache /
+ * v_cache hold bytes, k_scale / v_scale their (cache_B, capacity, H) fp32 scales; q, k_new, v_new and o keep `dtype`.  Everything above holds unchanged, with these additions:
+ * a scale is read from the batch element its row is read from (cache_batch_idx, cache_row_batch); the appended row is quantised in
+ * the launch, its bytes and scales are written to batch element b at row len_b, and the query attends the quantised row read
+ * back, not k_new / v_new, so o is a function of the cache contents after the call; a skipped append writes neither.  Rejected with
+ * FAT5_EINVAL before anything is launched: a cache_dtype outside the enum, a NULL or misaligned k_scale / v_scale in FP8 mode.
+ * cache_dtype 0 with the scale fields zero, and fat5_attn_decode itself: the kernels, grid and bits as before the fields existed.
  */
 typedef struct fat5_decode_params {
   int32_t B, H, D;            /* D in {64, 128} */
@@ -406,6 +450,21 @@ size_t fat5_sizeof_decode_params(void);
 /* workspace fat5_attn_decode needs for these host-known arguments (bytes; 0 when one split is used) */
 size_t fat5_attn_decode_workspace_bytes(const fat5_decode_params* p);
 int fat5_attn_decode(const fat5_decode_params* p, void* hip_stream);
+
+/* fat5_decode_params followed by the FP8-cache fields, for fat5_attn_decode_kv8.  The one-row descriptor itself ends at cache_B and
+ * keeps its size, so a caller compiled against it is untouched; the fields that extend it stand behind it here.  `base` is read as
+ * fat5_attn_decode reads it (base.dtype is the dtype of q, k_new, v_new and o); its workspace is
+ * fat5_attn_decode_workspace_bytes(&base).  cache_dtype 0 with the scale fields zero: fat5_attn_decode(&base), bit for bit. */
+typedef struct fat5_decode_kv8_params {
+  fat5_decode_params base;
+  /* FP8 KV cache; all zero: 16-bit caches of base.dtype */
+  int32_t cache_dtype;        /* FAT5_KV_NATIVE | FAT5_KV_FP8_E4M3 */
+  float* k_scale;             /* (cache_B, capacity, H) fp32: k_scale_stride [b, l, h]; written by an append */
+  float* v_scale;
+  int64_t k_scale_stride[3], v_scale_stride[3];
+} fat5_decode_kv8_params;
+size_t fat5_sizeof_decode_kv8_params(void);
+int fat5_attn_decode_kv8(const fat5_decode_kv8_params* p, void* hip_stream);
 
 /*
  * Chunked decode attention: M query rows per (batch, head) against a KV cache, their M key / value rows appended in the same launch
@@ -443,6 +502,11 @@ int fat5_attn_decode(const fat5_decode_params* p, void* hip_stream);
  * 1..2048 or a NULL rpe1d with RPE1D, a misaligned chunk_seqlens, exactly one of k_new / v_new, an append without cache_seqlens, a non-finite sm_scale,
  * NULL / misaligned pointers or strides; FAT5_EWORKSPACE when the workspace is missing, misaligned or smaller than
  * fat5_attn_decode_chunk_workspace_bytes().
+ * FP8 caches (cache_dtype FAT5_KV_FP8_E4M3, "FP8 KV cache" above): the caches hold bytes, k_scale / v_scale their (B, capacity, H)
+ * fp32 scales.  Every rule above holds; a key row j >= len_b still comes from k_new / v_new, and each workgroup that reads it
+ * quantises it itself and attends the quantised row read back (the rule is a function of the row alone, so all readers agree with
+ * the bytes and scales that the row's one writer stores).  Rejected with FAT5_EINVAL before anything is launched: a cache_dtype
+ * outside the enum, a NULL or misaligned scale pointer in FP8 mode.  All zero: as before the fields existed.
  */
 typedef struct fat5_decode_chunk_params {
   int32_t B, H, M, D;         /* M query rows per (b, h), 1..1024; D in {64, 128} */
@@ -467,6 +531,11 @@ typedef struct fat5_decode_chunk_params {
   void* workspace;            /* fat5_attn_decode_chunk_workspace_bytes(); 16-byte aligned; may be NULL when that is 0 */
   size_t workspace_bytes;
   const int32_t* chunk_seqlens; /* (B,) int32 device array of rows per batch element, each clamped to [0, M]; NULL: M for every b */
+  /* FP8 KV cache; all zero: 16-bit caches of `dtype` */
+  int32_t cache_dtype;        /* FAT5_KV_NATIVE | FAT5_KV_FP8_E4M3 */
+  float* k_scale;             /* (B, capacity, H) fp32: k_scale_stride [b, l, h]; written by the append */
+  float* v_scale;
+  int64_t k_scale_stride[3], v_scale_stride[3];
 } fat5_decode_chunk_params;
 /* sizeof(fat5_decode_chunk_params) as compiled into the library (bindings check their mirror against it). */
 size_t fat5_sizeof_decode_chunk_params(void);
