@@ -1,0 +1,333 @@
+"""The attention backward per element of dq, dk, dv, dbias, drpe1d and the T5 table gradient against the fp64 restatement and the derived
+bound of tests/attn_bwd_fp64.py: the FA2 backward from a GIVEN (o, lse).  The test fills `plan.o` and `plan.lse` of an AttentionPlan
+itself -- no forward launch is involved -- so delta = rowsum(o do) is formed from the same numbers on both sides, and the bound is in
+units of each element's own term magnitudes: no tensor maximum, no max(1, .).
+
+Covered (csrc/attn_bwd.h): the 32-wide bodies dq=32row, dkdv=32key at D = 16 / 32 / 64 / 128, both wave counts, as separate launches
+(groups w2, w4, causal, t5, dbias, pert) and in the one-launch form (group fused32); dense dbias by the routes direct, staged and inkernel
+(with its fp32 scratch at B = 5, and unsplit); drpe1d; the table gradient as dtable=runs and dtable=scan, bidirectional and
+unidirectional maps.  Shapes are the smallest at which the structure exists: rows and keys around every 32 / 64 / 128 boundary, radius
+1 / 8 / 128, bottom-right causal masks with N - M in {0, 1, 100, -1, -100} (dead rows included), dense biases of every broadcast kind and
+one holding finfo.min.  "Perturbed" cases shift lse by 0.25 on every third row and replace o by an unrelated tensor: the contract is
+"from the stored o, lse", and a kernel that recomputed either would leave the bound.  Some cases call the stages one by one.
+Not covered: every 64-wide body (see tests/attn_bwd_fp64.py); they stay with the max-norm tests.
+
+The value rows at key 0, N - 1 and the block seam and the `do` rows 0, M - 1 and the first rows of the last 32- / 64-row blocks carry 32
+times the others' magnitude, so that one dropped key or row there moves the gradients beyond the bound (tests/test_attn_bwd_fp64_cpu.py
+proves that on these very inputs, without a GPU).  Every case asserts its bodies through fat5_attn_describe before it launches.
+
+CASES, `inputs`, `reference` and `describe` are module-level and CPU-only.
+"""
+import ctypes
+import zlib
+
+import pytest
+import torch
+
+import attn_bwd_fp64 as G
+import attn_fwd_fp64 as F
+from oracle.rpe import relative_position_bucket
+
+BF16, F16 = torch.bfloat16, torch.float16
+BOOST = 32.0
+NUM_BUCKETS = 32
+WORST = {}   # group (bodies) -> [launches, {output: [worst ratio, its case]}]
+
+# fat5_variant bits by name (flasht5_amd/_lib.py), resolved where the library is loaded
+SEP32 = ("V_KV64_OFF", "V_Q64_OFF", "V_QDB64_OFF", "V_NO_FUSE")
+ONE32 = ("V_KV64_OFF", "V_Q64_OFF", "V_QDB64_OFF")
+FORCE64 = ("V_KV64_ON", "V_Q64_ON", "V_QDB64_ON", "V_FUSED64_ON")   # (dense rows that are no multiple of 8 keys cannot travel by LDS-DMA: the dispatcher keeps the 32-wide bodies)
+DENSE_SHAPE = {"11": (1, 1), "1h": (1, 0), "b1": (0, 1), "bh": (0, 0)}   # 1 = broadcast
+
+
+def _name(dtype):
+    return str(dtype)[6:]
+
+
+def _build_cases():
+    out = []
+
+    def add(group, bits, B, H, M, N, D, dtype, causal=False, bias="none", R=0, strided=False, pert=False, split=False, fused=0, route=None,
+            dtable=None):
+        cid = (f"{group}-{B}x{H}x{M}x{N}-D{D}-{_name(dtype)}-{bias}{R if R else ''}{'-causal' if causal else ''}{'-strided' if strided else ''}"
+               f"{'-pert' if pert else ''}{'-stages' if split else ''}{'-' + route if route in ('inkernel', 'nosplit') else ''}{'-' + dtable if dtable else ''}")
+        dense = bias[:2] in DENSE_SHAPE
+        if dense and route is None:
+            assert bias[:2] == "bh" or (B > 1 and H > 1)
+            route = "direct" if bias[:2] == "bh" else "staged"
+        if route in ("inkernel", "nosplit"):
+            bits = bits + ("V_DBIAS_INKERNEL",) + (("V_DBIAS_NOSPLIT",) if route == "nosplit" else ())
+        elif route == "staged" and bits is not FORCE64:
+            bits = bits + ("V_DBIAS_STAGED",)
+        if dtable == "scan":
+            bits = bits + ("V_DTABLE_RUNS_OFF",)
+        bodies = dict(dq="32row", dkdv="32key", fused=str(fused), qdiag="0")
+        if dense:
+            bodies["dbias"] = "inkernel" if route == "nosplit" else route
+        if dtable:
+            bodies["dtable"] = dtable
+        out.append(dict(id=cid, group=group, bodies=bodies, bits=bits, B=B, H=H, M=M, N=N, D=D, dtype=dtype, causal=causal, bias=bias, R=R,
+                        scale=float(D) ** -0.5, strided=strided, pert=pert, split=split))
+
+    # ---- 32-wide bodies, separate launches, two waves (fewer than 160 workgroups) ----
+    Ms, Ns = (1, 31, 32, 33, 64, 65, 129), (1, 63, 64, 65, 127, 128, 129, 200)
+    kinds = ("none", "rpe", "1h", "rpe", "bh", "none", "11", "rpe", "b1")
+    i = 0
+    for j, N in enumerate(Ns):
+        for M in (Ms[j % 7], Ms[(3 * j + 2) % 7]):
+            bias = kinds[i % 9]
+            add("w2", SEP32, 1 + i % 2 if bias not in ("1h", "b1", "11") else 2, 2, M, N, (16, 32, 64, 128)[i % 4], (BF16, F16)[(i // 2) % 2], causal=i % 5 in (1, 3),
+                bias=bias, R=(8, 128, 1)[(i // 2) % 3] if bias == "rpe" else 0, strided=i % 4 == 0, split=i % 5 == 2)
+            i += 1
+    # ---- ... four waves (160 workgroups or more in the stage) ----
+    for i, (H, M, N, D, bias) in enumerate(((80, 33, 129, 64, "rpe"), (40, 128, 200, 32, "none"), (80, 65, 64, 64, "1h"), (40, 129, 65, 128, "none"))):
+        add("w4", SEP32, 2, H, M, N, D, (BF16, F16)[i % 2], causal=i == 1, bias=bias, R=8 if bias == "rpe" else 0, strided=i == 0)
+    # ---- causal, bottom-right: N - M in {0, 1, 100, -1, -100} (the last two with dead rows), with the table, without, dense ----
+    for i, d in enumerate((0, 1, 100, -1, -100)):
+        M, N = (129, 129 + d) if d >= 0 else (129 - d, 129)
+        bias = ("rpe", "none")[i % 2]
+        add("causal", SEP32, 1, 2, M, N, 64, (BF16, F16)[(i // 2) % 2], causal=True, bias=bias, R=(128, 8)[(i // 2) % 2] if bias == "rpe" else 0)
+        add("causal", SEP32, 2, 2, M, N, (32, 128)[i % 2], (F16, BF16)[(i // 2) % 2], causal=True, bias=("1h", "bh", "11")[i % 3], strided=i == 3)
+    # ---- T5 tables through the bucket map: the table gradient per bucket run and by the scan, and drpe1d of an i.i.d. generator ----
+    i = 0
+    for R in (8, 128):
+        for B in (1, 3):
+            M, N = ((100, 140 + R), (131, 330))[i % 2] if R == 8 else ((200, 330), (65, 300))[i % 2]
+            add("t5", SEP32, B, 2, M, N, (64, 32)[i % 2], (BF16, F16)[i % 2], bias="t5b", R=R, dtable="runs", causal=i == 3)
+            add("t5", SEP32, B, 2, M, N, (64, 128)[i % 2], (F16, BF16)[i % 2], bias="t5u", R=R, dtable=("scan", "runs")[i % 2], split=i == 2)
+            add("t5", SEP32, B, 2, M, N, 64, (BF16, F16)[i % 2], bias="t5b", R=R, dtable="scan", strided=i == 1)
+            i += 1
+    add("t5", SEP32, 3, 2, 100, 141, 64, BF16, bias="rpe", R=1)
+    # ---- dense dbias: the batch-inner kernel (split over two wave groups, unsplit, with the fp32 scratch at B = 5), staged at B = 5 ----
+    for i, (B, M, N, D, route) in enumerate(((2, 65, 64, 64, "inkernel"), (5, 129, 136, 64, "inkernel"), (5, 65, 127, 64, "nosplit"), (4, 33, 200, 128, "inkernel"),
+                                             (5, 129, 136, 64, "staged"), (9, 64, 65, 32, "inkernel"))):
+        add("dbias", SEP32, B, 2, M, N, D, (BF16, F16)[i % 2], causal=i in (1, 4), bias="1h", route=route, split=i == 1)
+    add("dbias", SEP32, 2, 2, 130, 192, 64, BF16, bias="1h-min", route="staged")          # finfo.min on half the keys, and on all keys of some rows
+    add("dbias", FORCE64, 2, 2, 65, 63, 64, BF16, bias="1h")                              # the 64-wide bodies asked for, N % 8 != 0: falls back to the 32-wide ones
+    # ---- perturbed (o, lse): the kernels follow what is stored ----
+    add("pert", SEP32, 1, 2, 65, 129, 64, BF16, pert=True)
+    add("pert", SEP32, 2, 2, 129, 200, 128, F16, bias="rpe", R=8, causal=True, pert=True)
+    add("pert", SEP32, 2, 2, 64, 65, 32, BF16, bias="bh", pert=True, split=True)
+    add("pert", SEP32, 2, 2, 33, 128, 16, F16, bias="1h", pert=True, strided=True)
+    # ---- the 32-wide one-launch form: both stages at four waves, D <= 64, both grids together at most four workgroups per CU ----
+    add("fused32", ONE32, 2, 80, 129, 200, 64, BF16, fused=1)
+    add("fused32", ONE32, 2, 80, 33, 65, 32, F16, causal=True, fused=1, strided=True)
+    add("fused32", ONE32, 2, 80, 65, 129, 64, F16, bias="rpe", R=8, fused=1)
+    add("fused32", ONE32, 2, 80, 64, 100, 16, BF16, bias="t5b", R=128, dtable="runs", causal=True, fused=1)
+    add("fused32", ONE32, 2, 80, 33, 64, 64, BF16, bias="1h", fused=1)
+    add("fused32", ONE32, 2, 80, 31, 63, 64, F16, bias="bh", causal=True, fused=1)
+    add("fused32", ONE32, 2, 80, 65, 33, 64, BF16, causal=True, pert=True, fused=1)
+    add("fused32", ONE32, 2, 80, 32, 127, 32, BF16, bias="rpe", R=1, pert=True, fused=1)
+    assert len({c["id"] for c in out}) == len(out)
+    return out
+
+
+CASES = _build_cases()
+
+
+def _gen(*key):
+    return torch.Generator().manual_seed(zlib.crc32(repr(key).encode()))
+
+
+def boosted_rows(M):
+    """the `do` rows that carry BOOST times the others' magnitude: 0, M - 1, the first rows of the last 32- and 64-row blocks and the seam row"""
+    return sorted({0, M - 1, (M - 1) // 32 * 32, (M - 1) // 64 * 64, G.seam_row(M)} - {None})
+
+
+def bucket_map(case):
+    if case["bias"][:2] != "t5":
+        return None
+    R = case["R"]
+    return torch.from_numpy(relative_position_bucket(torch.arange(-R, R + 1).numpy(), case["bias"] == "t5b", NUM_BUCKETS, 128)).to(torch.int32)
+
+
+def inputs(case):
+    """CPU tensors of a case: q, k, v, do (strided views where the case says so), bias (dense, in the dtype) or None, rpe (H, 2R + 1) fp32 or
+    None, bucket (2R + 1) int32 or None, and the given o (in the dtype) and lse (fp32)"""
+    B, H, M, N, D, dtype = (case[x] for x in ("B", "H", "M", "N", "D", "dtype"))
+    g = _gen(case["id"])
+
+    def rnd(S):
+        if case["strided"]:   # the model's layout: (B, S, H, D) storage viewed as (B, H, S, D)
+            return torch.randn(B, S, H, D, generator=g).to(dtype).permute(0, 2, 1, 3)
+        return torch.randn(B, H, S, D, generator=g).to(dtype)
+
+    q, k, v, do = rnd(M), rnd(N), rnd(N), rnd(M)
+    for j in {0, N - 1, F.seam_key(N)} - {None}:
+        v[:, :, j] = (v[:, :, j].float() * BOOST).to(dtype)
+    for m in boosted_rows(M):
+        do[:, :, m] = (do[:, :, m].float() * BOOST).to(dtype)
+    bias = rpe = None
+    kind = case["bias"]
+    bucket = bucket_map(case)
+    if kind == "rpe":      # an i.i.d. generator: every entry distinct, so a wrong index shows
+        rpe = torch.randn(H, 2 * case["R"] + 1, generator=g)
+    elif bucket is not None:   # a T5 table through its bucket map (bidirectional / unidirectional), clamped at R
+        rpe = torch.randn(NUM_BUCKETS, H, generator=g)[bucket.long()].T.contiguous()
+    elif kind != "none":
+        sb, sh = DENSE_SHAPE[kind[:2]]
+        bias = torch.randn(1 if sb else B, 1 if sh else H, M, N, generator=g).to(dtype)
+        if kind.endswith("-min"):
+            bias[..., N // 2:] = torch.finfo(dtype).min
+            bias[:, :, 7::64, :] = torch.finfo(dtype).min
+    fwd = F.attn_fwd_ref(q, k, v, case["scale"], case["causal"], bias, rpe, case["R"])
+    o = torch.empty_like(q).copy_(fwd["o"].to(dtype))
+    lse = fwd["lse"].float()
+    if case["pert"]:
+        o = rnd(M)
+        lse[:, :, ::3] += 0.25   # (-inf stays -inf)
+    return dict(q=q, k=k, v=v, do=do, bias=bias, rpe=rpe, bucket=bucket, o=o, lse=lse)
+
+
+def reference(case, t, mutant=None):
+    return G.attn_bwd_ref(t["q"], t["k"], t["v"], t["o"], t["lse"], t["do"], case["scale"], case["causal"], t["bias"], t["rpe"], case["R"],
+                          t["bucket"], NUM_BUCKETS if t["bucket"] is not None else 0, mutant=mutant)
+
+
+def compared(case, ref):
+    """the outputs the kernels write for this case: with a bucket map the table gradient alone"""
+    outs = [x for x in G.outputs_of(ref) if x != "drpe1d" or "drpe_table" not in ref]
+    return outs
+
+
+def variant_bits(case):
+    from flasht5_amd import _lib
+    bits = 0
+    for name in case["bits"]:
+        bits |= getattr(_lib, name)
+    return bits
+
+
+def describe(case):
+    """the backward bodies the library would run this case with (fat5_attn_describe: host-only, no pointer but the host bucket map is followed)"""
+    from flasht5_amd import _lib
+    B, H, M, N = case["B"], case["H"], case["M"], case["N"]
+    p = _lib.AttnParams()
+    p.B, p.H, p.M, p.N, p.D = B, H, M, N, case["D"]
+    p.dtype, p.causal, p.variant, p.sm_scale = _lib.dtype_code(case["dtype"]), int(case["causal"]), variant_bits(case), case["scale"]
+    kind = case["bias"]
+    host = None
+    if kind[:2] in DENSE_SHAPE:
+        sb, sh = DENSE_SHAPE[kind[:2]]
+        nh = 1 if sh else H
+        p.bias_mode, p.bias, p.dbias = _lib.BIAS_DENSE, 16, 16
+        p.bias_stride[0], p.bias_stride[1], p.bias_stride[2] = (0 if sb else nh * M * N), (0 if sh else M * N), N
+        p.dbias_batch, p.dbias_heads = (1 if sb else B), nh
+    elif kind != "none":
+        p.bias_mode, p.rpe1d, p.rpe_radius = _lib.BIAS_RPE1D, 16, case["R"]
+        bucket = bucket_map(case)
+        if bucket is not None:
+            host = (ctypes.c_int32 * len(bucket))(*[int(x) for x in bucket])
+            p.rpe_bucket, p.drpe_table, p.rpe_num_buckets, p.rpe_bucket_host = 16, 16, NUM_BUCKETS, ctypes.addressof(host)
+        else:
+            p.drpe1d = 16
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().fat5_attn_describe(ctypes.byref(p), buf, 256), "fat5_attn_describe")
+    return dict(kv.split("=") for kv in buf.value.decode().split())
+
+
+def assert_bodies(case, d):
+    want = case["bodies"]
+    got = {key: d.get(key) for key in want}
+    assert got == want, f"{case['id']}: the dispatcher runs {got}, the case is meant for {want}"
+
+
+SENTINEL = 777.0
+
+
+def _bits(t):
+    return t.view(torch.int32 if t.element_size() == 4 else torch.int16)
+
+
+def _guarded(t):
+    """a (B, H, S, D) view with t's shape inside a sentinel-filled buffer that has one spare head slot behind every row of heads"""
+    B, H, S, D = t.shape
+    buf = torch.full((B, S, H + 1, D), SENTINEL, dtype=t.dtype, device=t.device)
+    return buf, buf[:, :, :H].permute(0, 2, 1, 3)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
+def test_backward_within_the_fp64_bound(case):
+    from flasht5_amd import _lib
+    from flasht5_amd.flash_attention_v2_bias import AttentionPlan
+    assert_bodies(case, describe(case))
+    t = inputs(case)
+    ref = reference(case, t)
+    bound = G.attn_bwd_bound(ref, case["dtype"], case["D"], case["bodies"], case["N"], case["M"])
+    dev = {key: (x.to("cuda") if x is not None else None) for key, x in t.items()}
+    if case["strided"]:
+        assert dev["q"].stride() == t["q"].stride() and dev["do"].stride() == t["do"].stride() and _lib.kernel_ready(dev["q"])   # (never copied)
+    plan = AttentionPlan(dev["q"], dev["k"], dev["v"], dev["do"], bias=dev["bias"], rpe1d=dev["rpe"], radius=case["R"], causal=case["causal"],
+                         sm_scale=case["scale"], need_dbias=True, rpe_bucket=dev["bucket"], num_buckets=NUM_BUCKETS if dev["bucket"] is not None else 0,
+                         variant=variant_bits(case))
+    assert plan.q.data_ptr() == dev["q"].data_ptr() and plan.do.data_ptr() == dev["do"].data_ptr()
+    assert_bodies(case, plan.describe())
+    assert plan.bwd_launches() == (1 if case["bodies"]["fused"] == "1" else 2)
+    guards = []
+    if case["strided"]:   # the gradients inside larger sentinel-filled buffers
+        for name in ("dq", "dk", "dv"):
+            buf, view = _guarded(getattr(plan, name))
+            guards.append(buf)
+            setattr(plan, name, view)
+            setattr(plan.p, name, view.data_ptr())
+            setattr(plan.p, name + "_stride", _lib.strides3(view))
+    plan.o.copy_(dev["o"])
+    plan.lse.copy_(dev["lse"])
+    given = {key: x.clone() for key, x in dev.items() if x is not None}
+    given["o"], given["lse"] = plan.o.clone(), plan.lse.clone()
+
+    def run():
+        for x in (plan.dq, plan.dk, plan.dv, plan.dbias):
+            if x is not None:
+                x.fill_(SENTINEL)   # (every element has to be written)
+        if case["split"]:
+            for stage in (1, 2, 4):   # FAT5_BWD_DQ, FAT5_BWD_DKDV, FAT5_BWD_REDUCE
+                plan.backward(stage)
+        else:
+            plan.backward()
+        torch.cuda.synchronize()
+        got = dict(dq=plan.dq.cpu(), dk=plan.dk.cpu(), dv=plan.dv.cpu())
+        if plan.dbias is not None:
+            got["dbias" if t["bias"] is not None else ("drpe_table" if t["bucket"] is not None else "drpe1d")] = plan.dbias.cpu()
+        return got
+
+    got = run()
+    again = run()
+    for key, x in given.items():   # lse, o and the inputs are unchanged by the call
+        now = plan.o if key == "o" else (plan.lse if key == "lse" else dev[key])
+        assert torch.equal(_bits(now), _bits(x)), f"{case['id']}: the call changed {key}"
+    for buf in guards:
+        assert bool((buf[:, :, case["H"]] == SENTINEL).all()), f"{case['id']}: written outside the gradient's view"
+    outs = compared(case, ref)
+    assert sorted(got) == sorted(outs)
+    for x in outs:
+        assert torch.equal(_bits(got[x]), _bits(again[x])), f"{case['id']}: a second call gives other bits in {x}"
+    r = G.ratios(got, ref, bound)
+    tag = case["group"] + " (" + " ".join(f"{key}={val}" for key, val in case["bodies"].items()) + ")"
+    w = WORST.setdefault(tag, [0, {}])
+    w[0] += 1
+    for x in outs:
+        if r[x] >= w[1].setdefault(x, [0.0, ""])[0]:
+            w[1][x] = [r[x], case["id"]]
+    print(f"[attn-bwd-fp64] {case['id']}: err / bound " + " ".join(f"{x} {r[x]:.3f}" for x in outs))
+    bad = [x for x in outs if not r[x] <= 1.0]
+    if bad:
+        msg = []
+        for x in bad:
+            gx = got[x].double()
+            e = (gx - ref[x]).abs()
+            q = torch.where(e == 0, torch.zeros_like(e), e / bound[x])
+            q = torch.where(torch.isfinite(gx), q, torch.full_like(q, float("inf")))
+            idx = tuple(int(v) for v in torch.nonzero(q == q.max())[0])
+            msg.append(f"{x} err/bound {r[x]:.3f} at {idx}: got {float(gx[idx])!r} ref {float(ref[x][idx])!r} bound {float(bound[x][idx]):.3e} "
+                       f"T {float(ref['T_' + x][idx]):.3e}")
+        raise AssertionError(f"{case['id']}: " + "; ".join(msg))
+
+
+@pytest.mark.gpu
+def test_zz_summary():
+    """(runs last) one line per group: the launches and the worst err / bound of this session"""
+    for tag, (n, worst) in sorted(WORST.items()):
+        print(f"[attn-bwd-fp64] {tag}: {n} launches, worst err/bound " + ", ".join(f"{x} {v[0]:.3f} ({v[1]})" for x, v in sorted(worst.items())))
+    assert all(v[0] <= 1.0 for _, worst in WORST.values() for v in worst.values())
