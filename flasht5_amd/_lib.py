@@ -173,6 +173,18 @@ class SpecParams(ctypes.Structure):
     ]
 
 
+class LookupParams(ctypes.Structure):
+    """Mirror of `fat5_lookup_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("L_src", ctypes.c_int32), ("ncols", ctypes.c_int32), ("gamma", ctypes.c_int32),
+        ("max_ngram", ctypes.c_int32), ("V", ctypes.c_int32),
+        ("source", ctypes.c_void_p), ("source_stride", ctypes.c_int64), ("src_seqlens", ctypes.c_void_p),
+        ("labels", ctypes.c_void_p), ("labels_stride", ctypes.c_int64), ("cache_seqlens", ctypes.c_void_p),
+        ("tok", ctypes.c_void_p), ("seen_eos", ctypes.c_void_p), ("draft", ctypes.c_void_p), ("draft_stride", ctypes.c_int64),
+        ("n_proposed", ctypes.c_void_p),
+    ]
+
+
 EXPORTS = (
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
@@ -189,6 +201,7 @@ EXPORTS = (
     "fat5_process_logits", "fat5_sizeof_logits_params",
     "fat5_spec_accept", "fat5_spec_accept_workspace_bytes", "fat5_sizeof_spec_params",
     "fat5_kv_quantize", "fat5_sizeof_kv_quant_params",
+    "fat5_lookup_draft", "fat5_sizeof_lookup_params",
 )
 
 _lib = None
@@ -332,6 +345,12 @@ def load():
     if lib.fat5_sizeof_kv_quant_params() != ctypes.sizeof(KvQuantParams):
         raise ImportError(f"fat5_kv_quant_params layout mismatch: library {lib.fat5_sizeof_kv_quant_params()} B, "
                           f"binding {ctypes.sizeof(KvQuantParams)} B")
+    lib.fat5_lookup_draft.restype = ctypes.c_int
+    lib.fat5_lookup_draft.argtypes = [ctypes.POINTER(LookupParams), ctypes.c_void_p]
+    lib.fat5_sizeof_lookup_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_lookup_params() != ctypes.sizeof(LookupParams):
+        raise ImportError(f"fat5_lookup_params layout mismatch: library {lib.fat5_sizeof_lookup_params()} B, "
+                          f"binding {ctypes.sizeof(LookupParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

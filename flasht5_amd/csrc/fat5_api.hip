@@ -25,6 +25,7 @@
 #include "beam_kernels.h"
 #include "logits_kernels.h"
 #include "spec_kernels.h"
+#include "lookup_kernels.h"
 
 using namespace fat5;
 
@@ -1539,6 +1540,50 @@ int fat5_spec_accept(const fat5_spec_params* p, void* stream_) {
   hipLaunchKernelGGL(spec_accept_kernel, dim3(p->B), dim3(64), 0, stream, a);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "spec_accept launch");
+  return FAT5_OK;
+}
+
+// ---- prompt-lookup drafting of speculative greedy decoding (lookup_kernels.h) ----
+size_t fat5_sizeof_lookup_params(void) { return sizeof(fat5_lookup_params); }
+
+int fat5_lookup_draft(const fat5_lookup_params* p, void* stream_) {
+  const char* what = "lookup_draft";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (p->B < 0 || p->B > 65535) return fail(FAT5_EINVAL, "%s: B %d outside [0, 65535]", what, p->B);
+  if (p->L_src < 0 || p->L_src > LOOKUP_MAX_LEN) return fail(FAT5_EINVAL, "%s: L_src %d outside [0, %d]", what, p->L_src, LOOKUP_MAX_LEN);
+  if (p->ncols < 1 || p->ncols > LOOKUP_MAX_LEN) return fail(FAT5_EINVAL, "%s: ncols %d outside [1, %d]", what, p->ncols, LOOKUP_MAX_LEN);
+  if (p->gamma < 1 || p->gamma > LOOKUP_MAX_GAMMA) return fail(FAT5_EINVAL, "%s: gamma %d outside [1, %d]", what, p->gamma, LOOKUP_MAX_GAMMA);
+  if (p->max_ngram < 1 || p->max_ngram > LOOKUP_MAX_NGRAM)
+    return fail(FAT5_EINVAL, "%s: max_ngram %d outside [1, %d]", what, p->max_ngram, LOOKUP_MAX_NGRAM);
+  if (p->V < 0) return fail(FAT5_EINVAL, "%s: V %d (>= 0; 0: no id is cut)", what, p->V);
+  if (p->source_stride < p->L_src) return fail(FAT5_EINVAL, "%s: source_stride %lld < L_src %d", what, (long long)p->source_stride, p->L_src);
+  if (p->labels_stride < p->ncols) return fail(FAT5_EINVAL, "%s: labels_stride %lld < ncols %d", what, (long long)p->labels_stride, p->ncols);
+  if (p->draft_stride < p->gamma) return fail(FAT5_EINVAL, "%s: draft_stride %lld < gamma %d", what, (long long)p->draft_stride, p->gamma);
+  struct { const void* ptr; size_t al; const char* name; bool need; } t[] = {
+      {p->source, 8, "source", p->L_src > 0}, {p->labels, 8, "labels", true}, {p->cache_seqlens, 4, "cache_seqlens", true},
+      {p->tok, 8, "tok", true}, {p->seen_eos, 1, "seen_eos", true}, {p->draft, 8, "draft", true},
+      {p->src_seqlens, 4, "src_seqlens", false}, {p->n_proposed, 4, "n_proposed", false}};
+  for (const auto& e : t)
+    if ((e.need && !e.ptr) || (reinterpret_cast<uintptr_t>(e.ptr) % e.al))
+      return fail(FAT5_EINVAL, "%s: %s: %smisaligned pointer", what, e.name, e.need ? "null or " : "");
+  if (p->B == 0) return FAT5_OK;
+  LookupArgs a = {};
+  a.source = p->source;
+  a.source_stride = p->source_stride;
+  a.src_seqlens = p->src_seqlens;
+  a.labels = p->labels;
+  a.labels_stride = p->labels_stride;
+  a.cache_seqlens = p->cache_seqlens;
+  a.tok = p->tok;
+  a.seen_eos = p->seen_eos;
+  a.draft = p->draft;
+  a.draft_stride = p->draft_stride;
+  a.n_proposed = p->n_proposed;
+  a.L_src = p->L_src, a.ncols = p->ncols, a.gamma = p->gamma, a.N = p->max_ngram, a.V = p->V;
+  hipStream_t stream = (hipStream_t)stream_;
+  hipLaunchKernelGGL(lookup_draft_kernel, dim3(p->B), dim3(LOOKUP_THREADS), 0, stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "lookup_draft launch");
   return FAT5_OK;
 }
 

@@ -34,6 +34,8 @@ loop then starts from the prompt's last token.  `decode_chunk` is also the verif
 Speculative greedy decoding (`assistant_model`; flasht5_amd/speculative.py): a second, cheaper model drafts gamma
 tokens per round, one `decode_chunk` step of gamma + 1 rows checks them, and the verification kernel accepts, rolls the per-row
 lengths back and does the step's bookkeeping on the device.  Without an assistant none of it runs: the code path above is unchanged.
+With `prompt_lookup_num_tokens` (flasht5_amd/prompt_lookup.py) the drafter is no model but ONE launch per round that
+searches input_ids and the row's own sequence for the row's last n-gram and proposes what followed it; the same rounds otherwise.
 
 Padding (`attention_mask`, `decoder_attention_mask`): right-padded masks are validated with one host read before an
 encoder runs (`check_padding`).  The encoder then sees only each row's valid keys (packed through `flash_attn_varlen_func` under
@@ -510,7 +512,7 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
              top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
              return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None,
              decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
-             decoder_attention_mask=None, kv_cache_dtype=None):
+             decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -575,7 +577,19 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     float8_e4m3fn bytes with one fp32 scale per (row, position, head), (D + 4) / (2 D) of the bytes.  Rows are quantised as they
     are appended, by the decode kernels; the encoder's K / V once.  All modes and graph=True work with it; the tokens can differ
     from the default's where two logits are within the quantisation error.  Any other value raises ValueError before an
-    encoder runs."""
+    encoder runs.
+
+    `prompt_lookup_num_tokens` = gamma in [1, 15] (HF's name; None: everything above, unchanged -- no launch, no allocation is
+    added): speculative greedy decoding without a second model (flasht5_amd/prompt_lookup.py).  Per round ONE launch
+    proposes, per row, the gamma tokens that followed the earliest, longest occurrence (up to `max_matching_ngram_size` = N in
+    [1, 16] tokens, HF's name) of the row's last n-gram in input_ids -- inside `attention_mask`: padding is never proposed -- or
+    in the row's own sequence, the decoder prompt included; the chunk step and the verification kernel are those of
+    `assistant_model`, so the result is what the call returns without it, with the same caveat.  graph=True captures one whole
+    round after the first eager one; decoder_input_ids, kv_cache_dtype and return_stats work as with an assistant (`drafted`
+    counts the tokens the lookup proposed for unfinished rows, `accepted` those of them that became output).  Rejected on the
+    host before the encoder runs: an assistant_model beside it, do_sample=True, num_beams > 1, any active logits processor, a
+    ragged decoder prompt, a non-int or out-of-range prompt_lookup_num_tokens / max_matching_ngram_size, a model the decode
+    path refuses, RoPE at B > 1, and a cache beyond the rotary tables."""
     check_kv_cache_dtype(kv_cache_dtype)
     from .beam import check_args as check_beam_args
     check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample)
@@ -584,10 +598,18 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     if dec_pad is not None:
         if assistant_model is not None:
             raise ValueError("generate: decoder_attention_mask (a ragged decoder prompt) with assistant_model is not supported")
+        if prompt_lookup_num_tokens is not None:
+            raise ValueError("generate: decoder_attention_mask (a ragged decoder prompt) with prompt_lookup_num_tokens is not supported")
         if model.decoder.block[0].self_attention_layer.self_attention.rotary and input_ids.shape[0] > 1:
             raise ValueError("generate: a ragged decoder prompt with RoPE needs B = 1: the decode path keeps one rotary position "
                              f"for the batch, and the rows of this one start at {dec_pad.lengths}")
     proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, P)
+    if prompt_lookup_num_tokens is not None:
+        from .speculative import check_lookup_generate_args, speculative_generate
+        check_lookup_generate_args(model, input_ids, max_length, prompt_lookup_num_tokens, max_matching_ngram_size, P, do_sample,
+                                   num_beams, proc is not None, assistant_model)
+        return speculative_generate(model, None, input_ids, attention_mask, max_length, graph, prompt_lookup_num_tokens, P,
+                                    decoder_input_ids, bool(return_stats), kv_cache_dtype, lookup_ngram=max_matching_ngram_size)
     if assistant_model is not None:
         from .speculative import check_generate_args, speculative_generate
         check_generate_args(model, assistant_model, input_ids, max_length, num_assistant_tokens, P, do_sample, num_beams,

@@ -6,6 +6,7 @@ row on the device.  The output is what greedy decoding without a drafter gives.
     n_accepted, n_new = speculative_accept(logits, draft, cache_seqlens, labels, tok, seen_eos, limit, draft_seqlens=None)
     n_accepted, n_new = speculative_round(model, state, tok, draft, labels, seen_eos, limit, draft_state=None)
     labels = model.generate(input_ids, max_length=64, assistant_model=small, num_assistant_tokens=4, graph=True)
+    labels = model.generate(input_ids, max_length=64, prompt_lookup_num_tokens=4, graph=True)   # (no second model: prompt_lookup.py)
 
 The invariant at every round boundary, per row b with len_b = cache_seqlens[b]: the self-attention caches of both models hold the
 K / V of labels[b, :len_b], and tok[b] = labels[b, len_b] is pending (decided, not yet run through either decoder).  A round
@@ -195,8 +196,14 @@ def check_generate_args(model, assistant_model, input_ids, max_length, num_assis
         raise ValueError(f"{what}: vocabulary mismatch, the model has {V} ids and the assistant {Va}")
     _check_supported(model)
     _check_supported(assistant_model)
-    cap = int(prompt_length) + int(max_length) + int(num_assistant_tokens) + 1
-    for name, m in (("the model", model), ("the assistant", assistant_model)):
+    _check_rotary(what, (("the model", model), ("the assistant", assistant_model)), input_ids, max_length, num_assistant_tokens,
+                  prompt_length)
+
+
+def _check_rotary(what, models, input_ids, max_length, gamma, prompt_length, gamma_name="num_assistant_tokens"):
+    """the two RoPE limits of a speculative loop, whatever drafts: one rotary position per batch, and the tables' rows"""
+    cap = int(prompt_length) + int(max_length) + int(gamma) + 1
+    for name, m in models:
         first = m.decoder.block[0].self_attention_layer.self_attention
         if not first.rotary:
             continue
@@ -204,42 +211,83 @@ def check_generate_args(model, assistant_model, input_ids, max_length, num_assis
             raise ValueError(f"{what}: {name} uses RoPE and the batch holds {input_ids.shape[0]} rows; rows advance raggedly and the "
                              "decode path keeps one rotary position for the batch (B = 1 only)")
         if cap > first.pe_encoding.max_sequence_length:
-            raise ValueError(f"{what}: the cache of {cap} positions (prompt + max_length + num_assistant_tokens + 1) exceeds the "
+            raise ValueError(f"{what}: the cache of {cap} positions (prompt + max_length + {gamma_name} + 1) exceeds the "
                              f"rotary tables' {first.pe_encoding.max_sequence_length} rows of {name}")
+
+
+def check_lookup_generate_args(model, input_ids, max_length, prompt_lookup_num_tokens, max_matching_ngram_size, prompt_length,
+                               do_sample, num_beams, processors_active, assistant_model=None):
+    """`generate(prompt_lookup_num_tokens=...)`'s host-side rejections, before the encoder runs"""
+    from .generation import _check_supported
+    from .prompt_lookup import check_args as check_lookup_args
+    what = "generate: prompt_lookup_num_tokens (prompt-lookup speculative decoding)"
+    if assistant_model is not None:
+        raise ValueError(f"{what} together with assistant_model is not supported: a round has one drafter")
+    if do_sample:
+        raise ValueError(f"{what} with do_sample=True is not supported: the verification is greedy (argmax against argmax)")
+    if num_beams > 1:
+        raise ValueError(f"{what} with num_beams > 1 is not supported")
+    if processors_active:
+        raise ValueError(f"{what} with logits processors (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens) "
+                         "is not supported: the chunk's rows would each need the sequence up to their own position")
+    check_lookup_args(prompt_lookup_num_tokens, max_matching_ngram_size, None, "generate",
+                      ("prompt_lookup_num_tokens", "max_matching_ngram_size"))
+    if not all(hasattr(model, a) for a in ("encoder", "decoder", "shared", "lm_head")):
+        raise ValueError(f"{what} must be called on a FAT5ForConditionalGeneration, got {type(model).__name__}")
+    _check_supported(model)
+    _check_rotary(what, (("the model", model),), input_ids, max_length, prompt_lookup_num_tokens, prompt_length,
+                  "prompt_lookup_num_tokens")
 
 
 @torch.no_grad()
 def speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, prompt_length,
-                         decoder_input_ids, return_stats, kv_cache_dtype=None):
-    """`generate`'s speculative loop (the arguments are checked already): per round gamma + 1 draft steps, one chunk step of the
-    target and the verification kernel, then ONE host read (`seen_eos.all()`), as the plain loop does once per token"""
+                         decoder_input_ids, return_stats, kv_cache_dtype=None, lookup_ngram=None):
+    """`generate`'s speculative loop (the arguments are checked already): per round the drafter, one chunk step of the target
+    and the verification kernel, then ONE host read (`seen_eos.all()`), as the plain loop does once per token.  The drafter is
+    the assistant model (gamma + 1 draft steps) or, with `assistant_model=None`, the prompt lookup (ONE launch over
+    input_ids and the rows' own sequences, `lookup_ngram` = N; no second model, no second state).  `attention_mask` is the validated
+    `Padding` or None; its device lengths keep the padding of input_ids out of the lookup"""
     from .generation import _capture_call, decode_chunk, finish_labels, init_decode_state
+    lookup = assistant_model is None
     gamma, P, T_max = int(num_assistant_tokens), int(prompt_length), int(max_length)
     B, dev = input_ids.shape[0], input_ids.device
     # capacity P + max_length + gamma + 1: a row at its last free column still appends a whole chunk before the roll-back
     kv = {} if kv_cache_dtype is None else dict(kv_cache_dtype=kv_cache_dtype)   # (both models' caches take the dtype)
     state = init_decode_state(model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P, **kv)
-    dstate = init_decode_state(assistant_model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P, **kv)
+    dstate = None if lookup else init_decode_state(assistant_model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P, **kv)
     labels = torch.zeros((B, P + T_max), dtype=torch.long, device=dev)
     limit = P - 1 + T_max
     tok = torch.zeros((B,), dtype=torch.long, device=dev)
     seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)
     draft = torch.zeros((B, gamma), dtype=torch.long, device=dev)
-    stats = torch.zeros((2,), dtype=torch.long, device=dev) if return_stats else None  # (live rows, accepted drafts)
+    # (live rows, accepted drafts) with an assistant; (proposed tokens, accepted ones) with the lookup
+    stats = torch.zeros((2,), dtype=torch.long, device=dev) if return_stats else None
+    if lookup:
+        from .prompt_lookup import prompt_lookup_draft
+        source = input_ids.to(torch.int64).contiguous()
+        src_seqlens = None if attention_mask is None else attention_mask.lengths_dev
+        N, V = int(lookup_ngram), int(model.lm_head.weight.shape[0])
     if decoder_input_ids is not None:
         prompt = decoder_input_ids.to(dev)
         labels[:, :P] = prompt
         tok.copy_(prompt[:, P - 1])
         if P > 1:
             decode_chunk(model, state, prompt[:, :P - 1], logits="none")
-            decode_chunk(assistant_model, dstate, prompt[:, :P - 1], logits="none")
+            if not lookup:
+                decode_chunk(assistant_model, dstate, prompt[:, :P - 1], logits="none")
 
     def one_round():
-        if stats is not None:
-            stats[0].add_((~seen_eos).sum())
-        draft_tokens(assistant_model, dstate, tok, draft)
+        if lookup:
+            _, n_prop = prompt_lookup_draft(source, labels, state.cache_seqlens, tok, seen_eos, gamma, N, src_seqlens, V, out=draft)
+        else:
+            if stats is not None:
+                stats[0].add_((~seen_eos).sum())
+            draft_tokens(assistant_model, dstate, tok, draft)
         n_acc, _ = speculative_round(model, state, tok, draft, labels, seen_eos, limit, draft_state=dstate)
         if stats is not None:
+            if lookup:  # (a finished row proposes nothing; a filler the target agrees with is no accepted draft)
+                stats[0].add_(n_prop.sum())
+                n_acc = torch.minimum(n_acc, n_prop)
             stats[1].add_(n_acc.sum())
 
     rounds = 0
@@ -260,6 +308,6 @@ def speculative_generate(model, assistant_model, input_ids, attention_mask, max_
     T = int(state.cache_seqlens.max()) - (P - 1)  # the most new tokens any row produced
     out = finish_labels(labels[:, :P + T])
     if return_stats:
-        live, acc = stats.tolist()
-        return out, dict(rounds=rounds, drafted=live * gamma, accepted=acc)
+        first, acc = stats.tolist()
+        return out, dict(rounds=rounds, drafted=first if lookup else first * gamma, accepted=acc)
     return out

@@ -750,6 +750,54 @@ size_t fat5_spec_accept_workspace_bytes(const fat5_spec_params* p);
 int fat5_spec_accept(const fat5_spec_params* p, void* hip_stream);
 
 /*
+ * Prompt-lookup drafting for speculative greedy decoding (lookup_kernels.h): per row, the draft of the next
+ * verification round is what followed the row's last n-gram the first time it occurred, in the encoder input or in the row's own
+ * sequence.  Per row b, with len = cache_seqlens[b]:
+ *   the own sequence is s[0 .. len], s[i] = labels[b, i] for i < len and s[len] = tok[b] (the pending token is taken from tok,
+ *   never from labels); Ls = clamp(src_seqlens[b], 0, L_src) (L_src when src_seqlens is NULL) and x = source[b, 0 .. Ls - 1];
+ *   a row with seen_eos[b] set, or with len outside [0, ncols - 1], proposes nothing and reads neither labels nor source;
+ *   a source position e in [0, Ls - 2] has the match length m = the largest m <= min(N, e + 1, len + 1) with
+ *   x[e - i] == s[len - i] for all i < m; an own position e in [0, len - 1] has m = the largest m <= min(N, e + 1) with
+ *   s[e - i] == s[len - i] for all i < m (N = max_ngram).  A match never runs across the seam between the two sequences, and
+ *   a candidate always has at least one token after it;
+ *   the winner is the candidate with the largest m >= 1; at equal m a source candidate beats an own candidate, and within one
+ *   sequence the smallest e wins (the first match).  Without a candidate the row proposes nothing;
+ *   the continuation is x[e + 1 .. min(e + gamma, Ls - 1)] for a source winner and s[e + 1 .. min(e + gamma, len)] for an own
+ *   winner, cut before its first id outside [0, V) (V == 0: no id is cut); c is its length;
+ *   draft[b, j] = continuation token j for j < c and tok[b] for c <= j < gamma; n_proposed[b] = c (may be NULL).
+ * No address outside source[b, 0 .. L_src - 1], labels[b, 0 .. ncols - 1] and draft[b, 0 .. gamma - 1] is touched, whatever
+ * cache_seqlens and src_seqlens hold.  All outputs are integers: the result is bitwise reproducible and independent of any order
+ * of evaluation (an integer maximum, no atomics).  One launch on `hip_stream`, grid B, no workspace; nothing is read back by the
+ * host.  B == 0 is a no-op.
+ * Rejected with FAT5_EINVAL before anything is launched: NULL params, B < 0 or > 65535, L_src outside [0, 2^20], ncols outside
+ * [1, 2^20], gamma outside [1, 15], max_ngram outside [1, 16], V < 0, source_stride < L_src, labels_stride < ncols,
+ * draft_stride < gamma, NULL or misaligned labels / cache_seqlens / tok / seen_eos / draft, a NULL source with L_src > 0,
+ * misaligned source / src_seqlens / n_proposed.
+ */
+typedef struct fat5_lookup_params {
+  int32_t B;
+  int32_t L_src;                /* 0 .. 2^20 columns of source */
+  int32_t ncols;                /* 1 .. 2^20 columns of labels */
+  int32_t gamma;                /* 1 .. 15 draft tokens per row */
+  int32_t max_ngram;            /* N, 1 .. 16 */
+  int32_t V;                    /* the vocabulary size, or 0: no id is cut */
+  const int64_t* source;        /* (B, L_src) int64 device array, row stride source_stride elements; may be NULL when L_src is 0 */
+  int64_t source_stride;
+  const int32_t* src_seqlens;   /* (B,) int32 device array, or NULL: L_src for every row */
+  const int64_t* labels;        /* (B, ncols) int64 device array, row stride labels_stride elements */
+  int64_t labels_stride;
+  const int32_t* cache_seqlens; /* (B,) int32 device array */
+  const int64_t* tok;           /* (B,) int64 device array: the pending token of every row */
+  const uint8_t* seen_eos;      /* (B,) one byte per row (torch.bool) */
+  int64_t* draft;               /* (B, gamma) int64 device array, row stride draft_stride elements */
+  int64_t draft_stride;
+  int32_t* n_proposed;          /* (B,) int32 device array or NULL */
+} fat5_lookup_params;
+/* sizeof(fat5_lookup_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_lookup_params(void);
+int fat5_lookup_draft(const fat5_lookup_params* p, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)

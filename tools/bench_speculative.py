@@ -12,7 +12,15 @@ process after a warm-up of both, timed with device events; tokens per second of 
 speculative run; and whether the two outputs are equal.  The condition a gain is expected under,
     (gamma + 1) draft steps + one chunk step  <  (mean accepted + 1) target steps,
 is reported beside every line from graph replays of the three steps timed on their own (`lhs_ms`, `rhs_ms`).
-The log goes to --log (default profiles/speculative_bench.log); one JSON line is printed at the end."""
+The log goes to --log (default profiles/speculative_bench.log); one JSON line is printed at the end.
+
+--lookup: the prompt-lookup drafter (`generate(prompt_lookup_num_tokens=gamma)`) instead of the model drafter, on
+the same target.  The greedy output is the target's permutation chain from the start token; a chosen share of it (the first
+share * 16 tokens of every 16) is written into input_ids, so that share of the output can be copied from the encoder input and
+the rest cannot.  B in {1, 8}, gamma in {2, 4, 8}, share in {1.0, 0.5, 0.0}, max_matching_ngram_size 2; the same alternation
+with plain greedy `generate(graph=True)`; the lookup launch's own time and both sides of
+    one lookup launch + one chunk step  <  (mean accepted + 1) target steps
+from graph replays timed alone.  The log goes to profiles/prompt_lookup_bench.log."""
 import json
 import os
 import statistics
@@ -108,9 +116,94 @@ def step_times(model, assistant, ids, gamma, it=50):
     return out
 
 
+def lookup_time(ids, gamma, ngram, V, it=200):
+    """graph replays of the lookup launch alone, in ms: sequences half full, every row live"""
+    from flasht5_amd import prompt_lookup_draft
+    B = ids.shape[0]
+    labels = torch.randint(2, V, (B, 1 + NEW), device="cuda")
+    lens = torch.full((B,), NEW // 2, dtype=torch.int32, device="cuda")
+    tok = ids[:, 200].clone()
+    seen = torch.zeros((B,), dtype=torch.bool, device="cuda")
+    draft = torch.zeros((B, gamma), dtype=torch.long, device="cuda")
+    one = lambda: prompt_lookup_draft(ids, labels, lens, tok, seen, gamma, ngram, vocab_size=V, out=draft)  # noqa: E731
+    one()
+    g = _capture_call(one)
+    for _ in range(3):
+        g.replay()
+    ms, _ = timed(lambda: [g.replay() for _ in range(it)])
+    del g
+    return ms / it
+
+
+def copy_inputs(sigma, B, V, share, seed):
+    """random input_ids with `share` of the greedy output (the chain from the start token 0) written into them, in runs"""
+    ids = torch.randint(2, V, (B, L_ENC), generator=torch.Generator().manual_seed(seed))
+    t = 0
+    for k in range(NEW):
+        t = int(sigma[t])
+        if k % 16 < round(16 * share):
+            ids[:, 100 + k] = t
+    return ids.cuda()
+
+
+def main_lookup(path, quick):
+    global _log
+    NGRAM = 2
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    _log = open(path, "w")
+    base = FAT5Config()
+    torch.manual_seed(0)
+    model = FAT5ForConditionalGeneration(base).cuda().bfloat16().eval()
+    V = base.vocab_size
+    sigma = sigma_without_eos(V, 1000)
+    decisive(model, sigma)
+    say(f"# prompt lookup: target {base.num_decoder_layers} + {base.num_layers} layers, bf16, L_enc {L_ENC}, {NEW} new tokens, "
+        f"max_matching_ngram_size {NGRAM}, graph=True, {REPS} alternating repeats (median, spread = max - min)")
+    rows = {}
+    with torch.no_grad():
+        for B in ((1,) if quick else (1, 8)):
+            for gamma in ((4,) if quick else (2, 4, 8)):
+                probe = copy_inputs(sigma, B, V, 1.0, B)
+                t_step, _, t_chunk = step_times(model, model, probe, gamma)
+                t_lookup = lookup_time(probe, gamma, NGRAM, V)
+                for share in ((1.0,) if quick else (1.0, 0.5, 0.0)):
+                    ids = copy_inputs(sigma, B, V, share, B)
+                    plain = lambda: model.generate(ids, max_length=NEW, graph=True)  # noqa: E731
+                    spec = lambda: model.generate(ids, max_length=NEW, graph=True, prompt_lookup_num_tokens=gamma,  # noqa: E731
+                                                  max_matching_ngram_size=NGRAM, return_stats=True)
+                    ref, (got, st) = plain(), spec()   # warm-up of both
+                    tp, ts = [], []
+                    for _ in range(REPS):
+                        tp.append(timed(plain)[0])
+                        ts.append(timed(spec)[0])
+                    (mp, sp), (ms, ss) = med_spread(tp), med_spread(ts)
+                    T = ref.shape[1] - 1
+                    mean_acc = st["accepted"] / max(1, st["rounds"] * B)
+                    lhs, rhs = t_lookup + t_chunk, (mean_acc + 1) * t_step
+                    faster = max(ts) < min(tp)
+                    rows[f"B{B}_g{gamma}_c{share}"] = dict(
+                        plain_ms=round(mp, 2), plain_spread_ms=round(sp, 2), spec_ms=round(ms, 2), spec_spread_ms=round(ss, 2),
+                        plain_tok_s=round(B * T / mp * 1e3, 1), spec_tok_s=round(B * (got.shape[1] - 1) / ms * 1e3, 1),
+                        accepted=st["accepted"], drafted=st["drafted"], rounds=st["rounds"], same_tokens=bool(torch.equal(ref, got)),
+                        step_ms=round(t_step, 3), lookup_ms=round(t_lookup, 4), chunk_ms=round(t_chunk, 3), lhs_ms=round(lhs, 3),
+                        rhs_ms=round(rhs, 3), expected=lhs < rhs, faster=faster)
+                    say(f"B={B} gamma={gamma} copy={share:.1f}: plain {mp:8.2f} ms (spread {sp:6.2f}) {B * T / mp * 1e3:8.1f} tok/s | "
+                        f"lookup {ms:8.2f} ms (spread {ss:6.2f}) {B * (got.shape[1] - 1) / ms * 1e3:8.1f} tok/s | "
+                        f"accepted {st['accepted']} / drafted {st['drafted']} in {st['rounds']} rounds | same tokens {torch.equal(ref, got)} | "
+                        f"lookup {t_lookup * 1e3:5.1f} us + chunk = {lhs:6.3f} ms {'<' if lhs < rhs else '>='} (acc+1) steps {rhs:6.3f} ms | "
+                        f"{'faster' if faster else 'NOT faster'}")
+    say(json.dumps(rows))
+    _log.close()
+
+
 def main():
     global _log
     assert torch.cuda.is_available(), "this benchmark needs the GPU (there is no CPU path)"
+    if "--lookup" in sys.argv:
+        path = os.path.join(ROOT, "profiles", "prompt_lookup_bench.log")
+        if "--log" in sys.argv:
+            path = sys.argv[sys.argv.index("--log") + 1]
+        return main_lookup(path, "--quick" in sys.argv)
     path = os.path.join(ROOT, "profiles", "speculative_bench.log")
     if "--log" in sys.argv:
         path = sys.argv[sys.argv.index("--log") + 1]
