@@ -5,13 +5,14 @@ the truth.  CPU only; imports no GPU code.  Used by tests/test_attn_bwd_fp64_cpu
 
 Covered: the 32-wide bodies of csrc/attn_bwd.h (dq=32row, dkdv=32key) at every head dimension, as separate launches and in the
 one-launch form (fused=1), with their bias gradients: dense dbias by the routes "direct", "staged" and "inkernel", drpe1d and the T5
-table gradient in both reduction forms (dtable=runs / scan).
-Not covered: the 64-wide bodies (dq=64row, 64row-batch4; dkdv=64key, 64key-half, 64key-mixed; their one-launch forms; qdiag=1; the
-dbias routes "dq-kernel" and "dq-kernel+partials").  Their derivation (statistics as accumulator initial values, the bias on the matrix
-pipe, the LDS merges, the diagonal sums of the pipelined steps) is not written: `attn_bwd_bound` raises for them, and the case list holds
-none.  They stay with the max-norm tests (tests/test_bwd64_gpu.py, test_dense64_gpu.py, test_qdiag_gpu.py).  Also left to the existing
-tests: the packed (cu_seqlens) layout, unit ranges, zero and negative sm_scale, head dimensions and dtypes the dispatcher rejects, the
-forward, any timing.
+table gradient in both reduction forms (dtable=runs / scan).  And the non-dense 64-wide bodies of csrc/attn_bwd64.h at D = 64, bias none
+and rpe1d / T5 table: dq=64row; dkdv=64key, 64key-half, 64key-mixed:*; separate launches (the statistics from either dQ kernel, so
+also the mixed pairs 32row + 64key and 64row + 32key) and the one-launch form (fused=1: attn_bwd_fused64_kernel, the dK/dV half in its
+SELF form); qdiag=0 / 1; dtable=runs / scan.  Their derivation is the section "The 64-wide bodies" below.
+Not covered: the DENSE 64-wide bodies (dq=64row-batch4; the DENSE form of the 64-key body; the dense one-launch form; the dbias routes
+"dq-kernel" and "dq-kernel+partials"): `attn_bwd_bound` raises for them, the case list holds none, and they stay with the max-norm tests
+(tests/test_dense64_gpu.py).  Also left to the existing tests: the packed (cu_seqlens) layout, unit ranges, zero and negative sm_scale,
+head dimensions and dtypes the dispatcher rejects, the forward, any timing.
 
 The restatement.  Per (b, h), in fp64, from the given o and lse:  p = exp(s - lse) on visible keys, exact 0 elsewhere (a dense bias
 entry <= -1e38 is a masked key; a row with lse < -1e30 -- kDeadRowLse, c:180: -inf, or the clamp of a fully masked row -- is dead: p, dS,
@@ -57,6 +58,53 @@ summation constant.  Lines cited as b:LINE (csrc/attn_bwd.h), c:LINE (attn_commo
       pack8): no u_T.  Band blocks add every element into U and the borrowed ones also into B, and take U - B (ds:50-59, ds:99): each term
       enters up to twice; then the carries, the wave sum (b:822), the per-wave arrays (b:833) and the partial rows (r:115-146, or r:192-217
       per bucket run): gamma_1(2 n + 8) for n terms.  Stored as fp32: no output rounding.
+The 64-wide bodies (k:LINE = csrc/attn_bwd64.h).  Same restatement, same T / TA / TD; what differs is where a rounding enters.
+  Statistics as accumulator initial values.  The 64-key body starts S' at -L / scale and dP' at -delta (k:505-506, k:712-717).  Both dQ
+      kernels write them as ONE fp32 quotient -L / scale (k:1250, b:120) and -delta (k:1251, b:121); the
+      SELF form makes them itself, 8 rows per wave two steps ahead (k:319-345, k:722-724): nis = -1 / scale (k:317) and L * nis (k:339),
+      two roundings.  Either way the error of 1 / scale and of the product is at most 2 u |L| / scale in S' units, i.e. 2 u |L| log2e <=
+      2 u A_i after the FMA by c2 = scale * log2e (k:451): the term on TA the 32-key derivation already holds (its "reciprocal and its
+      product 2 u"); a scale whose reciprocal is inexact (0.3) only makes that 2 u real.  Then D MFMA additions of at most
+      (smag + |L|) / scale: 2 D u A; c2: 2 u; the table entry * log2e: 2 u bmag; one FMA: u.  2 D + 7 <= 2 D + 9: the same kap, cA.
+      delta: the 64-row dQ kernel's fmaf chain over the lane's 32 elements and a pair sum (k:1233-1243); SELF: 8 fmaf and a three-stage
+      butterfly over 8 lanes (k:329-337); both at most D u sum |o do| -- on TD as before.  The statistics pass through fp32 memory: exact.
+      dQ body: -delta is the MFMA's C operand in the pipelined iteration (k:1599) and, in the general one, three 16-bit pieces
+      hi + mid + lo through one more MFMA ones x D3 (k:1255-1260, k:1454): exact in bf16 (3 x 8 bits); in fp16 the last piece may be
+      subnormal: 2^-25 absolute on dP', times p <= 1: one more 2^-25 per term (S_dq, and the count of a diagonal sum formed there).
+      The extra MFMA is up to two more additions: e_dS(64row) = 2^-23 + (2 D + 5) u.
+  Pipelined against general iterations.  dK/dV: far trips x = fma(S', c2, cst) with the tile-constant table entry (k:820), band trips
+      fma(S', c2, entry) (k:819), the general stage the same FMA (k:578-581) or S' * c2 without a bias (k:585): one rounding each.  dQ: far
+      trips fma(s, c2, cst + nL2) with the sum formed once per trip (k:1723, k:1573), band trips one v_add entry + nL2 then the FMA
+      (k:1569-1571), the general stage fmaf(s, c2, entry + nl) (k:1487-1494): one add, one FMA, as b:237-244.  No iteration rounds more
+      than the constants above allow, so the bound is not per step kind.  p = v_exp_f32 (k:818, k:590, k:1497, k:1576), dS = p * dP': u.
+  The causal mask.  No bias: the C operand of the score MFMAs is -inf (of the scale's sign) where the key is masked (k:495-498, k:736-743):
+      exp2 gives an exact 0 and dS = 0 * dP' an exact 0; the general steps select 0 (k:602-603, k:1504).  causal_in_band: the table
+      itself holds -inf above the diagonal (k:134, k:367).  Dead rows and rows past M: -L / scale = -inf (k:338-339, k:1249-1250).
+      Exact zeros above the diagonal and on dead rows; the bound there is 0.
+  P and dS rounded to the dtype before the contractions (k:608-609, k:687-689, k:1507, k:1580): u_T each and the fp16 absolute term, as in
+      the 32-wide bodies.  Contractions on the matrix pipe over the M rows (k:552-554, k:699-700) / the N keys (k:1468, k:1590):
+      gamma_2(M + 1) / gamma_2(N + 1), any order -- the split of the steps over two wave pairs included.
+  The hand-over of the half-length variant: the second pair's dK^T / dV^T through LDS, added in fp32 (k:1006, k:1033-1034): + u.
+  The output path: * scale (dk, dq: k:1059-1060, k:1092-1093, k:1773-1774, k:1795-1796), one rounding (pack2), whole rows staged through
+      LDS bit for bit (k:1063-1075, k:1775-1782): u and the final half ulp, as before.
+  The diagonal sums.  General steps add the fp32 dS (`s` before pack8: k:612-614, k:1509-1511).  Band steps of the pipelined iteration
+      ALSO add the fp32 dS: diag_el / stE_ read Dv[E], the product of asm_mul, not the packed words (k:680-684, k:833, k:1562-1566,
+      k:1648) -- the comment at k:651 ("the per-diagonal sums of the step's rounded dS ... diag_sums on DS") describes an earlier form.
+      Far trips are summed from the ROUNDED dS by ones . dS MFMAs (k:484-487, k:848-858, k:1662-1674): u_T per term, and 2^-25 per term
+      in fp16.  Far trips only ever feed the two far bins (k:941, k:1731), so the u_T term is carried on TF, the T of entries 0 and 2 R
+      (through the bucket map for the table): u_T (TF + err).  qdiag=1 (k:1133-1140, k:1295-1321): the same arithmetic with rows and keys
+      exchanged, in the dQ body: its e_dS and, in fp16, its -delta pieces.  Summation: within an MFMA 2 u per addition, each term
+      once; U - B of the band blocks (ds:99) each term up to twice; then (f0 + f1) + (f2 + f3), * 1/16 exact (k:939, k:1729), the
+      per-trip adds, the carries, wave_sum (k:981-982), the eight private arrays (k:994, k:1821), the partial rows per 128- or 256-key
+      / 256-row block and the batch (r:115-146, r:192-217): all additions of partial sums of the entry's own n terms (or of exact zeros:
+      the zeroed row behind a 256-key workgroup of a mixed launch, k:996, adds nothing): gamma_1(2 n + 8) as for the 32-wide bodies.
+          c_dv = (1 + u_T) (1 + 2^-23 + gamma_2(M + 1) + [half, mixed: u]) - 1,   c_dk, c_dq as above with e_dS of their body
+          err_drpe = e_dS T + c_A TA + D u TD + u_T (TF + that) + [fp16: 2^-25 (nF + [qdiag=1: n])], then gamma_1(2 n + 8) (T + err)
+  The far bins' bound is therefore u_T times the magnitudes of tens of thousands of terms of both signs: it sees a wrong diagonal or a
+  missing band, but not one 32 x 64 block more or less in a large far bin (tests/test_attn_bwd_fp64_cpu.py lists those pairs).
+The step classification (`steps_kv64`, `steps_q64`) restates k:891-967 and k:1700-1753 on the host: which steps run in aligned trips of
+four (far-positive, far-negative, band, on the causal diagonal) and which run the general iteration.  The case list asserts its coverage
+with it, the emulation takes from it which dS feeds the far bins rounded, the mutants where a trip, a remainder or a pair's half lies.
 No constant is fitted to a measured error and nothing is put on top.  Where T = 0 (a dead row's dq, a dbias entry above the causal
 diagonal or under a masking bias entry, a diagonal no visible score lies on) the bound is 0 and the kernels must give an exact zero.
 """
@@ -83,7 +131,7 @@ def _knobs(B, H, M, N, D, R, causal, scale, bias, rpe1d, bucket):
                 red_b=bias is not None and bias.shape[0] == 1 and B > 1, red_h=bias is not None and bias.shape[1] == 1 and H > 1,
                 wq=torch.ones(N, dtype=torch.float64), wr=torch.ones(M, dtype=torch.float64), delta_shift=0, delta_true=False,
                 own_softmax=False, dk_noscale=False, dq_scale2=False, db_drop=False, db_dup=False, db_above=False, db_row_shift=0,
-                g_shift=0, g_far_band=False, g_head_shift=0, bucket_shift=0, ragged=False)
+                g_shift=0, g_far_band=False, g_head_shift=0, bucket_shift=0, ragged=False, lse_scale2=False, g_w=None, g_far_add=None, g_sign=1)
 
 
 def _bias_all(c, bias, rpe1d, R, M, N):
@@ -98,7 +146,7 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
     """q, o, do (B, H, M, D), k / v (B, H, N, D) in bf16 / fp16 (any strides); lse (B, H, M) fp32; bias dense (B|1, H|1, M, N) or None; rpe1d
     (H, 2R + 1) fp32 or None; bucket (2R + 1) int ids or None.  Returns a dict: for X in dq, dk, dv and, where they exist, dbias, drpe1d,
     drpe_table: X (fp64), T_X, TA_X, TD_X (see the module docstring; TA_dv / TD_dv: dv has no delta, TD_dv = 0); S_dv, S_dk, S_dq the fp16
-    absolute-term sums; nsum (dbias) and n_drpe1d / n_drpe_table term counts; per row (B, H, M): smag, bmag, lse_abs, smax / smin (the
+    absolute-term sums; nsum (dbias) and n_drpe1d / n_drpe_table term counts; TF_ / nF_ of drpe1d and the table: T and the count restricted to the two far bins; per row (B, H, M): smag, bmag, lse_abs, smax / smin (the
     extremes of s - lse over the live keys, 0 on rows without one), dsmax (the largest |dS_ij|), dead; applied (the mutant changed something
     a correct kernel computes)."""
     B, H, M, D = q.shape
@@ -122,6 +170,8 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
     ninf = torch.full_like(s, -math.inf)
     L_true = torch.logsumexp(torch.where(vis & ~masked, s, ninf), -1) if mutant is not None else None
     Lu = L_true if c["own_softmax"] else L
+    if c["lse_scale2"]:                                                 # S' = q k - L scale (k:1250, k:339 with the scale for its reciprocal)
+        Lu = Lu * (scale * scale)
     L0 = torch.where(dead, torch.zeros_like(L), Lu)
     x = torch.where(ok, s - L0[..., None], ninf)
     p = torch.exp(x)
@@ -186,17 +236,25 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
             out[tag + "_dbias"] = red(m)
         out["nsum"] = (B if bias.shape[0] == 1 else 1) * (H if bias.shape[1] == 1 else 1)
     # ---- drpe1d, drpe_table ----
+    gw = fadd = None
     if rpe1d is not None:
         n1 = 2 * R + 1
         rel = torch.arange(N)[None, :] - torch.arange(M)[:, None]
-        gidx = ((rel + c["g_shift"]).clamp(-R, R) + R).reshape(-1)
+        gidx = ((c["g_sign"] * rel + c["g_shift"]).clamp(-R, R) + R).reshape(-1)
         wg = (rel.abs() <= R).double() if c["g_far_band"] else torch.ones(M, N, dtype=torch.float64)
-        X = torch.stack([(dS * wg).sum(0)] + [m.sum(0) for m in mags])                   # (4, H, M, N), summed over the batch
+        gw = c["g_w"](B, H, M, N) if c["g_w"] is not None else None       # (B, H, M, N) weights of the dS terms in the diagonal sums
+        X = torch.stack([(dS * wg if gw is None else dS * wg * gw).sum(0)] + [m.sum(0) for m in mags])   # (4, H, M, N), summed over the batch
         g = torch.zeros(4, H, n1, dtype=torch.float64).index_add_(2, gidx, X.reshape(4, H, -1))
+        fadd = c["g_far_add"](M, N) if c["g_far_add"] is not None else None   # ((M, N) mask, bin): these dS terms once more, into a far bin
+        if fadd is not None:
+            g[0][:, fadd[1]] += (dS * fadd[0].double()).sum((0, 2, 3))
         if c["g_head_shift"]:
             g[0] = g[0].roll(c["g_head_shift"], 0)
         cnt = torch.zeros(n1, dtype=torch.float64).index_add_(0, gidx, okf.sum((0, 1)).reshape(-1) / H)
         out["drpe1d"], out["T_drpe1d"], out["TA_drpe1d"], out["TD_drpe1d"], out["n_drpe1d"] = g[0], g[1], g[2], g[3], cnt
+        far = torch.zeros(n1, dtype=torch.float64)                       # the two far bins (d <= -R, d >= R): what the 64-wide bodies sum from the rounded dS
+        far[0] = far[2 * R] = 1.0
+        out["TF_drpe1d"], out["nF_drpe1d"] = g[1] * far, (cnt * far)[None, :].expand(H, n1)
         if bucket is not None:
             bk0 = torch.as_tensor(bucket, dtype=torch.int64)
             bk = bk0[(torch.arange(n1) + c["bucket_shift"]).clamp(0, n1 - 1)]
@@ -207,6 +265,8 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
             t[1:].index_add_(1, bk0[inr0], g[1:].transpose(1, 2)[:, inr0])
             out["drpe_table"], out["T_drpe_table"], out["TA_drpe_table"], out["TD_drpe_table"] = t[0], t[1], t[2], t[3]
             out["n_drpe_table"] = torch.zeros(num_buckets, dtype=torch.float64).index_add_(0, bk0[inr0], cnt[inr0])[:, None].expand(num_buckets, H)
+            out["TF_drpe_table"] = torch.zeros(num_buckets, H, dtype=torch.float64).index_add_(0, bk0[inr0], out["TF_drpe1d"].T[inr0])
+            out["nF_drpe_table"] = torch.zeros(num_buckets, dtype=torch.float64).index_add_(0, bk0[inr0], (cnt * far)[inr0])[:, None].expand(num_buckets, H)
         out["n_drpe1d"] = cnt[None, :].expand(H, n1)
     if mutant is not None and exists:   # did the defect change anything a correct kernel would compute?
         vis0 = _visible(base, M, N)
@@ -226,6 +286,10 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
         ch = ch or (c["g_far_band"] and bool(((torch.arange(N)[None, :] - torch.arange(M)[:, None]).abs() > R)[None, None].logical_and(ok0).any()))
         ch = ch or (c["bucket_shift"] != 0 and bool((bk != bk0).any()) and bool(ok0.any()))
         ch = ch or (c["ragged"] and M >= 2 and bool(anyok[:, :, M - 2:].any()))
+        ch = ch or (c["lse_scale2"] and scale != 1.0 and bool(ok0.any()))
+        ch = ch or (c["g_sign"] != 1 and bool(ok0.any()))
+        ch = ch or (gw is not None and bool(((gw != 1) & ok0).any()))
+        ch = ch or (fadd is not None and bool((fadd[0][None, None] & ok0).any()))
         out["applied"] = bool(ch)
     return out
 
@@ -234,11 +298,155 @@ def outputs_of(ref):
     return [x for x in OUTPUTS if x in ref]
 
 
+KINDS = ("far-positive trip", "far-negative trip", "band trip", "causal-diagonal trip", "general step", "remainder behind the last trip",
+         "fewer steps than ring slots", "key-tail wave")
+
+
+def _walk(ns, far, band, masked, mk=None):
+    """the step loop both 64-wide bodies share (k:908-967, k:1716-1753): aligned trips of four steps -- far (one side, judged by the first
+    and the last step), then band -- and single general steps.  Returns [(first step, kind)] with kind in far+ / far- / band / diag /
+    general; a band trip (or, without a bias, a trip whose mask rides in the C operand: `mk`) that sees a masked score is `diag`."""
+    segs, j = [], 0
+    trip = lambda j: j + 4 <= ns and j % 4 == 0
+    while j < ns:
+        while mk is not None and trip(j) and mk(j):                      # (k:914-917: no bias, causal, dK/dV body only)
+            segs.append((j, "diag"))
+            j += 4
+        while trip(j) and far(j)[0] and far(j + 3)[0] and far(j)[1] == far(j + 3)[1]:   # (k:932, k:1721)
+            segs.append((j, "far+" if far(j)[1] > 0 else "far-"))
+            j += 4
+        fartrip = lambda j: trip(j) and far(j)[0] and far(j + 3)[0] and far(j)[1] == far(j + 3)[1]
+        while band is not None and trip(j) and band(j) and not fartrip(j):   # (k:946, k:1736)
+            segs.append((j, "diag" if masked(j) else "band"))
+            j += 4
+        if j < ns and not fartrip(j) and not (mk is not None and trip(j) and mk(j)):   # (k:922, k:957, k:1743)
+            segs.append((j, "general"))
+            j += 1
+    return segs
+
+
+def steps_kv64(M, N, R, causal, rpe, half=False):
+    """The dK/dV body's own classification of its 32-row query steps (attn_bwd64.h:244-256, :891-967), restated on the host: one entry per
+    (key block, wave, pair): dict(kw0, mt0, ns, segs).  BNK = 128 keys per workgroup in the half-length form (two pairs, each half of the
+    steps), 256 otherwise; a wave owns the 64 keys from kw0."""
+    P, out = N - M, []
+    ctab = rpe and causal and -R <= P < R                                # (k:134: the table carries the mask)
+    bnk = 128 if half else 256
+    for n0 in range(0, N, bnk):
+        for wp in range(bnk // 64):
+            kw0 = n0 + 64 * wp
+            m_lo = max(0, n0 - P) // 32 * 32 if causal else 0            # (k:245-246)
+            mt0, ns = m_lo // 32, (M + 31) // 32 - m_lo // 32
+            for pr in ((0, 1) if half else (0,)):
+                if half:                                                 # (k:250-256)
+                    hs = (ns + 1) // 2
+                    mt0p, nsp = mt0 + pr * hs, hs
+                else:
+                    mt0p, nsp = mt0, ns
+                mb = lambda j: (mt0p + j) * 32
+                tail = kw0 + 64 > N
+
+                def far(j):                                              # (k:893-903)
+                    fast = not tail and (not causal or kw0 + 63 <= mb(j) + P)
+                    if not rpe:
+                        return fast, -1
+                    fpos, fneg = kw0 - (mb(j) + 31) >= R, kw0 + 63 - mb(j) <= -R
+                    return fast and (fpos or fneg), (1 if fpos else -1)
+                allvis = lambda j: not tail and (not causal or ctab or kw0 + 63 <= mb(j) + P)   # (k:905)
+                masked = lambda j: causal and not kw0 + 63 <= mb(j) + P
+                segs = _walk(max(nsp, 0), far, allvis if rpe else None, masked, mk=None if rpe else (lambda j: not tail and not allvis(j)))
+                out.append(dict(kw0=kw0, n0=n0, pair=pr, mt0=mt0p, ns=max(nsp, 0), segs=segs, tail=kw0 < N < kw0 + 64, live=kw0 < N))
+    return out
+
+
+def steps_q64(M, N, R, causal, rpe):
+    """The dQ body's classification of its 32-key steps, per wave by its 64 rows (attn_bwd64.h:1170-1173, :1700-1753)"""
+    P, out = N - M, []
+    ctab = rpe and causal and -R <= P < R                                # (k:1169)
+    for m0 in range(0, M, 256):
+        n_end = min(N, m0 + 256 + P) if causal else N                    # (k:1170-1172)
+        nt = (n_end + 31) // 32 if n_end > 0 else 0
+        for w in range(4):
+            qw0 = m0 + 64 * w
+            if qw0 >= M:
+                continue                                                 # (its rows are stored nowhere)
+
+            def far(t):                                                  # (k:1701-1711)
+                nb = 32 * t
+                fast = nb + 32 <= N and (not causal or nb + 31 <= qw0 + P)
+                if not rpe:
+                    return fast, -1
+                fneg, fpos = nb + 31 - qw0 <= -R, nb - (qw0 + 63) >= R
+                return fast and (fneg or fpos), (-1 if fneg else 1)
+            allvis = lambda t: 32 * (t + 3) + 32 <= N and (not causal or ctab or 32 * (t + 3) + 31 <= qw0 + P)   # (k:1713, asked of the trip's LAST step: k:1736)
+            masked = lambda t: causal and not 32 * (t + 3) + 31 <= qw0 + P
+            segs = _walk(nt, far, allvis if rpe else None, masked)
+            out.append(dict(qw0=qw0, m0=m0, nt=nt, ns=nt, segs=segs, tail=nt * 32 > N, live=True))
+    return out
+
+
+def kinds_of(walks):
+    """which of KINDS occur in the walks of a body (steps_kv64 / steps_q64)"""
+    names = {"far+": "far-positive trip", "far-": "far-negative trip", "band": "band trip", "diag": "causal-diagonal trip", "general": "general step"}
+    got = set()
+    for wv in walks:
+        if not wv["live"]:
+            continue
+        if 0 < wv["ns"] < 4:
+            got.add("fewer steps than ring slots")
+        if wv["tail"]:
+            got.add("key-tail wave")
+        for j, kind in wv["segs"]:
+            got.add(names[kind])
+            if kind == "general" and wv["ns"] >= 4 and j >= wv["ns"] - wv["ns"] % 4 and any(k != "general" for _, k in wv["segs"]):
+                got.add("remainder behind the last trip")
+    return got
+
+
+def layout_of(bodies, M, N, R, causal, rpe):
+    """the step walks of the 64-wide bodies a case runs: dict(kv=[...] or None, q=[...] or None, kvh=[...] (the half-length walks of a mixed
+    launch) or None)"""
+    kv = bodies.get("dkdv", "")
+    lay = dict(kv=None, kvh=None, q=None)
+    if kv == "64key" or kv.startswith("64key-mixed"):
+        lay["kv"] = steps_kv64(M, N, R, causal, rpe)
+    if kv == "64key-half" or kv.startswith("64key-mixed"):
+        lay["kvh"] = steps_kv64(M, N, R, causal, rpe, half=True)
+    if bodies.get("dq") == "64row":
+        lay["q"] = steps_q64(M, N, R, causal, rpe)
+    return lay
+
+
+def far_rounded_mask(bodies, M, N, R, causal):
+    """(M, N) bool: the scores whose dS reaches the diagonal sums ROUNDED to the dtype -- those of the pipelined far trips of the body
+    that forms the sums (qdiag=1: the dQ body, k:1662-1674; else the dK/dV body, k:848-858).  In a mixed launch a key block runs in
+    either form; the 256-key walk is taken (its far trips are the longer ones)."""
+    m = torch.zeros(M, N, dtype=torch.bool)
+    lay = layout_of(bodies, M, N, R, causal, True)
+    if bodies.get("qdiag", "0") == "1":
+        for wv in lay["q"] or ():
+            for t, kind in wv["segs"]:
+                if kind[:3] == "far":
+                    m[wv["qw0"]:wv["qw0"] + 64, 32 * t:32 * t + 128] = True
+    else:
+        for wv in (lay["kv"] or lay["kvh"] or ()):
+            for j, kind in wv["segs"]:
+                if kind[:3] == "far":
+                    m[(wv["mt0"] + j) * 32:(wv["mt0"] + j) * 32 + 128, wv["kw0"]:wv["kw0"] + 64] = True
+    return m
+
+
 def attn_bwd_bound(ref, dtype, D, bodies, N, M):
     """{output: bound tensor} for an `attn_bwd_ref` result computed by the bodies `bodies` names (the dq=, dkdv=, fused=, dbias=, qdiag=,
     dtable= fields of fat5_attn_describe, as a dict) at head dimension D"""
-    if bodies.get("dq") != "32row" or bodies.get("dkdv") != "32key" or bodies.get("qdiag", "0") != "0":
-        raise NotImplementedError(f"not covered: {bodies} (the 64-wide bodies; see the module docstring)")
+    dqb, kvb, qdiag = bodies.get("dq"), bodies.get("dkdv", ""), bodies.get("qdiag", "0")
+    kv64, q64 = kvb == "64key" or kvb == "64key-half" or kvb.startswith("64key-mixed:"), dqb == "64row"
+    if dqb not in ("32row", "64row") or not (kvb == "32key" or kv64):
+        raise NotImplementedError(f"not covered: {bodies} (the dense 64-wide bodies; see the module docstring)")
+    if (kv64 or q64) and ("dbias" in ref or D != 64):
+        raise NotImplementedError(f"not covered: {bodies} with a dense bias (the DENSE form of the 64-key body, dq-kernel routes; see the module docstring)")
+    if qdiag != "0" and not (q64 and kv64):   # (QDG exists in the 64-row dQ body beside the NODIAG 64-key one only: k:104-105, k:1133)
+        raise NotImplementedError(f"not covered: {bodies}")
     fp16 = dtype == torch.float16
     uT = U_T[dtype]
     kap = LN2 * (2 * D + 9) * U32
@@ -248,17 +456,19 @@ def attn_bwd_bound(ref, dtype, D, bodies, N, M):
     assert not fp16 or float(ref["dsmax"].max() if ref["dsmax"].numel() else 0.0) < 60000.0, "dS would overflow fp16: outside the derivation"
     cA = kap * (1 + E_EXP) / (1 - 2.0 ** -7)
     e_ds = E_EXP + (2 * D + 1) * U32
+    e_ds_q64 = E_EXP + (2 * D + 5) * U32        # (-delta as three 16-bit pieces through one more MFMA in the general steps: k:1255-1260, k:1454)
+    hand = U32 if (kvb == "64key-half" or kvb.startswith("64key-mixed:")) else 0.0   # (the second pair's dK^T / dV^T added in fp32: k:1033-1034)
 
     def close(x, err):
         b = err + 0.5 * ulp(ref[x].abs() + err, dtype)
         return torch.where(ref["T_" + x] == 0, torch.zeros_like(b), b)
 
     out = {}
-    for x, n, e in (("dv", M, E_EXP), ("dk", M, e_ds + U32), ("dq", N, e_ds + U32)):
+    for x, n, e in (("dv", M, E_EXP + hand), ("dk", M, e_ds + U32 + hand), ("dq", N, (e_ds_q64 if q64 else e_ds) + U32)):
         cT = (1 + uT) * (1 + e + _gamma(n + 1, 2)) - 1
         err = cT * ref["T_" + x] + (1 + uT) * (cA * ref["TA_" + x] + D * U32 * ref["TD_" + x])
         if fp16:
-            err = err + 2.0 ** -25 * ref["S_" + x]
+            err = err + (2.0 if (x == "dq" and q64) else 1.0) * 2.0 ** -25 * ref["S_" + x]   # (64row: the last 16-bit piece of -delta is absolute too, k:1259)
         out[x] = close(x, err)
     if "dbias" in ref:
         route = bodies.get("dbias")
@@ -270,20 +480,32 @@ def attn_bwd_bound(ref, dtype, D, bodies, N, M):
             ns = ref["nsum"]
             err = (1 + uT) * err + uT * T + _gamma(ns) * (1 + uT) * T + (ns * 2.0 ** -25 if fp16 else 0.0)
         out["dbias"] = close("dbias", err)
+    wide_sums = q64 if qdiag == "1" else kv64    # the body that forms the diagonal sums: the dQ one (QDG) or the dK/dV one
     for x in ("drpe1d", "drpe_table"):
         if x in ref:
             T = ref["T_" + x]
-            err = e_ds * T + cA * ref["TA_" + x] + D * U32 * ref["TD_" + x]
+            err = (e_ds_q64 if (wide_sums and qdiag == "1") else e_ds) * T + cA * ref["TA_" + x] + D * U32 * ref["TD_" + x]
+            if wide_sums:
+                # the far bins of the pipelined trips are summed from the dS ROUNDED to the dtype (ones . dS MFMAs: k:484-487, k:848-858,
+                # k:1662-1674): u_T of every such term, at most the whole of the two far bins (TF); the band and the general steps add the
+                # fp32 dS (k:614, k:682-683 -- Dv, not the packed words --, k:1511, k:1564-1565)
+                err = err + uT * (ref["TF_" + x] + err)
+                if fp16:
+                    err = err + 2.0 ** -25 * ref["nF_" + x] + (2.0 ** -25 * ref["n_" + x] if qdiag == "1" else 0.0)
             g = 2 * ref["n_" + x] + 8
             err = err + (g * U32 / (1 - g * U32)) * (T + err)
             out[x] = torch.where(T == 0, torch.zeros_like(err), err)
     return out
 
 
-def emulate(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R=0, bucket=None, num_buckets=0, dbias_route="direct"):
-    """What the 32-wide bodies do arithmetically, in float32 torch ops (not in their summation order): scores, p, delta, dP and dS in fp32;
+def emulate(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R=0, bucket=None, num_buckets=0, dbias_route="direct", stats=None,
+            rounded_sums=None):
+    """What the bodies do arithmetically, in float32 torch ops (not in their summation order): scores, p, delta, dP and dS in fp32;
     P and dS rounded to the dtype before the three contractions; dbias from the rounded dS (summed in fp32 and rounded once where the
-    route reduces); the diagonal sums from the fp32 dS; one output rounding.  Returns {output: tensor}."""
+    route reduces); the diagonal sums from the fp32 dS; one output rounding.  Returns {output: tensor}.
+    The 64-wide setting: `stats` = "stat2" (the score accumulator starts at the fp32 quotient -L / scale, k:1250) or "self" (at L times the
+    fp32 reciprocal -1 / scale, k:317, k:339), and the exponent is exp2(fma-like (q k - L/scale) (scale log2e) + bias log2e) as in k:819-820;
+    `rounded_sums` = an (M, N) bool mask of the scores whose dS enters the diagonal sums rounded to the dtype (`far_rounded_mask`)."""
     B, H, M, D = q.shape
     N = k.shape[2]
     dt = q.dtype
@@ -301,7 +523,17 @@ def emulate(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R=0, b
         s = s + f(rpe1d)[:, rel][None]
     L = f(lse)
     ok = vis & (L >= DEAD_LSE)[..., None]
-    p = torch.where(ok, torch.exp(s - torch.where(L >= DEAD_LSE, L, torch.zeros(()))[..., None]), torch.zeros(()))
+    if stats is None:
+        p = torch.where(ok, torch.exp(s - torch.where(L >= DEAD_LSE, L, torch.zeros(()))[..., None]), torch.zeros(()))
+    else:
+        L0 = torch.where(L >= DEAD_LSE, L, torch.zeros(()))
+        nls = -(L0 / scale) if stats == "stat2" else L0 * (torch.tensor(-1.0) / scale)
+        c2 = scale * torch.tensor(LOG2E, dtype=torch.float32)
+        sp = f(q) @ f(k).transpose(-1, -2) + nls[..., None]                 # S' = Q K^T - L / scale
+        x2 = sp * c2
+        if rpe1d is not None:
+            x2 = x2 + (f(rpe1d) * torch.tensor(LOG2E, dtype=torch.float32))[:, rel][None]
+        p = torch.where(ok, torch.exp2(x2), torch.zeros(()))
     delta = (f(o) * f(do)).sum(-1, keepdim=True)
     ds = p * (f(do) @ f(v).transpose(-1, -2) - delta)
     pr, dsr = f(p.to(dt)), f(ds.to(dt))
@@ -316,7 +548,8 @@ def emulate(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R=0, b
         out["dbias"] = t.to(dt)
     if rpe1d is not None:
         n1 = 2 * R + 1
-        g = torch.zeros(H, n1).index_add_(1, rel.reshape(-1), ds.sum(0).reshape(H, -1))
+        dsg = ds if rounded_sums is None else torch.where(rounded_sums, dsr, ds)
+        g = torch.zeros(H, n1).index_add_(1, rel.reshape(-1), dsg.sum(0).reshape(H, -1))
         out["drpe1d"] = g
         if bucket is not None:
             bk = torch.as_tensor(bucket, dtype=torch.int64)
@@ -406,4 +639,148 @@ MUTANTS = {
     "drpe1d of the neighbouring head": _set("g_head_shift", 1, lambda c: c["rpe"] and c["H"] > 1),
     "table gradient with a bucket boundary one entry off": _set("bucket_shift", 1, lambda c: c["table"]),
     "last row of a ragged 64-row block from row M-2": _set("ragged", True, lambda c: c["M"] % 64 != 0 and c["M"] >= 2),
+}
+
+
+# Defects only the 64-wide bodies can have.  Each entry takes the case's layout -- dict(bodies, walks = layout_of(...), B, H, M, N, R) -- and
+# returns a mutant like the ones above, or None where the structure it breaks does not exist in the case.
+def _first(walks, kinds):
+    for wv in walks or ():
+        for j, kind in wv["segs"]:
+            if kind in kinds:
+                return wv, j
+    return None
+
+
+def _rows(lo, hi, value):
+    def f(c):
+        if not 0 <= lo < min(hi, c["M"]):
+            return False
+        c["wr"][lo:hi] = value
+        return True
+    return f
+
+
+def _keys(lo, hi, value):
+    def f(c):
+        if not 0 <= lo < min(hi, c["N"]):
+            return False
+        c["wq"][lo:hi] = value
+        return True
+    return f
+
+
+TRIPS = ("far+", "far-", "band", "diag")
+
+
+def _m_trip_last(L):
+    hit = _first(L["walks"]["kv"] or L["walks"]["kvh"], TRIPS)
+    if hit is None:
+        return None
+    r0 = (hit[0]["mt0"] + hit[1] + 3) * 32
+    return _rows(r0, r0 + 32, 0.0)
+
+
+def _m_remainder(L):
+    for wv in (L["walks"]["kv"] or L["walks"]["kvh"] or ()):
+        ns = wv["ns"]
+        if wv["pair"] == 0 and ns >= 4 and ns % 4 and any(k in TRIPS for _, k in wv["segs"]):
+            r0 = (wv["mt0"] + ns - ns % 4) * 32
+            return _rows(r0, (wv["mt0"] + ns) * 32, 0.0)
+    return None
+
+
+def _second_half(L, value):
+    for wv in L["walks"]["kvh"] or ():
+        if wv["pair"] == 1 and wv["ns"] > 0 and wv["mt0"] * 32 < L["M"]:
+            return _rows(wv["mt0"] * 32, L["M"], value)
+    return None
+
+
+def _m_q_step(L):
+    hit = _first(L["walks"]["q"], TRIPS)
+    if hit is None:
+        return None
+    k0 = 32 * (hit[1] + 2)
+    return _keys(k0, k0 + 32, 0.0)
+
+
+def _m_q_tail(L):
+    if L["walks"]["q"] is None or L["N"] % 32 == 0:
+        return None
+    return _keys(L["N"] // 32 * 32, L["N"], 0.0)
+
+
+def _sum_side(L):
+    """the walks of the body that forms the diagonal sums, and whether it is the dQ one"""
+    if "drpe" not in L or not L["drpe"]:
+        return None, False
+    if L["bodies"].get("qdiag", "0") == "1":
+        return L["walks"]["q"], True
+    return (L["walks"]["kv"] or L["walks"]["kvh"]), False
+
+
+def _rect(wv, j, isq, steps=1):
+    """(row lo, row hi, key lo, key hi) of `steps` steps from step j of a walk"""
+    if isq:
+        return wv["qw0"], wv["qw0"] + 64, 32 * j, 32 * (j + steps)
+    return (wv["mt0"] + j) * 32, (wv["mt0"] + j + steps) * 32, wv["kw0"], wv["kw0"] + 64
+
+
+def _m_far_drop(L):
+    walks, isq = _sum_side(L)
+    hit = _first(walks, ("far+", "far-"))
+    if hit is None:
+        return None
+    r0, r1, k0, k1 = _rect(hit[0], hit[1], isq)   # (the trip's first step: its first row / key is a boosted seam)
+
+    def gw(B, H, M, N):
+        t = torch.ones(B, H, M, N, dtype=torch.float64)
+        t[:, :, r0:r1, k0:k1] = 0.0
+        return t
+    return _set("g_w", lambda c: gw)
+
+
+def _m_far_band(L):
+    walks, isq = _sum_side(L)
+    hit = _first(walks, ("band",))
+    if hit is None:
+        return None
+    r0, r1, k0, k1 = _rect(hit[0], hit[1], isq, 4)
+    R = L["R"]
+
+    def fadd(M, N):
+        m = torch.zeros(M, N, dtype=torch.bool)
+        m[r0:r1, k0:k1] = True
+        return m, 2 * R
+    return _set("g_far_add", lambda c: fadd)
+
+
+def _m_mixed_row(L):
+    kv = L["bodies"].get("dkdv", "")
+    if not kv.startswith("64key-mixed:") or "drpe" not in L or not L["drpe"] or L["N"] <= 128:
+        return None
+    pf, B, H = int(kv.split(":")[1]), L["B"], L["H"]
+
+    def gw(B_, H_, M, N):   # the 256-key workgroup 0 of a full-length pair (units u = h B + b < 8 pf: k:1866-1870, k:1887-1889) leaves its row twice
+        t = torch.ones(B, H, M, N, dtype=torch.float64)
+        for u in range(8 * pf):
+            t[u % B, u // B, :, :256] = 2.0
+        return t
+    return _set("g_w", lambda c: gw)
+
+
+MUTANTS64 = {
+    "dK/dV without the last step of a trip": _m_trip_last,
+    "dK/dV without the remainder steps": _m_remainder,
+    "dK/dV without the second pair's half": lambda L: _second_half(L, 0.0),
+    "dK/dV with the hand-over added twice": lambda L: _second_half(L, 2.0),
+    "dQ without one 32-key step of a trip": _m_q_step,
+    "dQ without the key-tail step": _m_q_tail,
+    "delta of the row 8 further on": lambda L: _set("delta_shift", 8, lambda c: c["M"] >= 9) if L["bodies"].get("fused") == "1" else None,
+    "-L/scale formed with the scale instead of its reciprocal": lambda L: _set("lse_scale2", True) if L["walks"]["kv"] or L["walks"]["kvh"] else None,
+    "a far bin without one pipelined step's block": _m_far_drop,
+    "a far bin with the band's blocks added": _m_far_band,
+    "the mirrored diagonal index with the wrong sign": lambda L: _set("g_sign", -1) if (L["bodies"].get("qdiag") == "1" and L.get("drpe")) else None,
+    "the partial row behind a 256-key workgroup of a mixed launch counted twice": _m_mixed_row,
 }

@@ -8,7 +8,14 @@
     reference rounded once to the storage dtype lie within it on every case and every output;
   * the bound is not too loose: every mutant that applies to a case leaves it on that case, except for the (mutant, case) pairs of
     EXCUSED, each with its reason: at most 5 % of the applied pairs, and no mutant in every case of a group;
-  * the bound's shape: 0 on a dead row's dq and above the causal diagonal of dbias, finite everywhere.
+  * the bound's shape: 0 on a dead row's dq and above the causal diagonal of dbias, finite everywhere;
+  * for the non-dense 64-wide cases: the host restatement of the kernels' step classification (which steps run in pipelined trips: far-positive,
+    far-negative, band, on the causal diagonal; which run the general iteration: remainders, key tails, short sweeps) agrees with hand-worked
+    examples and finds every kind of step in the case list, per body; `emulate` runs in its 64-wide setting (statistics as accumulator initial
+    values, the far bins of the pipelined trips from the rounded dS); and twelve more mutants break what only these bodies have (a trip's last
+    step, the remainder, the second pair's half, the hand-over, a key step of the dQ trips, the key tail, the 8-row statistic groups, 1 / scale,
+    the far bins, the mirrored diagonal index, the partial rows of a mixed launch).
+The dense 64-wide bodies are not covered (tests/attn_bwd_fp64.py).
 """
 import functools
 
@@ -21,7 +28,7 @@ import oracle
 from test_attn_bwd_fp64_gpu import CASES, inputs, reference, describe, compared
 
 IDS = [c["id"] for c in CASES]
-DETECTED = {name: {} for name in G.MUTANTS}   # mutant -> {case id: caught} over the cases where it applied
+DETECTED = {name: {} for name in list(G.MUTANTS) + list(G.MUTANTS64)}   # mutant -> {case id: caught} over the cases where it applied
 EMU = {}                                      # group -> {output: [worst ratio of `emulate`, its case]}
 
 # (mutant, case id): why the bound cannot see this defect on this case.  Nothing else is excused.
@@ -37,6 +44,120 @@ EXCUSED[("drpe1d far entries without what lies beyond the band", "t5-3x2x65x300-
     "the unidirectional map puts every n >= m into bucket 0 and only the table gradient is written: that entry sums some 50 000 terms of both "
     "signs whose rows each sum to zero, and what lies beyond the band is a partial sum of the same kind, inside the fp32 summation term")
 
+# The 64-wide cases.  Their far bins are summed from the dS ROUNDED to the dtype, so the bound of a far entry carries u_T times the magnitudes of
+# all its terms -- tens of thousands, of both signs, whose true sum is of the order of their square root.
+_FAR_BIN = ("a far bin of the 64-wide bodies: the bound is u_T times the summed magnitudes of all the bin's terms (the pipelined trips sum the rounded dS), and "
+            "what the defect adds or leaves out is a partial sum of the same terms of both signs, below that; the same defect is caught on the smaller bins of the group's other cases")
+_FAR_CASES = {
+    "a far bin with the band's blocks added": (
+        "kv64h-1x2x256x256-float16-rpe64-s0.3",
+        "kv64-2x2x129x64-float16-rpe8-s1.0-strided",
+        "kv64-1x2x255x256-bfloat16-rpe8-s0.125-pert",
+        "kv64-2x2x257x257-float16-rpe1-s1.0",
+        "kv64-2x2x127x520-float16-rpe128-s0.125-strided",
+        "kv64-1x2x255x257-float16-rpe8-s0.125",
+        "kv64-2x2x384x384-float16-t5b8-s0.3-runs",
+        "kv64-1x2x385x520-bfloat16-t5u128-s1.0-scan",
+        "kv64h-1x2x415x300-bfloat16-rpe8-s0.3-strided",
+        "kv64m-4x4x140x384-float16-t5b128-s0.3-scan",
+        "kv64m-3x8x130x520-float16-t5u8-s1.0-scan",
+        "kv64m-2x8x160x300-bfloat16-rpe8-s0.3",
+        "sep64-1x2x257x300-bfloat16-rpe8-s0.3",
+        "fused64-2x2x129x385-float16-rpe8-s1.0-plain",
+        "fused64-1x4x512x512-bfloat16-t5b128-s1.0-runs-plain",
+        "fused64-1x2x300x520-float16-rpe128-s0.3-stages",
+        "qdiag-1x2x384x384-bfloat16-rpe8-s0.125-qd1",
+        "qdiag-1x2x384x384-bfloat16-rpe8-s0.125-qd0",
+        "qdiag-3x2x257x300-float16-t5b8-s1.0-runs-qd1",
+        "qdiag-3x2x257x300-float16-t5b8-s1.0-runs-qd0",
+        "qdiag-1x2x300x385-bfloat16-t5u128-s0.3-scan-qd1",
+        "qdiag-1x2x300x385-bfloat16-t5u128-s0.3-scan-qd0",
+        "qdiag-3x2x129x257-float16-t5b128-s0.125-stages-scan-qd1",
+        "qdiag-3x2x129x257-float16-t5b128-s0.125-stages-scan-qd0",
+        "qdiag-1x2x385x257-bfloat16-t5u8-s1.0-runs-qd1",
+        "qdiag-1x2x385x257-bfloat16-t5u8-s1.0-runs-qd0",
+        "causal64-fused64-1x2x284x384-bfloat16-rpe8-s0.125-causal",
+    ),
+    "a far bin without one pipelined step's block": (
+        "kv64-1x2x256x65-bfloat16-rpe1-s0.3",
+        "kv64-1x2x255x256-bfloat16-rpe8-s0.125-pert",
+        "kv64-2x2x257x257-float16-rpe1-s1.0",
+        "kv64-2x2x127x520-float16-rpe128-s0.125-strided",
+        "kv64-1x2x385x128-float16-rpe8-s0.3",
+        "kv64-1x2x384x384-bfloat16-rpe8-s0.125",
+        "kv64-2x2x384x384-float16-t5b8-s0.3-runs",
+        "kv64-1x2x385x520-bfloat16-t5u128-s1.0-scan",
+        "kv64h-1x2x415x300-bfloat16-rpe8-s0.3-strided",
+        "kv64h-1x2x544x130-bfloat16-t5b8-s1.0-runs",
+        "kv64h-1x2x385x384-bfloat16-rpe128-s0.125-causal",
+        "kv64m-4x4x140x384-float16-t5b128-s0.3-scan",
+        "kv64m-3x8x130x520-float16-t5u8-s1.0-scan",
+        "kv64m-2x8x160x300-bfloat16-rpe8-s0.3",
+        "sep64-1x2x257x300-bfloat16-rpe8-s0.3",
+        "sep64-1x2x300x385-float16-t5b8-s1.0-scan",
+        "fused64-2x2x129x385-float16-rpe8-s1.0-plain",
+        "fused64-1x2x384x384-float16-rpe1-s0.3-pert-plain",
+        "fused64-1x4x512x512-bfloat16-t5b128-s1.0-runs-plain",
+        "fused64-1x2x300x520-float16-rpe128-s0.3-stages",
+        "qdiag-1x2x384x384-bfloat16-rpe8-s0.125-qd1",
+        "qdiag-1x2x384x384-bfloat16-rpe8-s0.125-qd0",
+        "qdiag-3x2x257x300-float16-t5b8-s1.0-runs-qd1",
+        "qdiag-3x2x257x300-float16-t5b8-s1.0-runs-qd0",
+        "qdiag-1x2x300x385-bfloat16-t5u128-s0.3-scan-qd1",
+        "qdiag-1x2x300x385-bfloat16-t5u128-s0.3-scan-qd0",
+        "qdiag-1x2x385x257-bfloat16-t5u8-s1.0-runs-qd1",
+        "qdiag-1x2x385x257-bfloat16-t5u8-s1.0-runs-qd0",
+        "causal64-kv64-1x2x357x257-bfloat16-rpe128-s0.125-causal",
+        "causal64-kv64-1x2x284x384-bfloat16-rpe8-s1.0-causal",
+        "causal64-kv64-1x2x512x512-float16-rpe128-s0.3-causal",
+        "causal64-fused64-1x2x257x257-bfloat16-rpe8-s1.0-causal",
+        "causal64-fused64-1x2x258x257-float16-rpe8-s1.0-causal-pert",
+        "causal64-fused64-1x2x284x384-bfloat16-rpe8-s0.125-causal",
+        "causal64-fused64-1x2x512x512-float16-rpe128-s1.0-causal",
+    ),
+    "drpe1d far entries without what lies beyond the band": (
+        "kv64-2x2x127x520-float16-rpe128-s0.125-strided",
+        "kv64-2x2x384x384-float16-t5b8-s0.3-runs",
+        "kv64-1x2x385x520-bfloat16-t5u128-s1.0-scan",
+        "kv64h-1x2x544x130-bfloat16-t5b8-s1.0-runs",
+        "kv64h-1x2x385x384-bfloat16-rpe128-s0.125-causal",
+        "q64-2x2x300x384-bfloat16-t5b8-s0.3-runs",
+        "fused64-1x4x512x512-bfloat16-t5b128-s1.0-runs-plain",
+        "qdiag-1x2x384x384-bfloat16-rpe8-s0.125-qd1",
+        "qdiag-1x2x384x384-bfloat16-rpe8-s0.125-qd0",
+        "qdiag-1x2x385x257-bfloat16-t5u8-s1.0-runs-qd1",
+        "causal64-kv64-1x2x512x512-float16-rpe128-s0.3-causal",
+    ),
+}
+EXCUSED.update({(m, cid): _FAR_BIN for m, ids in _FAR_CASES.items() for cid in ids})
+_ALL_FAR = "N - M = -100 at R = 8: every visible score lies beyond -R, the clamped index does not move and the result is the reference's own (ratio 0)"
+EXCUSED[("drpe1d diagonal index +1", "causal64-q64-1x2x357x257-float16-rpe8-s1.0-causal-pert")] = _ALL_FAR
+EXCUSED[("drpe1d diagonal index -1", "causal64-q64-1x2x357x257-float16-rpe8-s1.0-causal-pert")] = _ALL_FAR
+_LAST_KEY = "key N - 1 is visible to the last row alone, with p = 8.5e-4 there: the dropped term is 0.92 of that row's bound"
+EXCUSED[("dQ without key N-1", "causal64-kv64-1x2x257x357-bfloat16-none-s1.0-causal")] = _LAST_KEY
+EXCUSED[("dQ without the last key of a ragged last tile", "causal64-kv64-1x2x257x357-bfloat16-none-s1.0-causal")] = _LAST_KEY
+
+
+def _rpe(case):
+    return case["bias"] != "none" and case["bias"][:2] not in ("11", "1h", "b1", "bh")
+
+
+def _layout(case):
+    """what the mutants of the 64-wide bodies need of a case: its bodies and their step walks"""
+    return dict(bodies=case["bodies"], walks=G.layout_of(case["bodies"], case["M"], case["N"], case["R"], case["causal"], _rpe(case)), B=case["B"], H=case["H"],
+                M=case["M"], N=case["N"], R=case["R"], drpe=_rpe(case))
+
+
+def _mutants(case):
+    muts = dict(G.MUTANTS)
+    if case["wide"]:
+        lay = _layout(case)
+        for name, make in G.MUTANTS64.items():
+            m = make(lay)
+            if m is not None:
+                muts[name] = m
+    return muts
+
 
 @functools.lru_cache(maxsize=2)
 def _truth(i):
@@ -49,11 +170,14 @@ def _truth(i):
 def test_the_case_list_is_what_the_issue_asks_for():
     def of(group, key):
         return {c[key] for c in CASES if c["group"] == group}
-    assert {c["bodies"]["dq"] for c in CASES} == {"32row"} and {c["bodies"]["dkdv"] for c in CASES} == {"32key"}   # (the 64-wide bodies: not covered)
+    OLD = ("w2", "w4", "causal", "t5", "dbias", "pert", "fused32")
+    assert {c["bodies"]["dq"] for c in CASES if c["group"] in OLD} == {"32row"} and {c["bodies"]["dkdv"] for c in CASES if c["group"] in OLD} == {"32key"}
+    assert sum(c["group"] in OLD for c in CASES) == 63 and all(c["wide"] == (c["group"] not in OLD) for c in CASES)
+    _the_64_wide_groups(of)
     assert {1, 31, 32, 33, 64, 65, 129} <= of("w2", "M") and {1, 63, 64, 65, 127, 128, 129, 200} <= of("w2", "N")
     assert of("w2", "D") == {16, 32, 64, 128} and {1, 8, 128} <= of("w2", "R")
     assert {"none", "rpe", "11", "1h", "b1", "bh"} <= of("w2", "bias") | of("causal", "bias")
-    for c in CASES:
+    for c in (c for c in CASES if c["group"] in OLD):
         if c["group"] in ("w4", "fused32"):   # four waves in at least one stage (both in the one-launch form)
             nq, nk = (c["B"] * c["H"] * -(-c[x] // 128) >= 160 for x in ("M", "N"))
             assert (nq and nk) if c["group"] == "fused32" else (nq or nk), c["id"]
@@ -72,6 +196,93 @@ def test_the_case_list_is_what_the_issue_asks_for():
     assert any(c["bias"].endswith("-min") for c in CASES)
     assert any(c["dtype"] == torch.bfloat16 and c["D"] == 64 and c["N"] % 8 and c["bias"] == "1h" and "V_QDB64_ON" in c["bits"] for c in CASES)   # the fallback
     assert max(c["B"] * c["H"] * c["M"] * c["N"] for c in CASES) <= 700 * 700 * 12
+
+
+def _the_64_wide_groups(of):
+    """the non-dense 64-wide groups: shapes, forms and -- by the host restatement of the kernels' step classification -- every kind of step"""
+    W = [c for c in CASES if c["wide"]]
+    assert all(c["D"] == 64 and c["B"] * c["H"] * c["M"] * c["N"] <= 2 ** 22 and c["bias"] in ("none", "rpe", "t5b", "t5u") for c in W)
+    assert {90, 127, 128, 129, 255, 256, 257, 300, 385} <= of("kv64", "M") and {63, 64, 65, 128, 192, 255, 256, 257, 300, 520} <= of("kv64", "N")
+    assert {0, 1, 8, 128} <= of("kv64", "R") and any(c["M"] == c["N"] == 384 and c["R"] == 8 for c in W if c["group"] == "kv64")
+    assert {63, 64, 65, 128, 255, 256, 257} <= of("q64", "M") and {90, 127, 128, 129, 256, 300, 385} <= of("q64", "N")
+    for g, dq, kv in (("kv64", "32row", "64key"), ("kv64h", "32row", "64key-half"), ("q64", "64row", "32key"), ("fused64", "64row", "64key"), ("qdiag", "64row", "64key")):
+        assert {(c["bodies"]["dq"], c["bodies"]["dkdv"]) for c in W if c["group"] == g} == {(dq, kv)}, g
+    for c in W:
+        if c["group"] == "kv64m":
+            assert c["bodies"]["dkdv"].startswith("64key-mixed:") and (c["B"] * c["H"]) % 8 == 0 and c["B"] * c["H"] >= 16
+        assert (c["bodies"]["fused"] == "1") == (c["group"] in ("fused64", "qdiag") or "-fused64-" in c["id"]), c["id"]
+    assert {c["N"] for c in W if c["group"] == "kv64m"} >= {300, 384, 520}
+    assert {c["bodies"].get("dtable") for c in W if c["group"] == "kv64m"} >= {"runs", "scan"}
+    assert any(((c["M"] + 31) // 32) % 2 == 1 for c in W if c["group"] == "kv64h") and any((c["M"] + 31) // 32 < 8 for c in W if c["group"] == "kv64h")
+    plain = [c for c in W if c["group"] == "fused64" and not c["bits"]]
+    assert len(plain) >= 4 and all(c["bodies"]["fused"] == "1" for c in plain)
+    assert any(c["bodies"]["qdiag"] == "1" and c["bodies"].get("dtable") == "runs" and c["bias"] == "t5b" and c["M"] == c["N"] == 512 and c["R"] == 128 for c in plain)
+    qd = [c for c in W if c["group"] == "qdiag"]
+    assert {c["B"] for c in qd} >= {1, 3} and {c["bias"] for c in qd} >= {"rpe", "t5b", "t5u"} and {c["bodies"].get("dtable") for c in qd} >= {None, "runs", "scan"}
+    for c in qd:   # ON and OFF on the same inputs
+        twin = [x for x in qd if x is not c and all(x[key] == c[key] for key in ("B", "H", "M", "N", "bias", "R", "dtype", "scale"))]
+        assert len(twin) == 1 and {twin[0]["bodies"]["qdiag"], c["bodies"]["qdiag"]} == {"0", "1"}
+    for form in ("-kv64-", "-q64-", "-fused64-"):
+        cs = [c for c in W if c["group"] == "causal64" and form in c["id"]]
+        assert all(c["causal"] for c in cs) and {c["N"] - c["M"] for c in cs} >= {0, 1, 100, -1, -100}
+        assert any(c["bias"] == "none" for c in cs) and any(c["bias"] == "rpe" and -c["R"] <= c["N"] - c["M"] < c["R"] for c in cs)
+        assert any(c["bias"] == "rpe" and c["R"] == 8 and c["N"] - c["M"] == 100 for c in cs)
+    assert sum(c["scale"] == 0.3 for c in W) >= 6 and sum(c["scale"] == 1.0 for c in W) >= 6 and {c["scale"] for c in W} == {0.125, 1.0, 0.3}
+    for g in ("kv64", "kv64h", "kv64m", "q64", "sep64", "fused64", "qdiag", "causal64"):
+        assert of(g, "dtype") == {torch.bfloat16, torch.float16}, g
+        assert {c["scale"] for c in W if c["group"] == g} >= {0.3}, g
+    assert sum(c["pert"] for c in W) >= 4 and sum(c["split"] for c in W) >= 4 and sum(c["strided"] for c in W) >= 6
+    assert any(c["pert"] and c["bodies"]["fused"] == "1" for c in W)   # (the SELF form follows the stored o, lse)
+    # every kind of step, per body: over all the cases that run it, and -- but for the causal diagonal, which only a causal case has -- inside its own group
+    kinds = {}
+    for c in W:
+        lay = G.layout_of(c["bodies"], c["M"], c["N"], c["R"], c["causal"], c["bias"] != "none")
+        for body in ("kv", "kvh", "q"):
+            if lay[body] is not None:
+                for key in (body, (body, c["group"])):
+                    kinds.setdefault(key, set()).update(G.kinds_of(lay[body]))
+    for body in ("kv", "kvh", "q"):
+        assert kinds[body] == set(G.KINDS), (body, set(G.KINDS) - kinds[body])
+    for key in (("kv", "kv64"), ("kvh", "kv64h"), ("q", "q64"), ("kv", "fused64"), ("q", "fused64")):
+        assert kinds[key] >= set(G.KINDS) - ({"causal-diagonal trip"} if key != ("kvh", "kv64h") else set()), (key, set(G.KINDS) - kinds[key])
+    for body in ("kv", "q"):
+        assert "causal-diagonal trip" in kinds[(body, "causal64")] and "general step" in kinds[(body, "causal64")]
+    # the boosted seams: every wave's first key, every trip's first row, the first step behind the last aligned trip, the second pair's first step
+    from test_attn_bwd_fp64_gpu import seams64
+    for c in W:
+        rows, keys = seams64(c)
+        nst = (c["M"] + 31) // 32
+        assert set(range(0, c["N"], 64)) <= set(keys) and set(range(0, c["M"], 128)) <= set(rows)
+        assert all(r in rows for r in ((nst - nst % 4) * 32, (nst + 1) // 2 * 32) if r < c["M"])
+
+
+def test_the_bound_still_raises_for_the_dense_64_wide_bodies():
+    i = next(i for i, c in enumerate(CASES) if c["group"] == "dbias" and c["D"] == 64)
+    case, (t, ref, _) = CASES[i], _truth(i)
+    for bodies in (dict(dq="64row-batch4", dkdv="64key", fused="1", qdiag="0", dbias="dq-kernel"), dict(dq="64row-batch4", dkdv="32key", fused="0", qdiag="0", dbias="dq-kernel+partials"),
+                   dict(dq="32row", dkdv="64key", fused="0", qdiag="0", dbias="staged"), dict(dq="32row", dkdv="32key", fused="0", qdiag="0", dbias="dq-kernel")):
+        with pytest.raises(NotImplementedError):
+            G.attn_bwd_bound(ref, case["dtype"], 64, bodies, case["N"], case["M"])
+
+
+def test_the_step_classification_on_hand_worked_examples():
+    """M = N = 384, R = 8, the dK/dV body (one 256-key workgroup + one of 128 live keys): the wave at keys 192.. sees rows 0..127 far to its left (far-positive) and the rest across
+    the band (key 255 is only 1 above row 256), the wave at keys 0.. rows 128.. far-negative: one workgroup holds all three kinds of trip"""
+    w = {x["kw0"]: [k for _, k in x["segs"]] for x in G.steps_kv64(384, 384, 8, False, True)}
+    assert w[192] == ["far+", "band", "band"] and w[64] == ["band", "band", "far-"] and w[0] == ["band", "far-", "far-"] and w[320] == ["far+", "far+", "band"]
+    # 90 rows: three steps, fewer than the ring has slots -- all general; 65 keys: the second wave has a key tail and stays general
+    assert all(k == "general" for x in G.steps_kv64(90, 128, 0, False, False) for _, k in x["segs"])
+    w = {x["kw0"]: [k for _, k in x["segs"]] for x in G.steps_kv64(128, 65, 0, False, False)}
+    assert w[0] == ["far-"] and w[64] == ["general"] * 4
+    # no bias, causal, M = N = 256: the wave at keys 64.. has its diagonal in the first trip (mask in the C operand), then sees everything
+    w = {x["kw0"]: [k for _, k in x["segs"]] for x in G.steps_kv64(256, 256, 0, True, False)}
+    assert w[64] == ["diag", "far-"] and w[0] == ["diag", "far-"]
+    # the dQ body, M = 64, N = 300, no bias: two trips, one whole general step, one with a key tail
+    (x,) = G.steps_q64(64, 300, 0, False, False)
+    assert [k for _, k in x["segs"]] == ["far-", "far-", "general", "general"] and x["tail"]
+    # half-length form, 9 steps: the pairs walk 5 and 4 (+ 1 empty) steps
+    hs = [(x["pair"], x["mt0"], x["ns"]) for x in G.steps_kv64(288, 128, 0, False, False, half=True) if x["kw0"] == 0]
+    assert hs == [(0, 0, 5), (1, 5, 5)]
 
 
 @pytest.mark.parametrize("i", range(len(CASES)), ids=IDS)
@@ -175,8 +386,13 @@ def test_the_term_magnitudes_dominate_and_the_bound_has_its_shape(i):
 def test_correct_arithmetic_satisfies_the_bound(i):
     case = CASES[i]
     t, ref, bound = _truth(i)
+    kw = {}
+    if case["wide"]:   # the 64-wide setting: the statistics as accumulator initial values, the far bins of the pipelined trips from the rounded dS
+        kw["stats"] = "self" if case["bodies"]["fused"] == "1" else "stat2"
+        if t["rpe"] is not None:
+            kw["rounded_sums"] = G.far_rounded_mask(case["bodies"], case["M"], case["N"], case["R"], case["causal"])
     emu = G.emulate(t["q"], t["k"], t["v"], t["o"], t["lse"], t["do"], case["scale"], case["causal"], t["bias"], t["rpe"], case["R"], t["bucket"],
-                    32 if t["bucket"] is not None else 0, case["bodies"].get("dbias", "direct"))
+                    32 if t["bucket"] is not None else 0, case["bodies"].get("dbias", "direct"), **kw)
     r = G.ratios(emu, ref, bound)
     w = EMU.setdefault(case["group"], {})
     for x, v in r.items():
@@ -196,7 +412,7 @@ def test_every_applicable_mutant_violates_the_bound(i):
     outs = compared(case, ref)
     bnd = {x: bound[x] for x in outs}
     missed = []
-    for name, mutant in G.MUTANTS.items():
+    for name, mutant in _mutants(case).items():
         mut = reference(case, t, mutant)
         if not mut["applied"]:
             continue

@@ -10,11 +10,22 @@ unidirectional maps.  Shapes are the smallest at which the structure exists: row
 1 / 8 / 128, bottom-right causal masks with N - M in {0, 1, 100, -1, -100} (dead rows included), dense biases of every broadcast kind and
 one holding finfo.min.  "Perturbed" cases shift lse by 0.25 on every third row and replace o by an unrelated tensor: the contract is
 "from the stored o, lse", and a kernel that recomputed either would leave the bound.  Some cases call the stages one by one.
-Not covered: every 64-wide body (see tests/attn_bwd_fp64.py); they stay with the max-norm tests.
+Covered (csrc/attn_bwd64.h, D = 64, bias none / rpe1d / T5 table): the non-dense 64-wide bodies.  Groups kv64 (dkdv=64key beside the 32-row dQ kernel,
+whose statistics it starts from), kv64h (64key-half: two wave pairs, each half of the steps, and the hand-over), kv64m (64key-mixed: both in one
+launch), q64 (dq=64row beside the 32-key body), sep64 (both 64-wide bodies as two launches), fused64 (one launch, the dK/dV half on statistics of
+its own; five cases carry NO variant bit -- the path a plain call takes --, one of them the benchmark's configuration at B = 1, H = 4 with qdiag=1
+dtable=runs), qdiag (V_QDIAG_ON and V_QDIAG_OFF on the same inputs) and causal64 (each form at N - M in {0, 1, 100, -1, -100}, without bias, with
+the table inside the band, with a table far from the diagonal).  sm_scale is 0.125, 1.0 or 0.3 (no exact reciprocal); q is scaled so that the
+scores spread alike.  Shapes sit around the trip (128 rows), ring (4 steps), wave (64 keys) and workgroup (128 / 256 keys, 256 rows) boundaries;
+tests/test_attn_bwd_fp64_cpu.py asserts with the host restatement of the kernels' step classification that every kind of step occurs.
+Not covered: the DENSE 64-wide bodies (64row-batch4, the DENSE form of the 64-key body, the dense one-launch form, dbias dq-kernel /
+dq-kernel+partials; see tests/attn_bwd_fp64.py); they stay with the max-norm tests.
 
 The value rows at key 0, N - 1 and the block seam and the `do` rows 0, M - 1 and the first rows of the last 32- / 64-row blocks carry 32
-times the others' magnitude, so that one dropped key or row there moves the gradients beyond the bound (tests/test_attn_bwd_fp64_cpu.py
-proves that on these very inputs, without a GPU).  Every case asserts its bodies through fat5_attn_describe before it launches.
+times the others' magnitude -- in the 64-wide cases also the keys at every wave start (64 w: the 128- and 256-key block starts among them) and the
+rows at every trip start (multiples of 128), at the first step behind the last aligned trip and at the first step of the second pair's half --,
+so that one dropped key or row there moves the gradients beyond the bound (tests/test_attn_bwd_fp64_cpu.py proves that on these very inputs,
+without a GPU).  Every case asserts its bodies through fat5_attn_describe before it launches.
 
 CASES, `inputs`, `reference` and `describe` are module-level and CPU-only.
 """
@@ -118,6 +129,98 @@ def _build_cases():
     add("fused32", ONE32, 2, 80, 31, 63, 64, F16, bias="bh", causal=True, fused=1)
     add("fused32", ONE32, 2, 80, 65, 33, 64, BF16, causal=True, pert=True, fused=1)
     add("fused32", ONE32, 2, 80, 32, 127, 32, BF16, bias="rpe", R=1, pert=True, fused=1)
+    # ================================================================================================================================
+    # The non-dense 64-wide bodies of csrc/attn_bwd64.h (D = 64): smallest shapes at which their trips, rings, wave and workgroup seams exist
+    # ================================================================================================================================
+    SCALES = (0.125, 1.0, 0.3)   # (0.125 = 64 ** -0.5 has an exact reciprocal; 0.3 has none in fp32 or in 16 bits)
+    KV, KVH, KVM = ("V_KV64_ON", "V_KV64_HALF_OFF", "V_KV64_MIX_OFF"), ("V_KV64_ON", "V_KV64_HALF_ON"), ("V_KV64_ON", "V_KV64_MIX_ON")
+    Q32, Q64, SEP = ("V_Q64_OFF", "V_FUSED64_OFF"), ("V_Q64_ON", "V_FUSED64_OFF"), ("V_FUSED64_OFF",)
+    n64 = [0]
+
+    def add64(group, bits, dq, dkdv, B, H, M, N, dtype, fused=0, qdiag=0, causal=False, bias="none", R=0, scale=None, dtable=None, strided=False, pert=False,
+              split=False, tag=""):
+        i = n64[0]
+        n64[0] += 1
+        scale = SCALES[i % 3] if scale is None else scale
+        if dtable == "scan":
+            bits = bits + ("V_DTABLE_RUNS_OFF",)
+        cid = (f"{group}{tag}-{B}x{H}x{M}x{N}-{_name(dtype)}-{bias}{R if R else ''}-s{scale}{'-causal' if causal else ''}{'-strided' if strided else ''}"
+               f"{'-pert' if pert else ''}{'-stages' if split else ''}{'-' + dtable if dtable else ''}{'-qd%d' % qdiag if 'V_QDIAG_ON' in bits or 'V_QDIAG_OFF' in bits else ''}"
+               f"{'-plain' if not bits else ''}")
+        if group == "fused64":
+            fused = 1
+        bodies = dict(dq=dq, dkdv=dkdv, fused=str(fused), qdiag=str(qdiag))
+        if dtable:
+            bodies["dtable"] = dtable
+        out.append(dict(id=cid, group=group, bodies=bodies, bits=bits, B=B, H=H, M=M, N=N, D=64, dtype=dtype, causal=causal, bias=bias, R=R, scale=scale,
+                        strided=strided, pert=pert, split=split, wide=True))
+
+    dt = lambda i: (BF16, F16)[i % 2]
+    # ---- kv64: the 64-key dK/dV body on the statistics of the 32-row dQ kernel ----
+    Ms, Ns = (90, 127, 128, 129, 255, 256, 257, 300, 385), (63, 64, 65, 128, 192, 255, 256, 257, 300, 520)
+    kinds = (("none", 0), ("rpe", 8), ("rpe", 1), ("none", 0), ("rpe", 128))
+    for i, N in enumerate(Ns):
+        bias, R = kinds[i % 5]
+        add64("kv64", KV + Q32, "32row", "64key", 1 + i % 2, 2, Ms[(2 * i + 1) % 9], N, dt(i), bias=bias, R=R, strided=i % 4 == 1, split=i % 5 == 3, pert=i == 6)
+    for i, (M, N) in enumerate(((90, 300), (128, 64), (255, 257), (300, 192), (385, 128))):   # (the M values the pairing above left out)
+        add64("kv64", KV + Q32, "32row", "64key", 1, 2, M, N, dt(i + 1), bias=("rpe", "none")[i % 2], R=8 if i % 2 == 0 else 0)
+    add64("kv64", KV + Q32, "32row", "64key", 1, 2, 384, 384, BF16, bias="rpe", R=8)          # far-positive, band and far-negative trips in one workgroup
+    add64("kv64", KV + Q32, "32row", "64key", 2, 2, 384, 384, F16, bias="t5b", R=8, dtable="runs", scale=0.3)
+    add64("kv64", KV + Q32, "32row", "64key", 1, 2, 385, 520, BF16, bias="t5u", R=128, dtable="scan", scale=1.0)
+    # ---- kv64h: 128-key workgroups, two pairs: an odd number of steps (unequal halves), fewer steps than two rings ----
+    for i, (M, N, bias, R, causal) in enumerate(((288, 257, "none", 0, False), (160, 128, "rpe", 8, False), (415, 300, "rpe", 8, False), (96, 192, "none", 0, False),
+                                                 (544, 130, "t5b", 8, False), (300, 300, "none", 0, True), (385, 384, "rpe", 128, True))):
+        add64("kv64h", KVH + Q32, "32row", "64key-half", 1 + i % 2, 2, M, N, dt(i), bias=bias, R=R, causal=causal, dtable="runs" if bias == "t5b" else None,
+              strided=i == 2, pert=i == 3, split=i == 1)
+    # ---- kv64m: 256-key and half-length workgroups in one launch: B H a multiple of 8, at least 16 ----
+    for i, (B, H, M, N, bias, R, dtable) in enumerate(((2, 8, 129, 300, "t5b", 8, "runs"), (4, 4, 140, 384, "t5b", 128, "scan"), (2, 8, 257, 520, "none", 0, None),
+                                                       (3, 8, 130, 520, "t5u", 8, "scan"), (2, 8, 160, 300, "rpe", 8, None))):
+        add64("kv64m", KVM + Q32, "32row", "64key-mixed:1", B, H, M, N, dt(i), bias=bias, R=R, dtable=dtable, strided=i == 2, split=i == 0)
+    # ---- q64: the 64-row dQ body beside the 32-key dK/dV body (the mirror of kv64) ----
+    Ms, Ns = (63, 64, 65, 128, 255, 256, 257), (90, 127, 128, 129, 256, 300, 385)
+    for i, M in enumerate(Ms):
+        bias, R = kinds[(i + 1) % 5]
+        add64("q64", ("V_KV64_OFF",) + Q64, "64row", "32key", 1 + i % 2, 2, M, Ns[(3 * i + 2) % 7], dt(i), bias=bias, R=R, strided=i % 4 == 2, split=i == 4, pert=i == 5)
+    add64("q64", ("V_KV64_OFF",) + Q64, "64row", "32key", 1, 2, 384, 385, F16, bias="rpe", R=8)
+    add64("q64", ("V_KV64_OFF",) + Q64, "64row", "32key", 2, 2, 300, 384, BF16, bias="t5b", R=8, dtable="runs")
+    # ---- sep64: both 64-wide bodies as separate launches (the statistics as the dQ kernel's quotient -L / scale) ----
+    add64("sep64", KV + ("V_Q64_ON",) + SEP, "64row", "64key", 1, 2, 257, 300, BF16, bias="rpe", R=8, scale=0.3)
+    add64("sep64", KV + ("V_Q64_ON",) + SEP, "64row", "64key", 2, 2, 385, 257, F16, scale=0.3, split=True)
+    add64("sep64", KVH + ("V_Q64_ON",) + SEP, "64row", "64key-half", 1, 2, 300, 385, F16, bias="t5b", R=8, dtable="scan", scale=1.0)
+    # ---- fused64: one launch, the dK/dV half on statistics of its own (SELF) ----
+    ONE = ("V_FUSED64_ON",)
+    add64("fused64", (), "64row", "64key", 1, 2, 257, 300, BF16)                                                      # no variant bit: the path a plain call takes
+    add64("fused64", (), "64row", "64key", 2, 2, 129, 385, F16, bias="rpe", R=8, qdiag=1)
+    add64("fused64", (), "64row", "64key", 1, 2, 384, 384, F16, bias="rpe", R=1, qdiag=1, pert=True)
+    add64("fused64", (), "64row", "64key", 1, 4, 512, 512, BF16, bias="t5b", R=128, qdiag=1, dtable="runs", scale=1.0)  # the benchmark's configuration at B = 1, H = 4
+    add64("fused64", (), "64row", "64key", 2, 2, 90, 63, BF16, scale=0.3, strided=True)
+    add64("fused64", ONE, "64row", "64key", 1, 2, 300, 520, F16, bias="rpe", R=128, qdiag=1, split=True)
+    add64("fused64", ONE, "64row", "64key", 2, 2, 255, 256, BF16, pert=True)
+    add64("fused64", ONE, "64row", "64key", 1, 2, 128, 129, F16, bias="t5u", R=8, qdiag=1, dtable="scan", strided=True)
+    # ---- qdiag: the diagonal sums in the dQ workgroups always / never, on the same inputs ----
+    for i, (B, M, N, bias, R, dtable) in enumerate(((1, 384, 384, "rpe", 8, None), (3, 257, 300, "t5b", 8, "runs"), (1, 300, 385, "t5u", 128, "scan"),
+                                                    (3, 129, 257, "t5b", 128, "scan"), (1, 385, 257, "t5u", 8, "runs"), (1, 257, 300, "rpe", 128, None))):
+        for qd in (1, 0):
+            add64("qdiag", ONE + (("V_QDIAG_ON",) if qd else ("V_QDIAG_OFF",)), "64row", "64key", B, 2, M, N, dt(i), fused=1, qdiag=qd, bias=bias, R=R, dtable=dtable,
+                  scale=SCALES[i % 3], split=i == 3)
+    # ---- causal64: bottom-right masks; no bias (the mask in the C operand), the table inside the band, a table at R = 8 far from the diagonal ----
+    forms = (("kv64", KV + Q32, "32row", "64key", 0), ("q64", ("V_KV64_OFF",) + Q64, "64row", "32key", 0), ("fused64", ONE, "64row", "64key", 1))
+    for f, (name, bits, dq, dkdv, fused) in enumerate(forms):
+        for i, d in enumerate((0, 1, 100, -1, -100)):
+            M, N = (257, 257 + d) if d >= 0 else (257 - d, 257)
+            bias, R = (("none", 0), ("rpe", 128), ("rpe", 8))[(i + f) % 3] if d != 100 else ("none", 0)
+            add64("causal64", bits, dq, dkdv, 1, 2, M, N, dt(i + f), fused=fused, causal=True, bias=bias, R=R, qdiag=1 if (fused and bias == "rpe") else 0,
+                  strided=(i + f) == 3, pert=(i + f) == 5, tag="-" + name)
+        add64("causal64", bits, dq, dkdv, 1, 2, 284, 384, dt(f), fused=fused, causal=True, bias="rpe", R=8, qdiag=1 if fused else 0, tag="-" + name)   # N - M = 100, R = 8: general diagonal steps
+        add64("causal64", bits, dq, dkdv, 1, 2, 512, 512, dt(f + 1), fused=fused, causal=True, bias="rpe", R=128, qdiag=1 if fused else 0, tag="-" + name)   # band trips on the diagonal
+    # ---- far bins small enough that one pipelined step's block more or less leaves their bound (u_T times the bin's summed magnitudes) ----
+    add64("fused64", ONE, "64row", "64key", 1, 2, 64, 256, F16, bias="rpe", R=8, qdiag=1, scale=0.3)
+    add64("fused64", ONE, "64row", "64key", 1, 2, 64, 256, BF16, bias="rpe", R=64, qdiag=1, scale=0.3)
+    add64("kv64h", KVH + Q32, "32row", "64key-half", 1, 2, 256, 256, F16, bias="rpe", R=64, scale=0.3)
+    add64("sep64", KV + ("V_Q64_ON",) + SEP, "64row", "64key", 1, 2, 128, 256, F16, bias="rpe", R=64, scale=0.3)
+    add64("causal64", ONE, "64row", "64key", 1, 2, 256, 256, F16, fused=1, causal=True, bias="rpe", R=64, qdiag=1, scale=0.3, tag="-fused64")
+    for c in out:
+        c.setdefault("wide", False)   # (wide: a case of the 64-wide groups)
     assert len({c["id"] for c in out}) == len(out)
     return out
 
@@ -132,6 +235,15 @@ def _gen(*key):
 def boosted_rows(M):
     """the `do` rows that carry BOOST times the others' magnitude: 0, M - 1, the first rows of the last 32- and 64-row blocks and the seam row"""
     return sorted({0, M - 1, (M - 1) // 32 * 32, (M - 1) // 64 * 64, G.seam_row(M)} - {None})
+
+
+def seams64(case):
+    """(rows, keys) of the 64-wide bodies' seams: keys at every wave start (64 w, which covers the 128- and 256-key workgroup starts); rows at
+    every trip start (multiples of 128), at the first step behind the last aligned trip and at the first step of the second pair's half"""
+    M, N = case["M"], case["N"]
+    nst = (M + 31) // 32
+    rows = set(range(0, M, 128)) | {(nst - nst % 4) * 32, (nst + 1) // 2 * 32}
+    return sorted(r for r in rows if r < M), list(range(0, N, 64))
 
 
 def bucket_map(case):
@@ -153,9 +265,12 @@ def inputs(case):
         return torch.randn(B, H, S, D, generator=g).to(dtype)
 
     q, k, v, do = rnd(M), rnd(N), rnd(N), rnd(M)
-    for j in {0, N - 1, F.seam_key(N)} - {None}:
+    rows64, keys64 = seams64(case) if case["wide"] else ([], [])
+    if case["wide"] and case["scale"] != 0.125:   # (the same spread of scores at every sm_scale: the softmax stays as flat as in the other cases)
+        q.copy_((q.float() * (0.125 / case["scale"])).to(dtype))
+    for j in ({0, N - 1, F.seam_key(N)} | set(keys64)) - {None}:
         v[:, :, j] = (v[:, :, j].float() * BOOST).to(dtype)
-    for m in boosted_rows(M):
+    for m in sorted(set(boosted_rows(M)) | set(rows64)):
         do[:, :, m] = (do[:, :, m].float() * BOOST).to(dtype)
     bias = rpe = None
     kind = case["bias"]

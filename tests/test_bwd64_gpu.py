@@ -1,7 +1,9 @@
 """GPU parity tests of the long-sequence backward bodies (csrc/attn_bwd64.h: dK/dV with 64 keys per wave, dQ with 64 query rows
 per wave; software-pipelined step loops, 4-slot LDS rings, AGPR accumulators) -- forced per call with the variant bits FAT5_V_KV64_ON / FAT5_V_Q64_ON (include/fat5.h) at sizes
 the oracle finishes in seconds; at (4,12,8192,64) the default dispatch picks them by itself
-(test_attention_gpu.py::test_cfg3_properties_s8192)."""
+(test_attention_gpu.py::test_cfg3_properties_s8192).
+These are max-norm comparisons against the fp32 oracle.  The non-dense bodies are also held per element to an fp64 restatement with a derived
+bound (tests/test_attn_bwd_fp64_gpu.py, groups kv64, kv64h, kv64m, q64, sep64, fused64, qdiag, causal64); the dense 64-wide bodies are not yet."""
 import pytest
 import torch
 
