@@ -173,6 +173,16 @@ class SpecParams(ctypes.Structure):
     ]
 
 
+class SpecSampleParams(ctypes.Structure):
+    """Mirror of `fat5_spec_sample_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("spec", SpecParams), ("draft_logits", ctypes.c_void_p), ("draft_batch_stride", ctypes.c_int64),
+        ("draft_row_stride", ctypes.c_int64), ("temperature", ctypes.c_float), ("top_p", ctypes.c_float),
+        ("top_k", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_int64),
+        ("uniforms", ctypes.c_void_p), ("sampled", ctypes.c_void_p), ("aux", ctypes.c_void_p),
+    ]
+
+
 class LookupParams(ctypes.Structure):
     """Mirror of `fat5_lookup_params` (include/fat5.h) -- field order must match exactly."""
     _fields_ = [
@@ -200,6 +210,7 @@ EXPORTS = (
     "fat5_beam_step", "fat5_beam_step_workspace_bytes", "fat5_sizeof_beam_params",
     "fat5_process_logits", "fat5_sizeof_logits_params",
     "fat5_spec_accept", "fat5_spec_accept_workspace_bytes", "fat5_sizeof_spec_params",
+    "fat5_spec_accept_sampled", "fat5_spec_accept_sampled_workspace_bytes", "fat5_sizeof_spec_sample_params",
     "fat5_kv_quantize", "fat5_sizeof_kv_quant_params",
     "fat5_lookup_draft", "fat5_sizeof_lookup_params",
 )
@@ -339,6 +350,14 @@ def load():
     if lib.fat5_sizeof_spec_params() != ctypes.sizeof(SpecParams):
         raise ImportError(f"fat5_spec_params layout mismatch: library {lib.fat5_sizeof_spec_params()} B, "
                           f"binding {ctypes.sizeof(SpecParams)} B")
+    lib.fat5_spec_accept_sampled.restype = ctypes.c_int
+    lib.fat5_spec_accept_sampled.argtypes = [ctypes.POINTER(SpecSampleParams), ctypes.c_void_p]
+    lib.fat5_spec_accept_sampled_workspace_bytes.restype = ctypes.c_size_t
+    lib.fat5_spec_accept_sampled_workspace_bytes.argtypes = [ctypes.POINTER(SpecSampleParams)]
+    lib.fat5_sizeof_spec_sample_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_spec_sample_params() != ctypes.sizeof(SpecSampleParams):
+        raise ImportError(f"fat5_spec_sample_params layout mismatch: library {lib.fat5_sizeof_spec_sample_params()} B, "
+                          f"binding {ctypes.sizeof(SpecSampleParams)} B")
     lib.fat5_kv_quantize.restype = ctypes.c_int
     lib.fat5_kv_quantize.argtypes = [ctypes.POINTER(KvQuantParams), ctypes.c_void_p]
     lib.fat5_sizeof_kv_quant_params.restype = ctypes.c_size_t

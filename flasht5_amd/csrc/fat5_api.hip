@@ -25,6 +25,7 @@
 #include "beam_kernels.h"
 #include "logits_kernels.h"
 #include "spec_kernels.h"
+#include "spec_sample_kernels.h"
 #include "lookup_kernels.h"
 
 using namespace fat5;
@@ -1484,9 +1485,8 @@ size_t fat5_spec_accept_workspace_bytes(const fat5_spec_params* p) {
   return align_up((size_t)p->B * p->M * spec_slices(p) * sizeof(uint64_t), 16);
 }
 
-int fat5_spec_accept(const fat5_spec_params* p, void* stream_) {
-  const char* what = "spec_accept";
-  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+// the checks fat5_spec_accept and fat5_spec_accept_sampled share (everything but the workspace)
+static int spec_check(const fat5_spec_params* p, const char* what) {
   if (p->B < 0 || p->B > 65535) return fail(FAT5_EINVAL, "%s: B %d outside [0, 65535]", what, p->B);
   if (p->M < 2 || p->M > SPEC_MAX_M) return fail(FAT5_EINVAL, "%s: M %d outside [2, %d] (gamma + 1)", what, p->M, SPEC_MAX_M);
   if (p->V < 1 || p->V > SPEC_MAX_V) return fail(FAT5_EINVAL, "%s: V %d outside [1, %d]", what, p->V, SPEC_MAX_V);
@@ -1507,10 +1507,10 @@ int fat5_spec_accept(const fat5_spec_params* p, void* stream_) {
   for (const auto& e : t)
     if ((e.need && !e.ptr) || (reinterpret_cast<uintptr_t>(e.ptr) % e.al))
       return fail(FAT5_EINVAL, "%s: %s: %smisaligned pointer", what, e.name, e.need ? "null or " : "");
-  if (p->B == 0) return FAT5_OK;
-  const size_t need = fat5_spec_accept_workspace_bytes(p);
-  if (!p->workspace || !aligned16(p->workspace) || p->workspace_bytes < need)
-    return fail(FAT5_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", what, need, p->workspace_bytes);
+  return FAT5_OK;
+}
+
+static SpecArgs spec_args(const fat5_spec_params* p) {
   SpecArgs a = {};
   a.logits = p->logits;
   a.bstride = p->B > 1 ? p->batch_stride : 0;
@@ -1530,6 +1530,18 @@ int fat5_spec_accept(const fat5_spec_params* p, void* stream_) {
   a.B = p->B, a.M = p->M, a.V = p->V, a.ncols = p->ncols, a.slices = spec_slices(p), a.limit_scalar = p->limit_scalar;
   a.eos = p->eos_token_id;
   a.vec = aligned16(p->logits) && p->row_stride % 8 == 0 && (p->B == 1 || p->batch_stride % 8 == 0);
+  return a;
+}
+
+int fat5_spec_accept(const fat5_spec_params* p, void* stream_) {
+  const char* what = "spec_accept";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  if (int rc = spec_check(p, what)) return rc;
+  if (p->B == 0) return FAT5_OK;
+  const size_t need = fat5_spec_accept_workspace_bytes(p);
+  if (!p->workspace || !aligned16(p->workspace) || p->workspace_bytes < need)
+    return fail(FAT5_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", what, need, p->workspace_bytes);
+  const SpecArgs a = spec_args(p);
   hipStream_t stream = (hipStream_t)stream_;
   const dim3 grid(p->B * p->M, a.slices);
   if (p->dtype == FAT5_F32) hipLaunchKernelGGL((spec_argmax_kernel<FAT5_F32>), grid, dim3(SPEC_THREADS), 0, stream, a);
@@ -1541,6 +1553,76 @@ int fat5_spec_accept(const fat5_spec_params* p, void* stream_) {
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "spec_accept launch");
   return FAT5_OK;
+}
+
+// ---- draft verification of speculative sampling (spec_sample_kernels.h) ----
+size_t fat5_sizeof_spec_sample_params(void) { return sizeof(fat5_spec_sample_params); }
+
+// logits rows the warp launch takes: the B * M target rows, and the B * gamma draft rows when draft_logits is given
+static size_t spec_sample_rows(const fat5_spec_sample_params* p) {
+  return (size_t)p->spec.B * p->spec.M + (p->draft_logits ? (size_t)p->spec.B * (p->spec.M - 1) : 0);
+}
+
+size_t fat5_spec_accept_sampled_workspace_bytes(const fat5_spec_sample_params* p) {
+  if (!p || !spec_shape_ok(&p->spec)) return 0;
+  return align_up(spec_sample_rows(p) * SPEC_SAMPLE_WORDS * sizeof(uint64_t), 16);
+}
+
+int fat5_spec_accept_sampled(const fat5_spec_sample_params* p, void* stream_) {
+  const char* what = "spec_accept_sampled";
+  if (!p) return fail(FAT5_EINVAL, "%s: null params", what);
+  const fat5_spec_params* g = &p->spec;
+  if (int rc = spec_check(g, what)) return rc;
+  if (!std::isfinite(p->temperature) || !(p->temperature > 0.f))
+    return fail(FAT5_EINVAL, "%s: temperature %g (finite and > 0)", what, (double)p->temperature);
+  if (p->top_k < 0) return fail(FAT5_EINVAL, "%s: top_k %d (>= 0)", what, p->top_k);
+  if (!(p->top_p > 0.f && p->top_p <= 1.f)) return fail(FAT5_EINVAL, "%s: top_p %g outside (0, 1]", what, (double)p->top_p);
+  const size_t es = g->dtype == FAT5_F32 ? 4 : 2;
+  if (p->draft_logits) {
+    if (reinterpret_cast<uintptr_t>(p->draft_logits) % es) return fail(FAT5_EINVAL, "%s: draft_logits: misaligned pointer", what);
+    if (p->draft_row_stride < g->V)
+      return fail(FAT5_EINVAL, "%s: draft_row_stride %lld < V %d", what, (long long)p->draft_row_stride, g->V);
+    if (g->B > 1 && p->draft_batch_stride < (int64_t)(g->M - 2) * p->draft_row_stride + g->V)
+      return fail(FAT5_EINVAL, "%s: draft_batch_stride %lld: the rows of two batch elements overlap", what, (long long)p->draft_batch_stride);
+  }
+  if (reinterpret_cast<uintptr_t>(p->uniforms) & 3) return fail(FAT5_EINVAL, "%s: uniforms: misaligned pointer", what);
+  if (reinterpret_cast<uintptr_t>(p->sampled) & 7) return fail(FAT5_EINVAL, "%s: sampled: misaligned pointer", what);
+  if (reinterpret_cast<uintptr_t>(p->aux) & 3) return fail(FAT5_EINVAL, "%s: aux: misaligned pointer", what);
+  if (g->B == 0) return FAT5_OK;
+  const size_t need = fat5_spec_accept_sampled_workspace_bytes(p);
+  if (!g->workspace || !aligned16(g->workspace) || g->workspace_bytes < need)
+    return fail(FAT5_EWORKSPACE, "%s: workspace of %zu bytes (16-byte aligned) needed, %zu given", what, need, g->workspace_bytes);
+  SpecSampleArgs a = {};
+  a.s = spec_args(g);
+  a.draft_logits = p->draft_logits;
+  a.dl_bstride = g->B > 1 ? p->draft_batch_stride : 0;
+  a.dl_stride = p->draft_row_stride;
+  a.uniforms = p->uniforms;
+  a.sampled = p->sampled;
+  a.aux = p->aux;
+  a.seed = p->seed;
+  a.offset = p->offset;
+  a.top_k = p->top_k;
+  a.temperature = p->temperature;
+  a.top_p = p->top_p;
+  a.dl_vec = p->draft_logits && aligned16(p->draft_logits) && p->draft_row_stride % 8 == 0 && (g->B == 1 || p->draft_batch_stride % 8 == 0);
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 rows((unsigned)spec_sample_rows(p));
+  const bool reg = g->V <= SAMPLE_REG_TILES * SAMPLE_TILE;
+  auto go = [&](auto dt_) -> int {
+    constexpr int DT = decltype(dt_)::value;
+    if (reg) hipLaunchKernelGGL((spec_warp_kernel<DT, SAMPLE_REG_TILES>), rows, dim3(SAMPLE_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((spec_warp_kernel<DT, 0>), rows, dim3(SAMPLE_THREADS), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "spec_accept_sampled warp launch");
+    hipLaunchKernelGGL((spec_sample_accept_kernel<DT>), dim3(g->B), dim3(SAMPLE_THREADS), 0, stream, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "spec_accept_sampled launch");
+    return FAT5_OK;
+  };
+  if (g->dtype == FAT5_F32) return go(IC<FAT5_F32>{});
+  if (g->dtype == FAT5_F16) return go(IC<FAT5_F16>{});
+  return go(IC<FAT5_BF16>{});
 }
 
 // ---- prompt-lookup drafting of speculative greedy decoding (lookup_kernels.h) ----

@@ -17,6 +17,9 @@
 //          prefix mass exceeds target (per tile: a block scan of the threads' masses, then the owning thread's 8 elements).
 // Degenerate rows (a NaN or +inf in x, or no finite-or-(-inf) maximum above -inf) give torch.argmax's answer: the first NaN, else
 // the first +inf, else index 0.  No float atomics anywhere; a row's token depends only on its logits, the seed and its counter.
+//
+// The kernel's body is made of device functions that the verification kernels of speculative sampling call too
+// (spec_sample_kernels.h): SampleRow (the row as a workgroup sees it), sample_warp (the passes up to S_kept) and sample_draw.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -100,26 +103,44 @@ FAT5_DEV uint64_t sample_sum(uint64_t v, uint64_t* s_w) {
   return total;
 }
 
+// The workgroup's LDS, declared by the kernel and handed to the parts below
+struct SampleLds {
+  uint64_t* hist;  // [4096]
+  uint64_t* w;     // [SAMPLE_WAVES]
+  float* f;        // [SAMPLE_WAVES]
+  int* i;          // [3 * SAMPLE_WAVES]
+  uint64_t* sel;   // [2]
+  float* m;        // the row's maximum
+};
+#define FAT5_SAMPLE_LDS(s)                                                                                       \
+  __shared__ uint64_t s_hist[4096];                                                                              \
+  __shared__ uint64_t s_w[SAMPLE_WAVES];                                                                         \
+  __shared__ float s_f[SAMPLE_WAVES];                                                                            \
+  __shared__ int s_i[3 * SAMPLE_WAVES];                                                                          \
+  __shared__ uint64_t s_sel[2];                                                                                  \
+  __shared__ float s_m;                                                                                          \
+  const SampleLds s = {s_hist, s_w, s_f, s_i, s_sel, &s_m}
+
+// One logits row as a workgroup sees it: thread t owns elements [8t, 8t + 8) of every tile.
 template <int DT, int NREG>
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_logits_kernel(SampleArgs a) {
+struct SampleRow {
   typedef Elem<DT> E;
   typedef typename E::T T;
-  __shared__ uint64_t s_hist[4096];
-  __shared__ uint64_t s_w[SAMPLE_WAVES];
-  __shared__ float s_f[SAMPLE_WAVES];
-  __shared__ int s_i[3 * SAMPLE_WAVES];
-  __shared__ uint64_t s_sel[2];
-  __shared__ float s_m;
+  const T* row;
+  int V, ntiles, vec, tid;
+  float temperature;
+  // The register-resident row is held as keys, and every pass re-reads the maximum from LDS: nothing derived from the row (keys,
+  // exponentials) can then be kept live from one pass to the next, which would not fit beside the row in the register budget.
+  uint32_t kr[NREG > 0 ? NREG : 1][8];
 
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int V = a.V;
-  const int ntiles = (V + SAMPLE_TILE - 1) / SAMPLE_TILE;
-  const T* row = reinterpret_cast<const T*>(a.logits) + (int64_t)b * a.stride;
+  FAT5_DEV SampleRow(const void* base, int64_t elem_offset, int V_, int vec_, float temperature_)
+      : row(reinterpret_cast<const T*>(base) + elem_offset), V(V_), ntiles((V_ + SAMPLE_TILE - 1) / SAMPLE_TILE), vec(vec_),
+        tid(threadIdx.x), temperature(temperature_) {}
 
   // x of the 8 elements of tile i owned by this thread (elements past V: NaN, never looked at -- every use checks j < V)
-  auto load = [&](int i, float (&x)[8]) {
+  FAT5_DEV void load(int i, float (&x)[8]) const {
     const int j0 = i * SAMPLE_TILE + tid * 8;
-    if (a.vec && j0 + 8 <= V) {
+    if (vec && j0 + 8 <= V) {
       if constexpr (DT == FAT5_F32) {
         float y[4], z[4];
         E::load(row + j0, y);
@@ -134,14 +155,12 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_logits_kernel(SampleArg
       for (int c = 0; c < 8; ++c) x[c] = j0 + c < V ? E::ld1(row + j0 + c) : __builtin_nanf("");
     }
 #pragma unroll
-    for (int c = 0; c < 8; ++c) x[c] = x[c] / a.temperature;
-  };
+    for (int c = 0; c < 8; ++c) x[c] = x[c] / temperature;
+  }
 
-  // The register-resident row is held as keys, and every pass re-reads the maximum from LDS: nothing derived from the row (keys,
-  // exponentials) can then be kept live from one pass to the next, which would not fit beside the row in the register budget.
-  uint32_t kr[NREG > 0 ? NREG : 1][8];
   // f(k[8], j0) over the tiles of the row in order (k: the keys; elements past V hold an unused key)
-  auto tiles = [&](auto&& f) {
+  template <class F>
+  FAT5_DEV void tiles(F&& f) {
     if constexpr (NREG > 0) {
 #pragma unroll
       for (int i = 0; i < NREG; ++i)
@@ -156,14 +175,79 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_logits_kernel(SampleArg
         f(k, i * SAMPLE_TILE + tid * 8);
       }
     }
-  };
+  }
+};
 
+// fixed-point mass of a key; m: the maximum, read from LDS by the pass
+FAT5_DEV uint64_t sample_mass(uint32_t k, float m) { return sample_fixed(__expf(sample_unkey(k) - m)); }
+
+// what the warp part leaves: the thresholds and sums of a row (uniform over the workgroup)
+struct SampleWarp {
+  uint32_t tau;      // the lowest kept key
+  uint64_t S;        // kept mass after top-k
+  uint64_t S_kept;   // kept mass after top-p
+  int degenerate;    // a NaN or +inf in x, or only -inf: `index` is the token
+  int index;
+};
+
+// three-pass radix select: DESC = top-k (counts, from the top), else top-p (masses of keys >= lo_key, from the bottom)
+template <int DT, int NREG>
+FAT5_DEV uint32_t sample_select(SampleRow<DT, NREG>& r, const SampleLds& s, bool desc, uint32_t lo_key, uint64_t goal) {
+  const int tid = r.tid, V = r.V;
+  uint32_t prefix = 0;
+  uint64_t carry = 0;  // count above (top-k) / mass below (top-p) the current prefix's range
+#pragma unroll 1
+  for (int pass = 0; pass < 3; ++pass) {
+    const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0), bits = pass == 0 ? 12 : 10, nb = 1 << bits;
+    for (int i = tid; i < nb; i += SAMPLE_THREADS) s.hist[i] = 0;
+    __syncthreads();
+    const float m = *s.m;
+    r.tiles([&](const uint32_t (&kk)[8], int j0) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        if (j0 + c >= V) continue;
+        const uint32_t k = kk[c];
+        if (k < lo_key || (pass > 0 && (k >> (shift + bits)) != prefix)) continue;
+        const uint64_t add = desc ? 1ull : sample_mass(k, m);
+        if (add) atomicAdd(reinterpret_cast<unsigned long long*>(&s.hist[(k >> shift) & (nb - 1)]), (unsigned long long)add);
+      }
+    });
+    __syncthreads();
+    // thread t scans bins [t * per, (t + 1) * per) in search order (descending keys for top-k, ascending for top-p)
+    const int per = nb / SAMPLE_THREADS;
+    uint64_t v = 0;
+    for (int q = 0; q < per; ++q) {
+      const int b = tid * per + q;
+      v += s.hist[desc ? nb - 1 - b : b];
+    }
+    uint64_t total;
+    uint64_t run = carry + sample_scan(v, s.w, total);
+    for (int q = 0; q < per; ++q) {
+      const int b = tid * per + q, bin = desc ? nb - 1 - b : b;
+      const uint64_t h = s.hist[bin];
+      // top-k: the bin where the count from the top reaches k; top-p: where the mass from the bottom exceeds thr
+      if (h && (desc ? (run < goal && run + h >= goal) : (run <= goal && run + h > goal))) s.sel[0] = bin, s.sel[1] = run;
+      run += h;
+    }
+    __syncthreads();
+    prefix = (prefix << bits) | (uint32_t)s.sel[0];
+    carry = s.sel[1];
+    __syncthreads();  // (s.sel / s.hist are rewritten by the next pass)
+  }
+  return prefix;
+}
+
+// The warp part: the sampler's passes up to S_kept (stats, top-k select, S, top-p select, S_kept).  Fills r.kr on the
+// register-resident path and leaves the maximum in *s.m.
+template <int DT, int NREG>
+FAT5_DEV SampleWarp sample_warp(SampleRow<DT, NREG>& r, const SampleLds& s, int top_k, float top_p) {
+  const int tid = r.tid, lane = tid & 63, w = tid >> 6, V = r.V;
   // ---- pass 0: max, min, first NaN / +inf ----
   float mx = -INFINITY, mn = INFINITY;
   int first_nan = 0x7FFFFFFF, first_inf = 0x7FFFFFFF;
   auto stats = [&](int i, uint32_t (&k)[8]) {
     float x[8];
-    load(i, x);
+    r.load(i, x);
     const int j0 = i * SAMPLE_TILE + tid * 8;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -178,9 +262,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_logits_kernel(SampleArg
   if constexpr (NREG > 0) {
 #pragma unroll
     for (int i = 0; i < NREG; ++i)
-      if (i < ntiles) stats(i, kr[i]);
+      if (i < r.ntiles) stats(i, r.kr[i]);
   } else {
-    for (int i = 0; i < ntiles; ++i) {
+    for (int i = 0; i < r.ntiles; ++i) {
       uint32_t k[8];
       stats(i, k);
     }
@@ -192,20 +276,95 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_logits_kernel(SampleArg
     first_nan = min(first_nan, __shfl_xor(first_nan, off, 64));
     first_inf = min(first_inf, __shfl_xor(first_inf, off, 64));
   }
-  if (lane == 0) s_f[w] = mx, s_i[w] = first_nan, s_i[SAMPLE_WAVES + w] = first_inf, s_i[2 * SAMPLE_WAVES + w] = __float_as_int(mn);
+  if (lane == 0) s.f[w] = mx, s.i[w] = first_nan, s.i[SAMPLE_WAVES + w] = first_inf, s.i[2 * SAMPLE_WAVES + w] = __float_as_int(mn);
   __syncthreads();
   mx = -INFINITY, mn = INFINITY, first_nan = first_inf = 0x7FFFFFFF;
 #pragma unroll
   for (int i = 0; i < SAMPLE_WAVES; ++i) {
-    mx = fmaxf(mx, s_f[i]);
-    mn = fminf(mn, __int_as_float(s_i[2 * SAMPLE_WAVES + i]));
-    first_nan = min(first_nan, s_i[i]);
-    first_inf = min(first_inf, s_i[SAMPLE_WAVES + i]);
+    mx = fmaxf(mx, s.f[i]);
+    mn = fminf(mn, __int_as_float(s.i[2 * SAMPLE_WAVES + i]));
+    first_nan = min(first_nan, s.i[i]);
+    first_inf = min(first_inf, s.i[SAMPLE_WAVES + i]);
   }
-  // every pass re-reads the maximum from s_m (after a barrier of its own), so that nothing derived from it stays live across passes;
+  // every pass re-reads the maximum from *s.m (after a barrier of its own), so that nothing derived from it stays live across passes;
   // this barrier publishes it before the first reader, which may be the kept-mass pass right below when top-k is off
-  if (tid == 0) s_m = mx;
+  if (tid == 0) *s.m = mx;
   __syncthreads();
+
+  SampleWarp o;
+  o.tau = 0, o.S = 0, o.S_kept = 0;
+  o.degenerate = first_nan != 0x7FFFFFFF || first_inf != 0x7FFFFFFF || mx == -INFINITY;
+  o.index = first_nan != 0x7FFFFFFF ? first_nan : (first_inf != 0x7FFFFFFF ? first_inf : 0);
+  if (o.degenerate) return o;  // (uniform over the workgroup: every thread reduced the same values)
+
+  const int k = top_k;
+  uint32_t tau = sample_key(mn);  // (nothing filtered: every element is kept)
+  if (k > 0 && k < V) tau = sample_select(r, s, true, 0u, (uint64_t)k);
+
+  // kept mass after top-k
+  uint64_t part = 0;
+  float m = *s.m;
+  r.tiles([&](const uint32_t (&k)[8], int j0) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (j0 + c < V && k[c] >= tau) part += sample_mass(k[c], m);
+  });
+  const uint64_t S = sample_sum(part, s.w);  // (>= 2^40: the maximum's e is 1)
+  uint64_t S_kept = S;
+  if (top_p < 1.f) {
+    const double t = floor((1.0 - (double)top_p) * (double)S);
+    const uint64_t thr = t >= (double)(S - 1) ? S - 1 : (uint64_t)t;
+    tau = sample_select(r, s, false, tau, thr);
+    part = 0;
+    m = *s.m;
+    r.tiles([&](const uint32_t (&k)[8], int j0) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+        if (j0 + c < V && k[c] >= tau) part += sample_mass(k[c], m);
+    });
+    S_kept = sample_sum(part, s.w);
+  }
+  o.tau = tau, o.S = S, o.S_kept = S_kept;
+  return o;
+}
+
+// The draw part: target = floor(u * total), clamped to total - 1; the token is the first j in vocabulary order whose inclusive
+// prefix of weights exceeds target (per tile: a block scan of the threads' weights, then the owning thread's 8 elements).
+// weigh(k[8], j0, e[8], first) fills the uint64 weights of this thread's 8 elements of the tile in hand (0 for an element that is
+// not kept or lies past V); it is called a second time (first = false) by the one thread that owns the target, so that no weight
+// stays live across the scan.  The token is left in s.i[0] (-1: no prefix exceeded target), published by the caller's next barrier.
+template <int DT, int NREG, class W>
+FAT5_DEV void sample_draw(SampleRow<DT, NREG>& r, const SampleLds& s, float u, uint64_t total, W&& weigh) {
+  const double tu = (u >= 0.f) ? floor((double)u * (double)total) : 0.0;  // (u NaN or negative: 0)
+  const uint64_t target = tu >= (double)(total - 1) ? total - 1 : (uint64_t)tu;
+  uint64_t carry = 0;
+  if (r.tid == 0) s.i[0] = -1;
+  r.tiles([&](const uint32_t (&k)[8], int j0) {
+    uint64_t e[8];
+    weigh(k, j0, e, true);
+    uint64_t v = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v += e[c];
+    uint64_t tile_total;
+    uint64_t run = carry + sample_scan(v, s.w, tile_total);
+    if (run <= target && run + v > target) {
+      weigh(k, j0, e, false);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        if (e[c] && run <= target && run + e[c] > target) s.i[0] = j0 + c;
+        run += e[c];
+      }
+    }
+    carry += tile_total;
+  });
+}
+
+template <int DT, int NREG>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_logits_kernel(SampleArgs a) {
+  FAT5_SAMPLE_LDS(s);
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  SampleRow<DT, NREG> r(a.logits, (int64_t)b * a.stride, a.V, a.vec, a.temperature);
+  const SampleWarp wp = sample_warp(r, s, a.top_k, a.top_p);
 
   // ---- the uniform ----
   float u;
@@ -218,10 +377,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_logits_kernel(SampleArg
     u = (float)(c[0] >> 8) * 0x1p-24f;
   }
 
-  const bool degenerate = first_nan != 0x7FFFFFFF || first_inf != 0x7FFFFFFF || mx == -INFINITY;
-  if (degenerate) {  // (uniform over the workgroup: every thread reduced the same values)
+  if (wp.degenerate) {
     if (tid == 0) {
-      a.tokens[b] = first_nan != 0x7FFFFFFF ? first_nan : (first_inf != 0x7FFFFFFF ? first_inf : 0);
+      a.tokens[b] = wp.index;
       if (a.aux) {
         float* o = a.aux + (int64_t)b * 4;
         o[0] = __builtin_nanf(""), o[1] = __builtin_nanf(""), o[2] = u, o[3] = 0.f;
@@ -230,126 +388,34 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_logits_kernel(SampleArg
     return;
   }
 
-  // fixed-point mass of a key; m: the maximum, read from LDS by the pass
-  auto mass = [](uint32_t k, float m) -> uint64_t { return sample_fixed(__expf(sample_unkey(k) - m)); };
-
-  // three-pass radix select: DESC = top-k (counts, from the top), else top-p (masses of keys >= lo_key, from the bottom)
-  auto select = [&](bool desc, uint32_t lo_key, uint64_t goal) -> uint32_t {
-    uint32_t prefix = 0;
-    uint64_t carry = 0;  // count above (top-k) / mass below (top-p) the current prefix's range
-#pragma unroll 1
-    for (int pass = 0; pass < 3; ++pass) {
-      const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0), bits = pass == 0 ? 12 : 10, nb = 1 << bits;
-      for (int i = tid; i < nb; i += SAMPLE_THREADS) s_hist[i] = 0;
-      __syncthreads();
-      const float m = s_m;
-      tiles([&](const uint32_t (&kk)[8], int j0) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          if (j0 + c >= V) continue;
-          const uint32_t k = kk[c];
-          if (k < lo_key || (pass > 0 && (k >> (shift + bits)) != prefix)) continue;
-          const uint64_t add = desc ? 1ull : mass(k, m);
-          if (add) atomicAdd(reinterpret_cast<unsigned long long*>(&s_hist[(k >> shift) & (nb - 1)]), (unsigned long long)add);
-        }
-      });
-      __syncthreads();
-      // thread t scans bins [t * per, (t + 1) * per) in search order (descending keys for top-k, ascending for top-p)
-      const int per = nb / SAMPLE_THREADS;
-      uint64_t v = 0;
-      for (int q = 0; q < per; ++q) {
-        const int r = tid * per + q;
-        v += s_hist[desc ? nb - 1 - r : r];
-      }
-      uint64_t total;
-      uint64_t run = carry + sample_scan(v, s_w, total);
-      for (int q = 0; q < per; ++q) {
-        const int r = tid * per + q, bin = desc ? nb - 1 - r : r;
-        const uint64_t h = s_hist[bin];
-        // top-k: the bin where the count from the top reaches k; top-p: where the mass from the bottom exceeds thr
-        if (h && (desc ? (run < goal && run + h >= goal) : (run <= goal && run + h > goal))) s_sel[0] = bin, s_sel[1] = run;
-        run += h;
-      }
-      __syncthreads();
-      prefix = (prefix << bits) | (uint32_t)s_sel[0];
-      carry = s_sel[1];
-      __syncthreads();  // (s_sel / s_hist are rewritten by the next pass)
-    }
-    return prefix;
-  };
-
-  const int k = a.top_k;
-  uint32_t tau = sample_key(mn);  // (nothing filtered: every element is kept)
-  if (k > 0 && k < V) tau = select(true, 0u, (uint64_t)k);
-
-  // kept mass after top-k
-  uint64_t part = 0;
-  float m = s_m;
-  tiles([&](const uint32_t (&k)[8], int j0) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-      if (j0 + c < V && k[c] >= tau) part += mass(k[c], m);
-  });
-  const uint64_t S = sample_sum(part, s_w);  // (>= 2^40: the maximum's e is 1)
-  uint64_t S_kept = S;
-  if (a.top_p < 1.f) {
-    const double t = floor((1.0 - (double)a.top_p) * (double)S);
-    const uint64_t thr = t >= (double)(S - 1) ? S - 1 : (uint64_t)t;
-    tau = select(false, tau, thr);
-    part = 0;
-    m = s_m;
-    tiles([&](const uint32_t (&k)[8], int j0) {
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-        if (j0 + c < V && k[c] >= tau) part += mass(k[c], m);
-    });
-    S_kept = sample_sum(part, s_w);
-  }
-
   // ---- the draw: first kept j whose inclusive prefix mass exceeds target ----
-  const double tu = (u >= 0.f) ? floor((double)u * (double)S_kept) : 0.0;  // (u NaN or negative: 0)
-  const uint64_t target = tu >= (double)(S_kept - 1) ? S_kept - 1 : (uint64_t)tu;
+  const uint32_t tau = wp.tau;
   int kept = 0, last = -1;
-  uint64_t carry = 0;
-  if (tid == 0) s_i[0] = -1;
-  m = s_m;
-  tiles([&](const uint32_t (&k)[8], int j0) {
-    uint64_t v = 0;
+  const float m = *s.m;
+  const int V = a.V;
+  sample_draw(r, s, u, wp.S_kept, [&](const uint32_t (&k)[8], int j0, uint64_t (&e)[8], bool first) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c)
-      if (j0 + c < V && k[c] >= tau) {
-        v += mass(k[c], m);
-        ++kept;
-        last = j0 + c;
-      }
-    uint64_t total;
-    uint64_t run = carry + sample_scan(v, s_w, total);
-    if (run <= target && run + v > target) {
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-        if (j0 + c < V && k[c] >= tau) {
-          const uint64_t e = mass(k[c], m);
-          if (run <= target && run + e > target) s_i[0] = j0 + c;
-          run += e;
-        }
+    for (int c = 0; c < 8; ++c) {
+      const bool in = j0 + c < V && k[c] >= tau;
+      e[c] = in ? sample_mass(k[c], m) : 0;
+      if (in && first) ++kept, last = j0 + c;
     }
-    carry += total;
   });
-  const uint64_t kept_all = sample_sum((uint64_t)kept, s_w);  // (its barriers publish s_i[0])
-  const int token = s_i[0];
+  const uint64_t kept_all = sample_sum((uint64_t)kept, s.w);  // (its barriers publish s.i[0])
+  const int token = s.i[0];
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
   __syncthreads();
-  if (lane == 0) s_i[1 + w] = last;
+  if (lane == 0) s.i[1 + w] = last;
   __syncthreads();
   if (tid == 0) {
     int lst = -1;
-    for (int i = 0; i < SAMPLE_WAVES; ++i) lst = max(lst, s_i[1 + i]);
+    for (int i = 0; i < SAMPLE_WAVES; ++i) lst = max(lst, s.i[1 + i]);
     a.tokens[b] = token >= 0 ? token : lst;  // (the fallback cannot be needed with exact sums; it keeps the token a kept one)
     if (a.aux) {
       float* o = a.aux + (int64_t)b * 4;
       o[0] = sample_unkey(tau);
-      o[1] = (float)((double)S_kept / (double)S);
+      o[1] = (float)((double)wp.S_kept / (double)wp.S);
       o[2] = u;
       o[3] = (float)kept_all;
     }

@@ -107,22 +107,11 @@ __global__ __launch_bounds__(SPEC_THREADS) void spec_argmax_kernel(SpecArgs a) {
   }
 }
 
-__global__ __launch_bounds__(64) void spec_accept_kernel(SpecArgs a) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int M = a.M, gamma = M - 1;
-  // a_i: the slice words of row (b, i) in slice order (slice 0 always holds an element: V >= 1)
-  int64_t am = -1;
-  if (lane < M) {
-    const uint64_t* p = a.ws + ((int64_t)b * M + lane) * a.slices;
-    uint64_t best = 0;
-    for (int s = 0; s < a.slices; ++s) best = p[s] > best ? p[s] : best;
-    am = (int64_t)(0xFFFFFFFFu - (uint32_t)best);
-  }
-  const int64_t d = lane < gamma ? a.draft[(int64_t)b * a.draft_stride + lane] : -2;  // (an id outside [0, V) equals no a_i)
-  const unsigned long long miss = __ballot(!(lane < gamma && d == am));  // (bit gamma is always set)
-  const int n = __ffsll(miss) - 1;  // leading matches, 0 .. gamma
-  const int64_t bonus = __shfl(am, n, 64);
-  // the candidates in lane order: the n accepted drafts, then a_n
+// The bookkeeping of one batch row, by the row's first wave (all 64 lanes): n leading drafts stand, lane i < gamma holds d_i and
+// `bonus` is the token after them.  Shared by the greedy kernel below and the sampled one (spec_sample_kernels.h).
+FAT5_DEV void spec_bookkeep(const SpecArgs& a, int b, int lane, int n, int64_t d, int64_t bonus) {
+  const int M = a.M;
+  // the candidates in lane order: the n accepted drafts, then the token after them
   const int64_t cand = lane < n ? d : bonus;
   const unsigned long long is_eos = __ballot(lane <= n && cand == (int64_t)a.eos);
   const int old_len = (int)((uint32_t)a.cache_seqlens[b] - (uint32_t)M);  // (wraps, never traps, whatever the length holds)
@@ -152,6 +141,24 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(SpecArgs a) {
     if (a.n_accepted) a.n_accepted[b] = n < c ? n : c;
     if (a.n_new) a.n_new[b] = c;
   }
+}
+
+__global__ __launch_bounds__(64) void spec_accept_kernel(SpecArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int M = a.M, gamma = M - 1;
+  // a_i: the slice words of row (b, i) in slice order (slice 0 always holds an element: V >= 1)
+  int64_t am = -1;
+  if (lane < M) {
+    const uint64_t* p = a.ws + ((int64_t)b * M + lane) * a.slices;
+    uint64_t best = 0;
+    for (int s = 0; s < a.slices; ++s) best = p[s] > best ? p[s] : best;
+    am = (int64_t)(0xFFFFFFFFu - (uint32_t)best);
+  }
+  const int64_t d = lane < gamma ? a.draft[(int64_t)b * a.draft_stride + lane] : -2;  // (an id outside [0, V) equals no a_i)
+  const unsigned long long miss = __ballot(!(lane < gamma && d == am));  // (bit gamma is always set)
+  const int n = __ffsll(miss) - 1;  // leading matches, 0 .. gamma
+  const int64_t bonus = __shfl(am, n, 64);
+  spec_bookkeep(a, b, lane, n, d, bonus);
 }
 
 }  // namespace fat5

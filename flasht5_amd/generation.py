@@ -31,7 +31,7 @@ Decoder prompts (`decoder_input_ids` (B, P)): the first P - 1 promp
 (`decode_chunk`: M tokens per row, M key / value rows appended per layer by the chunk decode kernel, causal inside the chunk), the
 loop then starts from the prompt's last token.  `decode_chunk` is also the verification step of speculative decoding.
 
-Speculative greedy decoding (`assistant_model`; flasht5_amd/speculative.py): a second, cheaper model drafts gamma
+Speculative decoding, greedy or sampled (`assistant_model`; flasht5_amd/speculative.py): a second, cheaper model drafts gamma
 tokens per round, one `decode_chunk` step of gamma + 1 rows checks them, and the verification kernel accepts, rolls the per-row
 lengths back and does the step's bookkeeping on the device.  Without an assistant none of it runs: the code path above is unchanged.
 With `prompt_lookup_num_tokens` (flasht5_amd/prompt_lookup.py) the drafter is no model but ONE launch per round that
@@ -446,6 +446,15 @@ def _sample_pick(logits, state, tok, labels, seen_eos, sampling, proc=None):
     seen_eos.logical_or_(nxt == 1)
 
 
+def _spec_sampling(do_sample, temperature, top_k, top_p, seed):
+    """the `sampling` tuple of a speculative loop (None when greedy); a missing seed is drawn as in plain sampling"""
+    if not do_sample:
+        return None
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64))
+    return (float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
 def finish_labels(labels, last=None):
     """the reference's ending (:682-688): the last column becomes 1, and everything after each row's first 1 becomes 0.  `last`
     (B,) int64 on the device: each row's own last column (ragged prompts: rows end at different columns)"""
@@ -550,7 +559,8 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     num_beams > 1 it is rejected.
 
     `assistant_model` (a second FAT5ForConditionalGeneration with the same vocabulary size; None: everything above, unchanged):
-    speculative greedy decoding (flasht5_amd/speculative.py).  The assistant runs its own encoder once on input_ids
+    speculative decoding (flasht5_amd/speculative.py; with do_sample=True speculative sampling, DESIGN 4.19, see
+    below).  The assistant runs its own encoder once on input_ids
     and drafts `num_assistant_tokens` = gamma in [1, 15] tokens per round with gamma + 1 one-token steps; the model checks them in
     one `decode_chunk` step of gamma + 1 rows, and the verification kernel keeps the agreeing prefix plus the model's own next
     token and rolls both models' lengths back, per row, on the device.  One host read per round; graph=True captures one whole
@@ -558,9 +568,18 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     assistant -- the drafts only decide how many model steps it takes -- up to the rounding of a chunk step against a one-row
     step where two logits are within it.  decoder_input_ids works as above.  return_stats=True returns
     (labels, {"rounds", "drafted", "accepted"}) with host ints: the rounds run, the tokens drafted for unfinished rows and how many
-    of them were accepted.  Rejected on the host before either encoder runs: do_sample=True, num_beams > 1, any active logits
+    of them were accepted.  Rejected on the host before either encoder runs: num_beams > 1, any active logits
     processor, num_assistant_tokens outside [1, 15], a vocabulary mismatch, a model the decode path refuses, and RoPE models
     with more than one batch row (rows advance raggedly; the decode path keeps one rotary position for the batch).
+
+    do_sample=True with `assistant_model` or `prompt_lookup_num_tokens`: speculative sampling.  The assistant draws
+    its drafts with `sample_logits` under the same warpers and a Philox key of its own (seed ^ 0x9E3779B97F4A7C15), and the
+    verification kernel accepts draft d ~ q with probability min(1, p(d) / q(d)), redrawing the first rejected position from
+    norm(max(p - q, 0)); the lookup's drafts are taken as one-hot (accepted with probability p(d)).  Every emitted token is
+    distributed exactly as the plain sampler's at that position -- the sequences differ from the call without a drafter, their
+    law does not -- and with top_k=1 the result is the greedy one.  The seed is handled as in plain sampling; graph=True,
+    decoder_input_ids, the padding masks, kv_cache_dtype and return_stats work as in the greedy speculative loop.
+    input_ids that are not on the GPU are refused on the host, after every other check and before an encoder runs.
 
     Padding.  `attention_mask` (B, L) and `decoder_attention_mask` (B, P), bool or integer, right-padded with at
     least one valid position per row, are validated together with ONE host read before any encoder runs; holes, left padding
@@ -580,14 +599,14 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     encoder runs.
 
     `prompt_lookup_num_tokens` = gamma in [1, 15] (HF's name; None: everything above, unchanged -- no launch, no allocation is
-    added): speculative greedy decoding without a second model (flasht5_amd/prompt_lookup.py).  Per round ONE launch
+    added): speculative decoding without a second model (flasht5_amd/prompt_lookup.py).  Per round ONE launch
     proposes, per row, the gamma tokens that followed the earliest, longest occurrence (up to `max_matching_ngram_size` = N in
     [1, 16] tokens, HF's name) of the row's last n-gram in input_ids -- inside `attention_mask`: padding is never proposed -- or
     in the row's own sequence, the decoder prompt included; the chunk step and the verification kernel are those of
     `assistant_model`, so the result is what the call returns without it, with the same caveat.  graph=True captures one whole
     round after the first eager one; decoder_input_ids, kv_cache_dtype and return_stats work as with an assistant (`drafted`
     counts the tokens the lookup proposed for unfinished rows, `accepted` those of them that became output).  Rejected on the
-    host before the encoder runs: an assistant_model beside it, do_sample=True, num_beams > 1, any active logits processor, a
+    host before the encoder runs: an assistant_model beside it, num_beams > 1, any active logits processor, a
     ragged decoder prompt, a non-int or out-of-range prompt_lookup_num_tokens / max_matching_ngram_size, a model the decode
     path refuses, RoPE at B > 1, and a cache beyond the rotary tables."""
     check_kv_cache_dtype(kv_cache_dtype)
@@ -604,21 +623,24 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
             raise ValueError("generate: a ragged decoder prompt with RoPE needs B = 1: the decode path keeps one rotary position "
                              f"for the batch, and the rows of this one start at {dec_pad.lengths}")
     proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, P)
+    if do_sample and (prompt_lookup_num_tokens is not None or assistant_model is not None):
+        from .sampling import check_args as check_sampling_args
+        check_sampling_args(temperature, top_k, top_p)
     if prompt_lookup_num_tokens is not None:
         from .speculative import check_lookup_generate_args, speculative_generate
         check_lookup_generate_args(model, input_ids, max_length, prompt_lookup_num_tokens, max_matching_ngram_size, P, do_sample,
                                    num_beams, proc is not None, assistant_model)
+        spec_sampling = _spec_sampling(do_sample, temperature, top_k, top_p, seed)
         return speculative_generate(model, None, input_ids, attention_mask, max_length, graph, prompt_lookup_num_tokens, P,
-                                    decoder_input_ids, bool(return_stats), kv_cache_dtype, lookup_ngram=max_matching_ngram_size)
+                                    decoder_input_ids, bool(return_stats), kv_cache_dtype, lookup_ngram=max_matching_ngram_size,
+                                    sampling=spec_sampling)
     if assistant_model is not None:
         from .speculative import check_generate_args, speculative_generate
         check_generate_args(model, assistant_model, input_ids, max_length, num_assistant_tokens, P, do_sample, num_beams,
                             proc is not None)
-        if kv_cache_dtype is not None:
-            return speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, P,
-                                        decoder_input_ids, bool(return_stats), kv_cache_dtype)
+        spec_sampling = _spec_sampling(do_sample, temperature, top_k, top_p, seed)
         return speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, P,
-                                    decoder_input_ids, bool(return_stats))
+                                    decoder_input_ids, bool(return_stats), kv_cache_dtype, sampling=spec_sampling)
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
                               early_stopping, return_scores, proc, kv_cache_dtype)

@@ -1,8 +1,8 @@
-"""Prompt-lookup drafting for speculative greedy decoding: the drafter is no model but a search.  Per row, the
+"""Prompt-lookup drafting for speculative decoding: the drafter is no model but a search.  Per row, the
 tokens that followed the row's last n-gram the first time it occurred -- in the encoder input or in the row's own sequence --
 are proposed as the next round's draft (HF's `prompt_lookup_num_tokens`).  One HIP launch per round (`fat5_lookup_draft`,
 csrc/lookup_kernels.h) instead of gamma + 1 decoder steps of an assistant; the verification (`speculative_round`) is unchanged,
-so the output is what greedy decoding gives.
+so the output is what greedy decoding gives (with do_sample=True the drafts are verified as one-hot by the sampled rule).
 
     draft, n_proposed = prompt_lookup_draft(source, labels, cache_seqlens, tok, seen_eos, num_tokens, max_ngram=2,
                                             src_seqlens=None, vocab_size=None, out=None)

@@ -750,6 +750,67 @@ size_t fat5_spec_accept_workspace_bytes(const fat5_spec_params* p);
 int fat5_spec_accept(const fat5_spec_params* p, void* hip_stream);
 
 /*
+ * Draft verification of speculative SAMPLING (Leviathan et al. 2023; Chen et al. 2023): one round for all B rows on the device
+ * (spec_sample_kernels.h).  `spec` holds everything fat5_spec_accept takes, with the same meaning: the target's
+ * chunk logits (B, M, V), M = gamma + 1, draft (B, gamma), cache_seqlens ALREADY advanced by M (old = cache_seqlens[b] - M), and
+ * the bookkeeping arrays.  draft_logits (B, gamma, V), in the dtype of logits, holds in row i the drafter's logits d_i was
+ * drawn from; NULL stands for a one-hot drafter (a prompt lookup, a script).
+ *
+ * Distributions.  P_i is the warped distribution of logits[b, i], formed exactly as fat5_sample_logits forms it: x = fp32(logit)
+ * / temperature, the kept set from tau_k and tau_p, e_j = the sampler's fp32 exp(x_j - max x) truncated to a multiple of 2^-40,
+ * S_kept their exact fixed-point sum, and P_i(j) = e_j / S_kept in fp64 (0 outside the kept set).  Q_i is the same for
+ * draft_logits[b, i]; with draft_logits NULL, Q_i is one-hot at d_i.  A degenerate row (a NaN or +inf in x, or only -inf) is
+ * one-hot at the index the sampler's degenerate-row rule gives (the first NaN, else the first +inf, else 0).
+ *
+ * Uniforms.  (w0, w1, w2, w3) = Philox4x32-10 with key (seed lo, seed hi) and counter (lo, hi of offset + old + 1 + i, b, 0):
+ * the block fat5_sample_logits would use for the token in column old + 1 + i.  u0, u1, u2 = (w >> 8) * 2^-24 of w0, w1, w2.
+ * uniforms (optional, (B, M, 3) fp32 contiguous) replaces them; aux (optional, (B, M, 3) fp32 out) receives the three that
+ * were used for every chunk row.
+ *
+ * Acceptance.  Draft i is accepted iff every draft before it was, d_i lies in [0, V), and u1 * Q_i(d_i) < P_i(d_i) in fp64 (so
+ * P = 0 rejects and Q = 0 with P > 0 accepts).  n is the number of accepted drafts.
+ *
+ * The token after them.  With n = gamma it is the plain sampler's draw from P_gamma with u0: the first kept j whose inclusive
+ * prefix of e exceeds min(floor(u0 * S_kept), S_kept - 1), the token fat5_sample_logits returns for that row and counter.
+ * Otherwise it is the residual draw: r_j = floor(max(0, P_n(j) - Q_n(j)) * 2^40) as uint64, R their sum, and the token is the
+ * first j in vocabulary order whose inclusive prefix of r exceeds min(floor(u2 * R), R - 1); with R = 0, P_n's masses e and
+ * S_kept take the place of r and R (still with u2).  Every emitted token is then distributed as the plain sampler's.
+ *
+ * Bookkeeping.  The candidates are d_0 .. d_{n-1} followed by that token; from there on the text of fat5_spec_accept holds
+ * unchanged: the EOS and limit cuts, frozen rows, labels, tok, both length vectors, seen_eos, n_accepted, n_new, and no write
+ * outside columns [1, ncols) of labels.  sampled (optional, (B, M) int64 out): per chunk row the token it contributes, d_i for
+ * i < n, the drawn token for i = n, -1 for i > n (before the cuts); all -1 on a frozen row, which skips the draw.
+ *
+ * Two launches on `hip_stream`; grid and workspace are functions of B, M, V and of whether draft_logits is given; nothing is
+ * read back by the host; every sum is an integer sum (no float atomics), so the result is bitwise reproducible.  Loads follow
+ * fat5_spec_accept's rule, for draft_logits with its own strides.  B == 0 is a no-op.
+ * Rejected with FAT5_EINVAL before anything is launched: everything fat5_spec_accept rejects; a non-finite or non-positive
+ * temperature, top_k < 0, top_p outside (0, 1]; with draft_logits a misaligned pointer, draft_row_stride < V, or (B > 1)
+ * draft_batch_stride < (M - 2) * draft_row_stride + V; misaligned uniforms / sampled / aux.  FAT5_EWORKSPACE when spec.workspace
+ * is missing, misaligned (16 bytes) or smaller than fat5_spec_accept_sampled_workspace_bytes().
+ */
+typedef struct fat5_spec_sample_params {
+  fat5_spec_params spec;        /* as for fat5_spec_accept; workspace: fat5_spec_accept_sampled_workspace_bytes() bytes */
+  const void* draft_logits;     /* (B, M - 1, V) in spec.dtype, innermost stride 1, or NULL: one-hot drafts */
+  int64_t draft_batch_stride;   /* elements */
+  int64_t draft_row_stride;     /* elements */
+  float temperature;            /* > 0, finite */
+  float top_p;                  /* (0, 1]; 1: no top-p */
+  int32_t top_k;                /* 0 (or >= V): no top-k */
+  int32_t reserved;             /* 0 */
+  uint64_t seed;                /* Philox key */
+  int64_t offset;               /* added to every counter */
+  const float* uniforms;        /* (B, M, 3) fp32 device array replacing the Philox words, or NULL */
+  int64_t* sampled;             /* (B, M) int64 out, or NULL */
+  float* aux;                   /* (B, M, 3) fp32 out, or NULL */
+} fat5_spec_sample_params;
+/* sizeof(fat5_spec_sample_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_spec_sample_params(void);
+/* bytes of workspace for (B, M, V, draft_logits given or not); 0 for a NULL pointer or a shape fat5_spec_accept rejects */
+size_t fat5_spec_accept_sampled_workspace_bytes(const fat5_spec_sample_params* p);
+int fat5_spec_accept_sampled(const fat5_spec_sample_params* p, void* hip_stream);
+
+/*
  * Prompt-lookup drafting for speculative greedy decoding (lookup_kernels.h): per row, the draft of the next
  * verification round is what followed the row's last n-gram the first time it occurred, in the encoder input or in the row's own
  * sequence.  Per row b, with len = cache_seqlens[b]:
