@@ -14,6 +14,7 @@ _VAR = os.environ.get("FAT5_LIB_VARIANT", "")
 LIB_PATH = os.path.join(_HERE, "lib", "libfat5" + ("_" + _VAR if _VAR else "") + ".so")
 
 FAT5_F32, FAT5_F16, FAT5_BF16 = 0, 1, 2
+FAT5_FORCED_BOS, FAT5_FORCED_EOS = 1, 2  # fat5_logits_params.forced_tokens
 BIAS_NONE, BIAS_DENSE, BIAS_RPE1D = 0, 1, 2
 KV_NATIVE, KV_FP8_E4M3 = 0, 1  # fat5_kv_cache_dtype
 MAX_RPE_RADIUS = 1024  # forward alone takes 2048; the backward's per-wave diagonal accumulators must fit LDS (include/fat5.h)
@@ -157,6 +158,14 @@ class LogitsParams(ctypes.Structure):
         ("sequences", ctypes.c_void_p), ("seq_stride", ctypes.c_int64), ("lengths", ctypes.c_void_p), ("seq_len", ctypes.c_int32),
         ("repetition_penalty", ctypes.c_float), ("no_repeat_ngram_size", ctypes.c_int32), ("min_length", ctypes.c_int32),
         ("eos_token_id", ctypes.c_int32), ("n_suppress", ctypes.c_int32), ("suppress_tokens", ctypes.c_void_p),
+        # appended: all zero / None is the call as it was
+        ("encoder_repetition_penalty", ctypes.c_double), ("encoder_input_ids", ctypes.c_void_p), ("encoder_stride", ctypes.c_int64),
+        ("encoder_lengths", ctypes.c_void_p), ("encoder_rows", ctypes.c_int32), ("encoder_len", ctypes.c_int32),
+        ("rows_per_encoder_row", ctypes.c_int32), ("encoder_no_repeat_ngram_size", ctypes.c_int32),
+        ("bad_words_ids", ctypes.c_void_p), ("bad_words_offsets", ctypes.c_void_p), ("bad_words_offsets_host", ctypes.c_void_p),
+        ("n_bad_words", ctypes.c_int32), ("n_bad_word_ids", ctypes.c_int32), ("min_new_tokens", ctypes.c_int32),
+        ("prompt_length", ctypes.c_int32), ("prompt_lengths", ctypes.c_void_p), ("max_new_tokens", ctypes.c_int32),
+        ("forced_tokens", ctypes.c_int32), ("forced_bos_token_id", ctypes.c_int32), ("forced_eos_token_id", ctypes.c_int32),
     ]
 
 

@@ -1445,6 +1445,53 @@ int fat5_process_logits(const fat5_logits_params* p, void* stream_) {
   const bool inplace = static_cast<const void*>(p->out) == p->logits;
   if (inplace && (p->dtype != FAT5_F32 || p->out_stride != p->row_stride))
     return fail(FAT5_EINVAL, "%s: in place (out == logits) needs fp32 logits and out_stride == row_stride", what);
+  // ---- the appended fields (all zero / NULL: the call as it was) ----
+  const double phi = p->encoder_repetition_penalty;
+  if (!std::isfinite(phi) || phi < 0.0) return fail(FAT5_EINVAL, "%s: encoder_repetition_penalty %g (finite and > 0; 0 or 1: off)", what, phi);
+  const bool enc_pen = phi != 0.0 && phi != 1.0;
+  if (p->encoder_no_repeat_ngram_size < 0)
+    return fail(FAT5_EINVAL, "%s: encoder_no_repeat_ngram_size %d (>= 0)", what, p->encoder_no_repeat_ngram_size);
+  const bool enc_on = enc_pen || p->encoder_no_repeat_ngram_size > 0;
+  if (enc_on) {
+    if (!p->encoder_input_ids || (reinterpret_cast<uintptr_t>(p->encoder_input_ids) & 7))
+      return fail(FAT5_EINVAL, "%s: encoder_input_ids: null or misaligned pointer with an encoder processor on", what);
+    if (p->encoder_len < 1 || p->encoder_len > LOGITS_MAX_ENC)
+      return fail(FAT5_EINVAL, "%s: encoder_len %d outside [1, %d]", what, p->encoder_len, LOGITS_MAX_ENC);
+    if (p->encoder_stride < p->encoder_len)
+      return fail(FAT5_EINVAL, "%s: encoder_stride %lld < encoder_len %d", what, (long long)p->encoder_stride, p->encoder_len);
+    if (p->encoder_lengths && (reinterpret_cast<uintptr_t>(p->encoder_lengths) & 3)) return fail(FAT5_EINVAL, "%s: encoder_lengths: misaligned pointer", what);
+    if (p->rows_per_encoder_row < 1 || p->encoder_rows < 1 || (int64_t)p->encoder_rows * p->rows_per_encoder_row < p->rows)
+      return fail(FAT5_EINVAL, "%s: %d encoder_rows of %d rows_per_encoder_row do not cover %d rows", what, p->encoder_rows,
+                  p->rows_per_encoder_row, p->rows);
+  }
+  if (p->n_bad_words < 0 || p->n_bad_words > LOGITS_MAX_BAD_WORDS)
+    return fail(FAT5_EINVAL, "%s: n_bad_words %d outside [0, %d]", what, p->n_bad_words, LOGITS_MAX_BAD_WORDS);
+  if (p->n_bad_words > 0) {
+    if (p->n_bad_word_ids < p->n_bad_words || p->n_bad_word_ids > LOGITS_MAX_BAD_IDS)
+      return fail(FAT5_EINVAL, "%s: n_bad_word_ids %d outside [n_bad_words, %d]", what, p->n_bad_word_ids, LOGITS_MAX_BAD_IDS);
+    if (!p->bad_words_ids || (reinterpret_cast<uintptr_t>(p->bad_words_ids) & 3)) return fail(FAT5_EINVAL, "%s: bad_words_ids: null or misaligned pointer", what);
+    if (!p->bad_words_offsets || (reinterpret_cast<uintptr_t>(p->bad_words_offsets) & 3))
+      return fail(FAT5_EINVAL, "%s: bad_words_offsets: null or misaligned pointer", what);
+    if (const int32_t* o = p->bad_words_offsets_host) {  // the host's copy of the offsets: checked here, before the launch
+      if (o[0] != 0 || o[p->n_bad_words] != p->n_bad_word_ids)
+        return fail(FAT5_EINVAL, "%s: bad_words_offsets run from %d to %d, not from 0 to n_bad_word_ids %d", what, o[0], o[p->n_bad_words], p->n_bad_word_ids);
+      for (int i = 0; i < p->n_bad_words; ++i)
+        if (o[i + 1] <= o[i]) return fail(FAT5_EINVAL, "%s: bad_words_offsets not increasing at %d (%d, %d)", what, i, o[i], o[i + 1]);
+    }
+  }
+  if (p->min_new_tokens < 0) return fail(FAT5_EINVAL, "%s: min_new_tokens %d (>= 0)", what, p->min_new_tokens);
+  if (p->forced_tokens & ~(FAT5_FORCED_BOS | FAT5_FORCED_EOS)) return fail(FAT5_EINVAL, "%s: forced_tokens %d", what, p->forced_tokens);
+  if ((p->forced_tokens & FAT5_FORCED_BOS) && (p->forced_bos_token_id < 0 || p->forced_bos_token_id >= p->V))
+    return fail(FAT5_EINVAL, "%s: forced_bos_token_id %d outside [0, V)", what, p->forced_bos_token_id);
+  if ((p->forced_tokens & FAT5_FORCED_EOS) && (p->forced_eos_token_id < 0 || p->forced_eos_token_id >= p->V))
+    return fail(FAT5_EINVAL, "%s: forced_eos_token_id %d outside [0, V)", what, p->forced_eos_token_id);
+  if ((p->forced_tokens & FAT5_FORCED_EOS) && p->max_new_tokens < 1)
+    return fail(FAT5_EINVAL, "%s: max_new_tokens %d (>= 1 with a forced EOS)", what, p->max_new_tokens);
+  if (p->min_new_tokens > 0 || (p->forced_tokens & FAT5_FORCED_EOS)) {
+    if (p->prompt_lengths ? (reinterpret_cast<uintptr_t>(p->prompt_lengths) & 3) != 0 : p->prompt_length < 1)
+      return fail(FAT5_EINVAL, "%s: prompt_lengths misaligned, or NULL with prompt_length %d (>= 1)", what, p->prompt_length);
+  }
+  const bool ext = enc_on || p->n_bad_words > 0 || p->min_new_tokens > 0 || p->forced_tokens != 0;
   if (p->rows == 0) return FAT5_OK;
   LogitsArgs a = {};
   a.logits = p->logits;
@@ -1464,9 +1511,26 @@ int fat5_process_logits(const fat5_logits_params* p, void* stream_) {
   a.vec_out = aligned16(p->out) && p->out_stride % 4 == 0;
   hipStream_t stream = (hipStream_t)stream_;
   const dim3 grid(p->rows);
-  if (p->dtype == FAT5_F32) hipLaunchKernelGGL((process_logits_kernel<FAT5_F32>), grid, dim3(LOGITS_THREADS), 0, stream, a);
-  else if (p->dtype == FAT5_F16) hipLaunchKernelGGL((process_logits_kernel<FAT5_F16>), grid, dim3(LOGITS_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((process_logits_kernel<FAT5_BF16>), grid, dim3(LOGITS_THREADS), 0, stream, a);
+  if (ext) {  // the instance with the encoder-side processors, bad words, min_new_tokens and the forced tokens
+    a.enc = enc_on ? p->encoder_input_ids : nullptr;
+    a.enc_stride = p->encoder_stride;
+    a.enc_lengths = p->encoder_lengths;
+    a.enc_len = enc_on ? p->encoder_len : 0;
+    a.rows_per_enc = p->rows_per_encoder_row;
+    a.enc_ngram = p->encoder_no_repeat_ngram_size;
+    a.enc_penalty = enc_pen ? (float)(1.0 / p->encoder_repetition_penalty) : 1.f;  // (HF: 1 / phi in double, used as an fp32 scalar)
+    a.bad_ids = p->bad_words_ids, a.bad_off = p->bad_words_offsets, a.n_bad = p->n_bad_words, a.n_bad_ids = p->n_bad_word_ids;
+    a.min_new = p->min_new_tokens, a.prompt_length = p->prompt_length, a.prompt_lengths = p->prompt_lengths;
+    a.max_new = p->max_new_tokens;
+    a.forced_bos = (p->forced_tokens & FAT5_FORCED_BOS) ? p->forced_bos_token_id : -1;
+    a.forced_eos = (p->forced_tokens & FAT5_FORCED_EOS) ? p->forced_eos_token_id : -1;
+    const size_t lds = (size_t)((a.enc_len + LOGITS_ENC_PAD - 1) & ~(LOGITS_ENC_PAD - 1)) * sizeof(int32_t);
+    if (p->dtype == FAT5_F32) hipLaunchKernelGGL((process_logits_kernel<FAT5_F32, true>), grid, dim3(LOGITS_THREADS), lds, stream, a);
+    else if (p->dtype == FAT5_F16) hipLaunchKernelGGL((process_logits_kernel<FAT5_F16, true>), grid, dim3(LOGITS_THREADS), lds, stream, a);
+    else hipLaunchKernelGGL((process_logits_kernel<FAT5_BF16, true>), grid, dim3(LOGITS_THREADS), lds, stream, a);
+  } else if (p->dtype == FAT5_F32) hipLaunchKernelGGL((process_logits_kernel<FAT5_F32, false>), grid, dim3(LOGITS_THREADS), 0, stream, a);
+  else if (p->dtype == FAT5_F16) hipLaunchKernelGGL((process_logits_kernel<FAT5_F16, false>), grid, dim3(LOGITS_THREADS), 0, stream, a);
+  else hipLaunchKernelGGL((process_logits_kernel<FAT5_BF16, false>), grid, dim3(LOGITS_THREADS), 0, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "process_logits launch");
   return FAT5_OK;

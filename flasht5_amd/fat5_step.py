@@ -319,10 +319,13 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
                  top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
                  return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None,
                  decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
-                 decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2):
+                 decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
+                 encoder_repetition_penalty=1.0, encoder_no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
+                 forced_bos_token_id=None, forced_eos_token_id=None):
         """greedy (or, with do_sample=True, temperature / top-k / top-p sampled) decoding with a KV cache; returns what the
         reference's generate returns; num_beams > 1: HF's beam search; repetition_penalty / no_repeat_ngram_size / min_length /
-        suppress_tokens: HF's logits processors in one HIP launch per step; decoder_input_ids (B, P): a decoder prompt, prefilled
+        suppress_tokens / encoder_repetition_penalty / encoder_no_repeat_ngram_size / bad_words_ids / min_new_tokens /
+        forced_bos_token_id / forced_eos_token_id: HF's logits processors in one HIP launch per step; decoder_input_ids (B, P): a decoder prompt, prefilled
         in one chunk step; assistant_model: speculative greedy decoding, num_assistant_tokens drafted per round and verified in one
         chunk step; attention_mask / decoder_attention_mask: right-padded inputs and ragged decoder prompts; kv_cache_dtype="fp8": the K / V
         caches as e4m3fn bytes plus per-row scales, in every mode; prompt_lookup_num_tokens / max_matching_ngram_size: speculative greedy
@@ -335,7 +338,11 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
                         suppress_tokens=suppress_tokens, decoder_input_ids=decoder_input_ids, assistant_model=assistant_model,
                         num_assistant_tokens=num_assistant_tokens, return_stats=return_stats,
                         decoder_attention_mask=decoder_attention_mask, kv_cache_dtype=kv_cache_dtype,
-                        prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size)
+                        prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
+                        encoder_repetition_penalty=encoder_repetition_penalty,
+                        encoder_no_repeat_ngram_size=encoder_no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+                        min_new_tokens=min_new_tokens, forced_bos_token_id=forced_bos_token_id,
+                        forced_eos_token_id=forced_eos_token_id)
 
 
 def allreduce_gradients(model: nn.Module, group=None, average=True):

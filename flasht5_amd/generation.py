@@ -25,7 +25,9 @@ or reordered: each beam reads its history through the `cache_row_batch` table of
 Logits processors (`repetition_penalty`, `no_repeat_ngram_size`, `min_length`, `suppress_tokens`) are one more HIP
 launch between the decode step and the argmax / sampler / beam step (flasht5_amd/logits_process.py): it reads the running
 sequences (`labels`, `running_seqs`) and `cache_seqlens` on the device, so the step stays one graph.  With all of them at
-their defaults the launch is not made.
+their defaults the launch is not made.  The same launch runs the encoder-decoder ones (`encoder_repetition_penalty`,
+`encoder_no_repeat_ngram_size`, `bad_words_ids`, `min_new_tokens`, `forced_bos_token_id`, `forced_eos_token_id`): it then also
+reads `input_ids` with the encoder lengths and the rows' decoder-prompt lengths on the device.
 
 Decoder prompts (`decoder_input_ids` (B, P)): the first P - 1 prompt tokens go through the decoder in ONE chunk step
 (`decode_chunk`: M tokens per row, M key / value rows appended per layer by the chunk decode kernel, causal inside the chunk), the
@@ -489,7 +491,7 @@ def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, le
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask, num_beams=k, kv_cache_dtype=kv_cache_dtype)
     bs = new_state(B, k, int(max_length) + 1, state.capacity, dev)
-    proc = _proc_on_device(proc, dev)
+    proc = _proc_on_device(proc, dev, input_ids, attention_mask, None, k)
     bs.cache_row_batch = state.row_batch  # (one table: the decode kernel reads it, the beam step reorders it)
     tok = torch.zeros((B * k,), dtype=torch.long, device=dev)
     opts = (int(max_length), float(length_penalty), early_stopping)
@@ -521,7 +523,9 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
              top_p=1.0, seed=None, num_beams=1, num_return_sequences=1, length_penalty=1.0, early_stopping=False,
              return_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=None,
              decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
-             decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2):
+             decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
+             encoder_repetition_penalty=1.0, encoder_no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
+             forced_bos_token_id=None, forced_eos_token_id=None):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -549,6 +553,19 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     and does not renormalise.  They are checked on the host before the encoder runs; with every one at its default no launch
     is added and the step is the code path above.  The sequence buffer of a call with processors holds at most 4096 columns
     (max_length <= 4095).
+
+    Six more of HF's processors run in the same launch, in HF's place in the chain (encoder repetition penalty, repetition
+    penalty, n-grams, encoder n-grams, bad words, min_length, min_new_tokens, forced BOS, forced EOS, suppress_tokens), in the
+    same modes: `encoder_repetition_penalty` (a float > 0, 1.0 = off: the tokens of the row's input_ids are favoured by
+    1 / penalty), `encoder_no_repeat_ngram_size` (0 = off: no n-gram of the row's input_ids is copied), `bad_words_ids` (a
+    non-empty list of non-empty lists of ids: a sequence's last token is banned once the row ends in its prefix; [[1]] is
+    dropped as HF drops it; at most 1024 sequences of 4096 ids, packed to the device once per call), `min_new_tokens` (EOS is
+    banned for the first that many NEW tokens, whatever the decoder prompt's length -- per row with ragged prompts),
+    `forced_bos_token_id` (the first token after a lone start token; HF's literal rule, so it never fires behind a longer
+    decoder prompt) and `forced_eos_token_id` (the token at each row's own last position P_b + max_length - 1).  The encoder
+    ids of a row are its input_ids inside its attention_mask -- HF's classes see the padding too; here a padded row decodes what
+    it decodes alone -- and a beam reads the ids of its batch row; at most 4096 encoder ids per row.  All are checked on the
+    host before the encoder runs; with all ten processor arguments at their defaults no launch and no allocation is added.
 
     `decoder_input_ids` (B, P) int64, P >= 1: a decoder prompt as HF takes it, the start token included (None is [[0]]).  Up to
     max_length new tokens follow it; the result is (B, P + steps): the prompt, then the new tokens, with the same ending.  The
@@ -622,7 +639,9 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
         if model.decoder.block[0].self_attention_layer.self_attention.rotary and input_ids.shape[0] > 1:
             raise ValueError("generate: a ragged decoder prompt with RoPE needs B = 1: the decode path keeps one rotary position "
                              f"for the batch, and the rows of this one start at {dec_pad.lengths}")
-    proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, P)
+    proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, P,
+                             encoder_repetition_penalty, encoder_no_repeat_ngram_size, bad_words_ids, min_new_tokens,
+                             forced_bos_token_id, forced_eos_token_id, input_ids.shape[-1])
     if do_sample and (prompt_lookup_num_tokens is not None or assistant_model is not None):
         from .sampling import check_args as check_sampling_args
         check_sampling_args(temperature, top_k, top_p)
@@ -644,7 +663,7 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
                               early_stopping, return_scores, proc, kv_cache_dtype)
-    proc = _proc_on_device(proc, input_ids.device)
+    proc = _proc_on_device(proc, input_ids.device, input_ids, attention_mask, dec_pad)
     step = _greedy_step
 
     def pick(logits, state, tok, labels, seen_eos):
@@ -706,25 +725,46 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     return finish_labels(labels[:, :steps + P])
 
 
-def _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompt_length=1):
-    """host-side validation of the logits processors -> None when all of them are off, else process_logits' keyword arguments"""
-    from .logits_process import MAX_SEQ_LEN, active, check_args
-    check_args(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, model.lm_head.weight.shape[0])
-    if not active(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens):
+def _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompt_length=1,
+                      encoder_repetition_penalty=1.0, encoder_no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
+                      forced_bos_token_id=None, forced_eos_token_id=None, encoder_length=1):
+    """host-side validation of the logits processors -> None when all of them are off, else process_logits' keyword arguments
+    (without the tensors `_proc_on_device` adds)"""
+    from .logits_process import MAX_ENCODER_LEN, MAX_SEQ_LEN, active, check_args
+    check_args(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, model.lm_head.weight.shape[0], 1,
+               encoder_repetition_penalty, encoder_no_repeat_ngram_size, bad_words_ids, min_new_tokens, forced_bos_token_id,
+               forced_eos_token_id)
+    if not active(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, encoder_repetition_penalty,
+                  encoder_no_repeat_ngram_size, bad_words_ids, min_new_tokens, forced_bos_token_id, forced_eos_token_id):
         return None
     if int(max_length) + int(prompt_length) > MAX_SEQ_LEN:
         raise ValueError(f"max_length {max_length}: the logits processors hold at most {MAX_SEQ_LEN} sequence columns "
                          f"(max_length <= {MAX_SEQ_LEN - int(prompt_length)})")
+    if (encoder_repetition_penalty != 1.0 or encoder_no_repeat_ngram_size > 0) and int(encoder_length) > MAX_ENCODER_LEN:
+        raise ValueError(f"input_ids of {encoder_length} columns: the encoder-side logits processors hold at most {MAX_ENCODER_LEN} "
+                         "encoder ids per row")
     return dict(repetition_penalty=float(repetition_penalty), no_repeat_ngram_size=int(no_repeat_ngram_size),
-                min_length=int(min_length), eos_token_id=1, suppress_tokens=suppress_tokens)
+                min_length=int(min_length), eos_token_id=1, suppress_tokens=suppress_tokens,
+                encoder_repetition_penalty=encoder_repetition_penalty, encoder_no_repeat_ngram_size=int(encoder_no_repeat_ngram_size),
+                bad_words_ids=bad_words_ids, min_new_tokens=int(min_new_tokens), forced_bos_token_id=forced_bos_token_id,
+                forced_eos_token_id=forced_eos_token_id, prompt_length=int(prompt_length), max_new_tokens=int(max_length))
 
 
-def _proc_on_device(proc, device):
-    """the suppressed ids moved to the device, once per call"""
+def _proc_on_device(proc, device, input_ids=None, enc_pad=None, dec_pad=None, num_beams=1):
+    """the suppressed ids and the bad words moved to the device, once per call, and what the step's launch reads besides the
+    sequences: the encoder ids with their per-row lengths (`enc_pad`, a Padding or None), the rows per encoder row (num_beams)
+    and the per-row decoder-prompt lengths of a ragged prompt (`dec_pad`)"""
     if proc is None:
         return None
-    from .logits_process import suppress_to_device
-    return dict(proc, suppress_tokens=suppress_to_device(proc["suppress_tokens"], device))
+    from .logits_process import pack_bad_words, suppress_to_device
+    proc = dict(proc, suppress_tokens=suppress_to_device(proc["suppress_tokens"], device),
+                bad_words_ids=pack_bad_words(proc["bad_words_ids"], device, proc["eos_token_id"]))
+    if proc["encoder_repetition_penalty"] != 1.0 or proc["encoder_no_repeat_ngram_size"] > 0:
+        proc.update(encoder_input_ids=input_ids.to(device=device, dtype=torch.int64).contiguous(),
+                    encoder_lengths=None if enc_pad is None else enc_pad.lengths_dev, rows_per_encoder_row=int(num_beams))
+    if dec_pad is not None:
+        proc.update(prompt_lengths=dec_pad.lengths_dev)
+    return proc
 
 
 def _capture(model, state, tok, labels, seen_eos, step=_greedy_step):

@@ -672,6 +672,35 @@ int fat5_beam_step(const fat5_beam_params* p, void* hip_stream);
  * repetition_penalty, no_repeat_ngram_size < 0, min_length < 0, eos_token_id outside [0, V), n_suppress outside [0, 4096],
  * NULL or misaligned logits / out / sequences / lengths (/ suppress_tokens with n_suppress > 0), out == logits with a 16-bit
  * dtype or unequal strides.
+ *
+ * The appended fields switch on six more of HF's processors in the SAME launch (EncoderRepetitionPenaltyLogitsProcessor,
+ * EncoderNoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor, MinNewTokensLengthLogitsProcessor,
+ * ForcedBOSTokenLogitsProcessor, ForcedEOSTokenLogitsProcessor).  The whole order is HF's: encoder repetition penalty,
+ * repetition penalty, no-repeat n-grams, encoder no-repeat n-grams, bad words, min_length, min_new_tokens, forced BOS, forced
+ * EOS, suppress_tokens.  With P_r = prompt_lengths[r] (prompt_length when NULL), the row's decoder-prompt length with the start
+ * token, and e = the encoder ids of row r -- encoder_input_ids[r / rows_per_encoder_row, 0:L), L = clamp(encoder_lengths[...], 0,
+ * encoder_len), an entry outside [0, V) again "no token":
+ *   a. encoder_repetition_penalty = phi: every distinct token t of e gets, once, x_t < 0 ? x_t * p : x_t / p with
+ *      p = fp32(1.0 / phi) (the division in double, as HF forms it; then fp32 arithmetic, IEEE division).  It comes before
+ *      step 1: a token of e that also occurs in seq gets rep(enc(x_t)).
+ *   b. encoder_no_repeat_ngram_size = n: if s >= n - 1, for every i in [0, L - n] with e[i : i+n-1] == seq[s-n+1 : s],
+ *      y[e[i+n-1]] = -inf (n = 1 bans every encoder id).
+ *   c. bad words: sequence b of length len bans its last token if len == 1, or if s >= len and seq[s-len+1 : s] equals its
+ *      first len - 1 ids (HF skips a sequence longer than the context: s >= len, not s >= len - 1).
+ *   d. min_new_tokens = m: if s - P_r < m, y[eos_token_id] = -inf.
+ *   e. forced BOS t: if s == 1, the whole row becomes -inf and y_t = 0.  HF's literal rule: it never fires behind a decoder
+ *      prompt of more than one token.
+ *   f. forced EOS t: the same overwrite if s - P_r == max_new_tokens - 1 (HF: cur_len == max_length - 1 with its
+ *      max_length = P + max_new_tokens).  If both fire, the EOS decides.  suppress_tokens still applies afterwards.
+ * Deviation from HF: HF's two encoder classes take the padded (B, L) ids and so treat the pad id as an encoder token; here
+ * only the ids inside the row's length count, so that a padded row is processed as it is alone.
+ * Also rejected with FAT5_EINVAL before anything is launched: a negative or non-finite encoder_repetition_penalty,
+ * encoder_no_repeat_ngram_size < 0; with an encoder processor on, a NULL or misaligned encoder_input_ids, encoder_len outside
+ * [1, 4096], encoder_stride < encoder_len, a misaligned encoder_lengths, encoder_rows * rows_per_encoder_row < rows;
+ * n_bad_words outside [0, 1024], n_bad_word_ids outside [n_bad_words, 4096], NULL or misaligned bad_words_ids /
+ * bad_words_offsets, host offsets that do not start at 0, are not strictly increasing or do not end at n_bad_word_ids (the
+ * kernel clamps the device offsets it reads); min_new_tokens < 0; unknown forced_tokens bits, a forced id outside [0, V),
+ * max_new_tokens < 1 with a forced EOS; prompt_length < 1 (or a misaligned prompt_lengths) where P is read.
  */
 typedef struct fat5_logits_params {
   int32_t rows, V;
@@ -691,7 +720,30 @@ typedef struct fat5_logits_params {
   int32_t eos_token_id;         /* [0, V) */
   int32_t n_suppress;           /* 0..4096 */
   const int32_t* suppress_tokens; /* (n_suppress,) int32 device array, or NULL when n_suppress is 0 */
+  /* ---- appended; all zero / NULL: the call as it was (same launch, same bits) ---- */
+  double encoder_repetition_penalty;    /* phi > 0, finite; 0 or 1: off.  A double: HF forms 1 / phi in double */
+  const int64_t* encoder_input_ids;     /* (encoder_rows, encoder_len) int64 device array, row stride encoder_stride elements */
+  int64_t encoder_stride;
+  const int32_t* encoder_lengths;       /* (encoder_rows,) int32 device array, or NULL: every row holds encoder_len ids */
+  int32_t encoder_rows;
+  int32_t encoder_len;                  /* 1..4096 */
+  int32_t rows_per_encoder_row;         /* row r uses encoder row r / rows_per_encoder_row (num_beams; 1 otherwise) */
+  int32_t encoder_no_repeat_ngram_size; /* >= 0; 0: off */
+  const int32_t* bad_words_ids;         /* (n_bad_word_ids,) int32 device array: the sequences, one after the other */
+  const int32_t* bad_words_offsets;     /* (n_bad_words + 1,) int32 device array: sequence b is ids[offsets[b] : offsets[b+1]) */
+  const int32_t* bad_words_offsets_host;/* the same offsets in HOST memory, or NULL; checked before the launch when given */
+  int32_t n_bad_words;                  /* 0..1024; 0: off */
+  int32_t n_bad_word_ids;               /* n_bad_words..4096 */
+  int32_t min_new_tokens;               /* >= 0; 0: off */
+  int32_t prompt_length;                /* P >= 1, the start token included; read when prompt_lengths is NULL */
+  const int32_t* prompt_lengths;        /* (rows,) int32 device array of P_r, or NULL */
+  int32_t max_new_tokens;               /* >= 1 with a forced EOS */
+  int32_t forced_tokens;                /* FAT5_FORCED_BOS | FAT5_FORCED_EOS; 0: off */
+  int32_t forced_bos_token_id;          /* [0, V) when FAT5_FORCED_BOS is set */
+  int32_t forced_eos_token_id;          /* [0, V) when FAT5_FORCED_EOS is set */
 } fat5_logits_params;
+#define FAT5_FORCED_BOS 1
+#define FAT5_FORCED_EOS 2
 /* sizeof(fat5_logits_params) as compiled into the library (bindings check their mirror against it). */
 size_t fat5_sizeof_logits_params(void);
 int fat5_process_logits(const fat5_logits_params* p, void* hip_stream);

@@ -8,7 +8,12 @@ before it is timed), captured the same way.  Roofline: rows V (e + 4) bytes, the
 
 End to end, FAT5-base in bf16, L_enc = 512, 64 new tokens forced (no early stop): ms per token of graph-replayed cached decoding
 with n = 3, theta = 1.2, min_length = 30 against the same step without processors -- greedy and sampled at B in {1, 16, 64}, beam
-search (k = 4) at B in {1, 16} -- alternated, tools/bench_sample.py's and bench_beam.py's method.  Prints one JSON line at the end."""
+search (k = 4) at B in {1, 16} -- alternated, tools/bench_sample.py's and bench_beam.py's method.  Prints one JSON line at the end.
+
+`--ext`: the same shapes with the six further processors (L_enc 512, encoder n = 3, phi = 1.2, 16 bad-word sequences,
+min_new_tokens above s, a forced EOS that does not fire) next to the launch with only the old four arguments, alternated, and
+the end-to-end rows with them ("*_ext").  `--kernel-only` leaves the end-to-end part out; the "kernel" rows of a
+`--kernel-only` run of this file at two commits, alternated in one session, compare the old-argument launch across them."""
 import json
 import os
 import statistics
@@ -120,7 +125,52 @@ def kernel_rows(reps=7):
     return rows_out
 
 
+def ext_kernel_rows(reps=7, L_enc=512):
+    """the launch with all ten processors against the launch with the old four, same rows, alternated"""
+    from flasht5_amd import pack_bad_words
+    rows_out = {}
+    theta, n = 1.2, 3
+    for rows, V in ((1, 32128), (64, 32128), (64, 250112)):
+        for s in (64, 512):
+            L = s + 1
+            g0 = torch.Generator().manual_seed(rows + V + s)
+            logits = (torch.randn(rows, V, generator=g0) * 3).bfloat16().cuda()
+            seqs = torch.randint(0, 2000, (rows, L), generator=g0).cuda()
+            enc = torch.randint(0, 2000, (rows, L_enc), generator=g0).cuda()
+            lens = torch.full((rows,), s, dtype=torch.int32, device="cuda")
+            sup = torch.arange(32000, 32100, dtype=torch.int32, device="cuda")
+            bad = pack_bad_words([[int(t) for t in torch.randint(2, 2000, (1 + i % 3,), generator=g0)] for i in range(16)], "cuda")
+            old = dict(repetition_penalty=theta, no_repeat_ngram_size=n, min_length=s + 1, suppress_tokens=sup)
+            new = dict(old, encoder_repetition_penalty=1.2, encoder_no_repeat_ngram_size=3, encoder_input_ids=enc, bad_words_ids=bad,
+                       min_new_tokens=s + 1, forced_eos_token_id=1, max_new_tokens=4095)
+            for ls in (False, True):
+                g_old = _graph(lambda: process_logits(logits, seqs, lens, log_softmax=ls, **old))
+                g_new = _graph(lambda: process_logits(logits, seqs, lens, log_softmax=ls, **new))
+                t_old, t_new = [], []
+                for _ in range(reps):  # (alternated)
+                    t_old.append(_time(g_old))
+                    t_new.append(_time(g_new))
+                del g_old, g_new
+                key = f"rows{rows}_V{V}_s{s}_{'logsoftmax' if ls else 'plain'}"
+                us = lambda v: round(v * 1e6, 2)  # noqa: E731
+                rows_out[key] = {"old4_us": us(statistics.median(t_old)), "old4_min_max_us": [us(min(t_old)), us(max(t_old))],
+                                 "ext10_us": us(statistics.median(t_new)), "ext10_min_max_us": [us(min(t_new)), us(max(t_new))]}
+                print(f"{key:40s}: old four {rows_out[key]['old4_us']:8.2f} us {rows_out[key]['old4_min_max_us']} | all ten "
+                      f"{rows_out[key]['ext10_us']:8.2f} us {rows_out[key]['ext10_min_max_us']}", flush=True)
+    return rows_out
+
+
 PROC = dict(repetition_penalty=1.2, no_repeat_ngram_size=3, min_length=30, eos_token_id=1, suppress_tokens=None)
+EXT = "--ext" in sys.argv
+
+
+def _ext_proc(ids, k=1):
+    """PROC plus the six further processors, as `generate` hands them to the step"""
+    from flasht5_amd import pack_bad_words
+    proc = dict(PROC, encoder_repetition_penalty=1.2, encoder_no_repeat_ngram_size=3, min_new_tokens=30, forced_eos_token_id=1,
+                bad_words_ids=pack_bad_words([[5 + i, 9 + i] for i in range(16)], ids.device), encoder_input_ids=ids,
+                rows_per_encoder_row=k, max_new_tokens=64)
+    return proc
 
 
 def _replay_ms(g, steps):
@@ -158,6 +208,10 @@ def e2e_rows(new_tokens=64, L_enc=512, reps=3):
                 "sample": lambda m, st, t, lb, e: generation._sample_step(m, st, t, lb, e, sampling),
                 "sample_proc": lambda m, st, t, lb, e: generation._sample_step(m, st, t, lb, e, sampling, PROC),
             }
+            if EXT:
+                ext = _ext_proc(ids)
+                steps["greedy_ext"] = lambda m, st, t, lb, e: generation._greedy_step(m, st, t, lb, e, ext)
+                steps["sample_ext"] = lambda m, st, t, lb, e: generation._sample_step(m, st, t, lb, e, sampling, ext)
             cached(steps["greedy"])  # warm-up
             ms = {k: [] for k in steps}
             for _ in range(reps):  # (alternated)
@@ -166,6 +220,9 @@ def e2e_rows(new_tokens=64, L_enc=512, reps=3):
             row = {k: round(statistics.median(v), 4) for k, v in ms.items()}
             row["greedy_overhead_pct"] = round((row["greedy_proc"] / row["greedy"] - 1) * 100, 2)
             row["sample_overhead_pct"] = round((row["sample_proc"] / row["sample"] - 1) * 100, 2)
+            if EXT:
+                row["greedy_ext_overhead_pct"] = round((row["greedy_ext"] / row["greedy"] - 1) * 100, 2)
+                row["sample_ext_overhead_pct"] = round((row["sample_ext"] / row["sample"] - 1) * 100, 2)
             row["all"] = {k: [round(x, 4) for x in v] for k, v in ms.items()}
             out[f"B{B}"] = row
             print(f"B={B:3d}: {row}", flush=True)
@@ -185,11 +242,17 @@ def e2e_rows(new_tokens=64, L_enc=512, reps=3):
 
             beam(None)
             ms = {"beam": [], "beam_proc": []}
+            if EXT:
+                ms["beam_ext"] = []
             for _ in range(reps):
                 ms["beam"].append(beam(None))
                 ms["beam_proc"].append(beam(PROC))
+                if EXT:
+                    ms["beam_ext"].append(beam(_ext_proc(ids, k)))
             row = {k_: round(statistics.median(v), 4) for k_, v in ms.items()}
             row["beam_overhead_pct"] = round((row["beam_proc"] / row["beam"] - 1) * 100, 2)
+            if EXT:
+                row["beam_ext_overhead_pct"] = round((row["beam_ext"] / row["beam"] - 1) * 100, 2)
             row["all"] = {k_: [round(x, 4) for x in v] for k_, v in ms.items()}
             out[f"beam_B{B}_k{k}"] = row
             print(f"beam B={B:3d} k={k}: {row}", flush=True)
@@ -198,6 +261,8 @@ def e2e_rows(new_tokens=64, L_enc=512, reps=3):
 
 if __name__ == "__main__":
     res = {"kernel": kernel_rows()}
+    if EXT:
+        res["kernel_ext"] = ext_kernel_rows()
     if "--kernel-only" not in sys.argv:
         res["end_to_end"] = e2e_rows()
     print(json.dumps(res))
