@@ -152,14 +152,14 @@ def _check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius, cache
                              f"({H}, {2 * int(radius) + 1}) tensor, got {rpe1d.dtype} {tuple(rpe1d.shape)}")
 
 
-def _check_devices(q, k_cache, v_cache, k, v, rpe1d):
+def _check_devices(q, k_cache, v_cache, k, v, rpe1d, what="flash_attn_with_kvcache"):
     for t in (q, k_cache, v_cache, k, v, rpe1d):
         if t is None:
             continue
         if not t.is_cuda:
-            raise ValueError("flash_attn_with_kvcache: tensors must be on the GPU (there is no CPU path)")
+            raise ValueError(f"{what}: tensors must be on the GPU (there is no CPU path)")
         if t.device != q.device:
-            raise ValueError("flash_attn_with_kvcache: tensors on different devices")
+            raise ValueError(f"{what}: tensors on different devices")
 
 
 def _check(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius, cache_batch_idx=None, cache_row_batch=None, k_scale=None,
@@ -371,16 +371,6 @@ def _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, radius,
     _check_chunk_seqlens(chunk_seqlens, B)
 
 
-def _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d):
-    for t in (q, k_cache, v_cache, k, v, rpe1d):
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise ValueError("flash_attn_with_kvcache_chunk: tensors must be on the GPU (there is no CPU path)")
-        if t.device != q.device:
-            raise ValueError("flash_attn_with_kvcache_chunk: tensors on different devices")
-
-
 @torch.library.custom_op("fat5::attn_decode_chunk", mutates_args=("k_cache", "v_cache"), device_types="cuda")
 def attn_decode_chunk(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor],
                       v: Optional[torch.Tensor], cache_seqlens: Optional[torch.Tensor], sm_scale: float, causal: bool,
@@ -394,7 +384,7 @@ def attn_decode_chunk(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
 def _attn_decode_chunk(q, k_cache, v_cache, k, v, cache_seqlens, sm_scale, causal, rpe1d, rpe_radius, return_lse, num_splits,
                        chunk_seqlens=None, k_scale=None, v_scale=None):
     _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius, chunk_seqlens, k_scale, v_scale)
-    _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d)
+    _check_devices(q, k_cache, v_cache, k, v, rpe1d, "flash_attn_with_kvcache_chunk")
     _check_chunk_seqlens(chunk_seqlens, q.shape[0], q.device, "fat5::attn_decode_chunk")
     if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or cache_seqlens.device != q.device or
                                       not cache_seqlens.is_contiguous()):
@@ -465,7 +455,7 @@ def flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k=None, v=None, cache_seq
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32)
     _chunk_check_shapes(q, k_cache, v_cache, k, v, cache_seqlens, rpe1d, rpe_radius, chunk_seqlens, k_scale, v_scale)  # (before the device checks)
-    _chunk_check_devices(q, k_cache, v_cache, k, v, rpe1d)
+    _check_devices(q, k_cache, v_cache, k, v, rpe1d, "flash_attn_with_kvcache_chunk")
     lens = _as_seqlens(cache_seqlens, q.device)
     scale = 1.0 / math.sqrt(q.shape[-1]) if softmax_scale is None else float(softmax_scale)
     if k_scale is not None:

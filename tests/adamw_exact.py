@@ -60,7 +60,7 @@ TINY = {F32: 0.0, F16: 2.0 ** -25, BF16: 0.0}         # half the spacing of fp16
 U32 = 2.0 ** -24
 f32 = np.float32
 
-# (DT, SDT, KAHAN): every instantiation the host dispatches (fat5_api.hip:1604-1621)
+# (DT, SDT, KAHAN): every instantiation the host dispatches (adamw_step_impl, api_rowwise.hip)
 TRIPLES = [(F32, F32, 0), (F32, BF16, 0), (F32, F16, 0), (BF16, BF16, 0), (BF16, BF16, 1), (F16, F16, 0), (F16, F16, 1),
            (BF16, F16, 1), (F16, BF16, 0)]
 
@@ -134,7 +134,7 @@ def dev_scalars(cfg):
 
 
 def host_scalars(cfg, mut=None):
-    """the fp32 values the kernel sees: adamw_step_impl's double-to-float casts (fat5_api.hip:1592-1595), the c_float of the
+    """the fp32 values the kernel sees: adamw_step_impl's double-to-float casts (api_rowwise.hip), the c_float of the
     descriptor (adamw_scaled.py:145), or the three device scalars (adamw_kernels.h:107-109)"""
     lr, wd = float(cfg["lr"]), float(cfg["wd"])
     H = {"beta1": f32(cfg["beta1"]), "beta2": f32(cfg["beta2"]), "eps": f32(cfg["eps"]),               # :1592

@@ -30,7 +30,7 @@ body.  With A_max the largest A_i, c T would need c >= A_max-dependent, a whole-
 
 The bound.  u = 2^-24; an addition inside an MFMA is charged 2 u; u_T = 2^-8 / 2^-11; gamma_k(n) = k n u / (1 - k n u) the any-order
 summation constant.  Lines cited as b:LINE (csrc/attn_bwd.h), c:LINE (attn_common.h), d:LINE (attn_bwd_dbias.h), r:LINE
-(reduce_kernels.h), ds:LINE (diag_sum.h), api:LINE (fat5_api.hip).
+(reduce_kernels.h), ds:LINE (diag_sum.h), api (fat5_attn_bwd_stages, api_attn.hip: where it sets `a.ds_out`).
   e_p, the recomputed probability.  dQ body: s = k . q accumulates D products on the matrix pipe (b:215), 2 D u of smag; one FMA
       x = fma(s, c2, bias2 + nL2) in front of v_exp_f32 (b:221, b:228, b:237-240, b:244): c2 = scale * kLog2e (b:181) 2 u, the table entry
       * kLog2e (c:326) or bias_log2 (c:152) 2 u of bmag, nL2 = -L * kLog2e (b:114) 2 u of |L|, the add bias2 + nL2 and the FMA u each of
@@ -51,7 +51,7 @@ summation constant.  Lines cited as b:LINE (csrc/attn_bwd.h), c:LINE (attn_commo
           c_dk = (1 + u_T) (1 + 2^-23 + (2 D + 1) u + gamma_2(M + 1) + u) - 1,   c_dq likewise with N
           err_X = c_X T_X + (1 + u_T) (c_A TA_X + D u TD_X) + [fp16: the absolute term],   |got - ref| <= err + ulp_T(|ref| + err) / 2
   dbias.  Every route of these bodies starts from the dS the dQ body (b:260-282) or the batch-inner kernel (d:193-198) has ROUNDED to
-      the dtype.  "direct" (api:308): that rounded dS is dbias: err = e_dS T + ..., one rounding.  "staged" (api:306, r:53-72): the rounded
+      the dtype.  "direct" (api: ds_out = dbias): that rounded dS is dbias: err = e_dS T + ..., one rounding.  "staged" (api: ds_out in the workspace, r:53-72): the rounded
       dS of the nsum (batch, head) pairs are summed in fp32 and rounded once: u_T T + gamma_1(nsum) T (1 + u_T) (+ nsum 2^-25 in fp16).
       "inkernel" (d:192-198, d:226, d:240): the same, the fp32 sum passing through a scratch slab beyond four batch elements.
   drpe1d / table.  The 32-key body forms the diagonal sums from the fp32 dS, NOT the rounded one (b:730, b:736, b:742: `s`, before

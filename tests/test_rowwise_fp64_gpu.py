@@ -1,4 +1,4 @@
-"""Every launch path of the row-wise kernels (csrc/rowwise_kernels.h, csrc/fold_weights.h; host dispatch in csrc/fat5_api.hip)
+"""Every launch path of the row-wise kernels (csrc/rowwise_kernels.h, csrc/fold_weights.h; host dispatch in csrc/api_rowwise.hip)
 against the fp64 restatements of tests/rowwise_fp64.py, on both sides of each dispatch predicate.  Each case names the kernel
 instance it targets.  The module-level wrappers are called directly (rms_norm.rmsnorm_fwd, fused_linear.fold_weights, ...) so
 that strided views reach the kernels as they are; a misaligned base, which every wrapper would copy, goes through the C ABI.
@@ -121,7 +121,7 @@ def _check_bwd(dx, dw, dy, x, w, rstd, what, vector, dres=None):
 
 
 def _rows_vec(n, dtype, *ts):
-    """the 16-byte-row part of the host's `vecok` (fat5_api.hip): n a multiple of 8, row strides of VEC, 16-byte aligned bases
+    """the 16-byte-row part of the host's `vecok` (fat5_rmsnorm_fwd and its siblings, api_rowwise.hip): n a multiple of 8, row strides of VEC, 16-byte aligned bases
     (the outputs and w the wrappers allocate or make contiguous are aligned)"""
     return n % 8 == 0 and all(t.stride(0) % VEC[dtype] == 0 and t.data_ptr() % 16 == 0 for t in ts)
 
