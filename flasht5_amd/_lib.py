@@ -204,6 +204,15 @@ class LookupParams(ctypes.Structure):
     ]
 
 
+class PackParams(ctypes.Structure):
+    """Mirror of `fat5_pack_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("L", ctypes.c_int32), ("seg_cap", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("seg", ctypes.c_void_p), ("cu_seqlens", ctypes.c_void_p), ("index", ctypes.c_void_p), ("seg_count", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+    ]
+
+
 EXPORTS = (
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
@@ -222,6 +231,7 @@ EXPORTS = (
     "fat5_spec_accept_sampled", "fat5_spec_accept_sampled_workspace_bytes", "fat5_sizeof_spec_sample_params",
     "fat5_kv_quantize", "fat5_sizeof_kv_quant_params",
     "fat5_lookup_draft", "fat5_sizeof_lookup_params",
+    "fat5_pack_plan", "fat5_sizeof_pack_params",
 )
 
 _lib = None
@@ -379,6 +389,12 @@ def load():
     if lib.fat5_sizeof_lookup_params() != ctypes.sizeof(LookupParams):
         raise ImportError(f"fat5_lookup_params layout mismatch: library {lib.fat5_sizeof_lookup_params()} B, "
                           f"binding {ctypes.sizeof(LookupParams)} B")
+    lib.fat5_pack_plan.restype = ctypes.c_int
+    lib.fat5_pack_plan.argtypes = [ctypes.POINTER(PackParams), ctypes.c_void_p]
+    lib.fat5_sizeof_pack_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_pack_params() != ctypes.sizeof(PackParams):
+        raise ImportError(f"fat5_pack_params layout mismatch: library {lib.fat5_sizeof_pack_params()} B, "
+                          f"binding {ctypes.sizeof(PackParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

@@ -128,7 +128,13 @@ class FlashT5Attention(nn.Module):
         self.Wv = nn.Linear(self.d_model, self.inner_dim, bias=False)
         self.o = nn.Linear(self.inner_dim, self.d_model, bias=False)
 
-    def forward(self, hidden_states, mask=None, key_value_states=None, position_bias=None):
+    def forward(self, hidden_states, mask=None, key_value_states=None, position_bias=None, cu_seqlens=None, max_seqlen=None,
+                kv_cu_seqlens=None, kv_max_seqlen=None):
+        """cu_seqlens / max_seqlen (and, for cross-attention, kv_cu_seqlens / kv_max_seqlen of the key / value side): packed
+        hidden states (1, total, d_model), every sequence attending inside itself with positions of its own (packed_supported)"""
+        if cu_seqlens is not None:
+            return self._forward_packed(hidden_states, key_value_states, position_bias, cu_seqlens, max_seqlen, kv_cu_seqlens,
+                                        kv_max_seqlen)
         B, M = hidden_states.shape[:2]
         src = hidden_states if key_value_states is None else key_value_states
         N = src.shape[1]
@@ -142,7 +148,8 @@ class FlashT5Attention(nn.Module):
         out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias)
         return self.o(out), position_bias
 
-    def forward_fused(self, hidden_states, norm_weight, eps, mask=None, key_value_states=None, position_bias=None):
+    def forward_fused(self, hidden_states, norm_weight, eps, mask=None, key_value_states=None, position_bias=None, cu_seqlens=None,
+                      max_seqlen=None, kv_cu_seqlens=None, kv_max_seqlen=None):
         """One whole T5 attention sub-layer, `h + o(attention(layer_norm(h)))` (reference modeling_flash_t5.py:304-318 / :321-349),
         with the pre-norm inside the projection GEMM and the residual add as the output projection's epilogue
         (`fused_linear.rmsnorm_linear` / `linear_residual`): `hidden_states` is the UN-normalised residual stream,
@@ -150,6 +157,20 @@ class FlashT5Attention(nn.Module):
         from .fused_linear import rmsnorm_linear, linear_residual
         B, M = hidden_states.shape[:2]
         H, Dh = self.n_heads, self.key_value_proj_dim
+        if cu_seqlens is not None:    # packed rows: the same GEMMs, then (total, H, D) views of their outputs
+            self.packed_supported()
+            self._packed_args(hidden_states, key_value_states, cu_seqlens, max_seqlen, kv_cu_seqlens, kv_max_seqlen)
+            if key_value_states is None:
+                qkv, res = rmsnorm_linear(hidden_states, norm_weight, (self.Wq.weight, self.Wk.weight, self.Wv.weight), eps, return_residual=True)
+                q, k, v = (t[0].transpose(0, 1) for t in unpack_heads(qkv, 3, H))
+            else:
+                q, res = rmsnorm_linear(hidden_states, norm_weight, self.Wq.weight, eps, return_residual=True)
+                kv = torch.nn.functional.linear(key_value_states, torch.cat((self.Wk.weight, self.Wv.weight), 0))
+                q = q.view(M, H, Dh)
+                k, v = (t[0].transpose(0, 1) for t in unpack_heads(kv, 2, H))
+            out, position_bias = self._attend_packed(q, k, v, key_value_states is None, position_bias, cu_seqlens, max_seqlen,
+                                                     kv_cu_seqlens, kv_max_seqlen)
+            return linear_residual(out, self.o.weight, res), position_bias
         if key_value_states is None:  # self-attention: ONE GEMM for q, k, v
             qkv, res = rmsnorm_linear(hidden_states, norm_weight, (self.Wq.weight, self.Wk.weight, self.Wv.weight), eps, return_residual=True)
             if self.rotary and position_bias is None:  # the packed buffer in, a packed buffer out (and its gradient packed again): one launch each way
@@ -164,6 +185,71 @@ class FlashT5Attention(nn.Module):
             k, v = unpack_heads(kv, 2, H)
         out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias)
         return linear_residual(out, self.o.weight, res), position_bias
+
+    def packed_supported(self):
+        """raise NotImplementedError when this layer cannot run packed (cu_seqlens) rows: the packed kernels carry the T5 generator
+        or no bias at all, never a dense (B, H, M, N) one"""
+        if self.position_encoding_type == "FIRE":
+            raise NotImplementedError("padding masks / segment ids with FIRE: its bias is dense, and the packed (cu_seqlens) kernels "
+                                      "take no dense bias")
+        if self._randomized:
+            raise NotImplementedError("padding masks / segment ids with use_randomized_position_encoding: randomized positions are "
+                                      "not a function of n - m, which is what the packed kernels' in-kernel bias is built from")
+        if self.position_encoding_type == "t5" and self.attention_type != "fat5_rpe":
+            raise NotImplementedError("padding masks / segment ids with the dense T5 bias (attention_type='triton'): the packed "
+                                      "(cu_seqlens) kernels take no dense bias; use attention_type='fat5_rpe'")
+        if self.position_encoding_type not in ("t5", "RoPE"):
+            raise NotImplementedError(f"padding masks / segment ids with position_encoding_type {self.position_encoding_type!r}")
+
+    def _packed_args(self, hidden_states, key_value_states, cu_seqlens, max_seqlen, kv_cu_seqlens, kv_max_seqlen):
+        if max_seqlen is None:
+            raise ValueError("cu_seqlens needs max_seqlen")
+        if hidden_states.dim() != 3 or hidden_states.shape[0] != 1:
+            raise ValueError(f"packed hidden states are (1, total, d_model), got {tuple(hidden_states.shape)}")
+        if key_value_states is not None:
+            if kv_cu_seqlens is None or kv_max_seqlen is None:
+                raise ValueError("packed cross-attention needs kv_cu_seqlens and kv_max_seqlen of the key / value side")
+            if key_value_states.dim() != 3 or key_value_states.shape[0] != 1:
+                raise ValueError(f"packed key / value states are (1, total_k, d_model), got {tuple(key_value_states.shape)}")
+
+    def _forward_packed(self, hidden_states, key_value_states, position_bias, cu_seqlens, max_seqlen, kv_cu_seqlens, kv_max_seqlen):
+        self.packed_supported()
+        self._packed_args(hidden_states, key_value_states, cu_seqlens, max_seqlen, kv_cu_seqlens, kv_max_seqlen)
+        H, Dh = self.n_heads, self.key_value_proj_dim
+        src = hidden_states if key_value_states is None else key_value_states
+        q = self.Wq(hidden_states).view(hidden_states.shape[1], H, Dh)
+        k = self.Wk(src).view(src.shape[1], H, Dh)
+        v = self.Wv(src).view(src.shape[1], H, Dh)
+        out, position_bias = self._attend_packed(q, k, v, key_value_states is None, position_bias, cu_seqlens, max_seqlen,
+                                                 kv_cu_seqlens, kv_max_seqlen)
+        return self.o(out), position_bias
+
+    def _attend_packed(self, q, k, v, is_self, position_bias, cu, mx, kv_cu, kv_mx):
+        """packed attention of projected (total, H, D) views -> (1, total_q, inner_dim), plus the position bias to hand on: the T5
+        generator of block 0's forward_1d() in-kernel, or rotated q / k / v and no bias, positions local to each sequence"""
+        from .flash_attention_v2_bias import flash_attn_varlen_func
+        if is_self:
+            kv_cu, kv_mx = cu, mx
+        rpe1d, radius = None, 0
+        if self.rotary and position_bias is None:
+            cos, sin, cos_k, sin_k = self._rotary_tables(q)
+            il = self.pe_encoding.interleaved
+            if is_self:
+                q, k, v = apply_rotary_emb_qkv(q, k, v, cos, sin, cos_k, sin_k, il, cu_seqlens=cu, max_seqlen=mx)
+            else:  # (the two sides count their own positions: q under the decoder's cu_seqlens, k and v under the encoder's)
+                ck, sk = (cos, sin) if cos_k is None else (cos_k, sin_k)
+                q = apply_rotary_emb(q, cos, sin, il, cu_seqlens=cu, max_seqlen=mx)
+                k = apply_rotary_emb(k, ck, sk, il, cu_seqlens=kv_cu, max_seqlen=kv_mx)
+                v = apply_rotary_emb(v, ck, sk, il, cu_seqlens=kv_cu, max_seqlen=kv_mx)
+        elif is_self:
+            if position_bias is None and self.pe_encoding is not None:
+                position_bias = self.pe_encoding.forward_1d()
+            if position_bias is None:
+                raise ValueError("fat5_rpe self-attention without a bias producer needs position_bias=(rpe1d, radius) from the "
+                                 "block that owns the RelativePositionalEncoding")
+            rpe1d, radius = position_bias
+        out = flash_attn_varlen_func(q, k, v, cu, kv_cu, mx, kv_mx, self.is_causal and is_self, self.softmax_scale, rpe1d, radius)
+        return out.reshape(1, q.shape[0], self.inner_dim), position_bias
 
     def decode_supported(self):
         """raise NotImplementedError when this layer cannot run a cached decoding step"""

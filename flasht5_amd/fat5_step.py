@@ -97,6 +97,18 @@ class FAT5GatedAct(nn.Module):  # reference FlashT5DenseGatedAct / FlashT5DenseA
         return self.act(self.wi(x))
 
 
+def _self_kw(packing):
+    """the packed-row keyword arguments of a self-attention layer (none without a packing.Packed: today's call)"""
+    return {} if packing is None else dict(cu_seqlens=packing.cu_seqlens, max_seqlen=packing.max_seqlen)
+
+
+def _cross_kw(packing):
+    if packing is None:
+        return {}
+    return dict(cu_seqlens=packing.cu_seqlens, max_seqlen=packing.max_seqlen, kv_cu_seqlens=packing.kv_cu_seqlens,
+                kv_max_seqlen=packing.kv_max_seqlen)
+
+
 def _pre_norm(ln, h, pending):
     """pre-norm of a sub-layer with the previous sub-layer's residual add folded in: (h + pending, layer_norm(h + pending))"""
     if pending is None:
@@ -144,16 +156,17 @@ class FAT5LayerSelfAttention(nn.Module):  # :297-318
         self.self_attention = FlashT5Attention(c, has_positional_encoding=has_positional_encoding, is_causal=c.is_decoder)
         self.layer_norm = FlashT5LayerNorm(c.d_model, eps=c.layer_norm_epsilon)
 
-    def forward(self, h, position_bias=None):
-        a, position_bias = self.self_attention(self.layer_norm(h), position_bias=position_bias)
+    def forward(self, h, position_bias=None, packing=None):
+        a, position_bias = self.self_attention(self.layer_norm(h), position_bias=position_bias, **_self_kw(packing))
         return h + a, position_bias
 
-    def forward_fused(self, h, position_bias=None):
-        return self.self_attention.forward_fused(h, self.layer_norm.weight, self.layer_norm.variance_epsilon, position_bias=position_bias)
+    def forward_fused(self, h, position_bias=None, packing=None):
+        return self.self_attention.forward_fused(h, self.layer_norm.weight, self.layer_norm.variance_epsilon, position_bias=position_bias,
+                                                 **_self_kw(packing))
 
-    def forward_deferred(self, h, pending, position_bias=None):
+    def forward_deferred(self, h, pending, position_bias=None, packing=None):
         h, n = _pre_norm(self.layer_norm, h, pending)
-        a, position_bias = self.self_attention(n, position_bias=position_bias)
+        a, position_bias = self.self_attention(n, position_bias=position_bias, **_self_kw(packing))
         return h, a, position_bias
 
 
@@ -163,16 +176,17 @@ class FAT5LayerCrossAttention(nn.Module):  # :321-349
         self.cross_attention = FlashT5Attention(c, has_positional_encoding=False)
         self.layer_norm = FlashT5LayerNorm(c.d_model, eps=c.layer_norm_epsilon)
 
-    def forward(self, h, key_value_states):
-        a, _ = self.cross_attention(self.layer_norm(h), key_value_states=key_value_states)
+    def forward(self, h, key_value_states, packing=None):
+        a, _ = self.cross_attention(self.layer_norm(h), key_value_states=key_value_states, **_cross_kw(packing))
         return h + a
 
-    def forward_fused(self, h, key_value_states):
-        return self.cross_attention.forward_fused(h, self.layer_norm.weight, self.layer_norm.variance_epsilon, key_value_states=key_value_states)[0]
+    def forward_fused(self, h, key_value_states, packing=None):
+        return self.cross_attention.forward_fused(h, self.layer_norm.weight, self.layer_norm.variance_epsilon, key_value_states=key_value_states,
+                                                  **_cross_kw(packing))[0]
 
-    def forward_deferred(self, h, pending, key_value_states):
+    def forward_deferred(self, h, pending, key_value_states, packing=None):
         h, n = _pre_norm(self.layer_norm, h, pending)
-        a, _ = self.cross_attention(n, key_value_states=key_value_states)
+        a, _ = self.cross_attention(n, key_value_states=key_value_states, **_cross_kw(packing))
         return h, a
 
 
@@ -185,22 +199,22 @@ class FAT5Block(nn.Module):  # :352-392
             self.cross_attention_layer = FAT5LayerCrossAttention(c)
         self.ff_layer = FAT5LayerFF(c)
 
-    def forward(self, h, position_bias=None, encoder_hidden_states=None):
-        h, position_bias = self.self_attention_layer(h, position_bias)
+    def forward(self, h, position_bias=None, encoder_hidden_states=None, packing=None):
+        h, position_bias = self.self_attention_layer(h, position_bias, packing)
         if self.is_decoder and encoder_hidden_states is not None:
-            h = self.cross_attention_layer(h, encoder_hidden_states)
+            h = self.cross_attention_layer(h, encoder_hidden_states, packing)
         return self.ff_layer(h), position_bias
 
-    def forward_fused(self, h, position_bias=None, encoder_hidden_states=None):
-        h, position_bias = self.self_attention_layer.forward_fused(h, position_bias)
+    def forward_fused(self, h, position_bias=None, encoder_hidden_states=None, packing=None):
+        h, position_bias = self.self_attention_layer.forward_fused(h, position_bias, packing)
         if self.is_decoder and encoder_hidden_states is not None:
-            h = self.cross_attention_layer.forward_fused(h, encoder_hidden_states)
+            h = self.cross_attention_layer.forward_fused(h, encoder_hidden_states, packing)
         return self.ff_layer.forward_fused(h), position_bias
 
-    def forward_deferred(self, h, pending, position_bias=None, encoder_hidden_states=None):
-        h, pending, position_bias = self.self_attention_layer.forward_deferred(h, pending, position_bias)
+    def forward_deferred(self, h, pending, position_bias=None, encoder_hidden_states=None, packing=None):
+        h, pending, position_bias = self.self_attention_layer.forward_deferred(h, pending, position_bias, packing)
         if self.is_decoder and encoder_hidden_states is not None:
-            h, pending = self.cross_attention_layer.forward_deferred(h, pending, encoder_hidden_states)
+            h, pending = self.cross_attention_layer.forward_deferred(h, pending, encoder_hidden_states, packing)
         h, pending = self.ff_layer.forward_deferred(h, pending)
         return h, pending, position_bias
 
@@ -214,22 +228,24 @@ class FAT5Stack(nn.Module):  # :394-464
         self.fuse_add_norm = c.fuse_add_norm
         self.fuse_norm_linear = c.fuse_norm_linear
 
-    def forward(self, input_ids, encoder_hidden_states=None):
+    def forward(self, input_ids, encoder_hidden_states=None, packing=None):
+        """packing (packing.Packed): input_ids are the (1, total) valid tokens of a padded or packed batch, every attention layer
+        runs over cu_seqlens, and the output stays (1, total, d_model)"""
         h = self.embed_tokens(input_ids)
         if torch.is_autocast_enabled() and h.is_cuda:  # :424-425
             h = h.to(torch.get_autocast_gpu_dtype())
         position_bias = None  # produced by block 0, shared by the others (:452-455)
         if self.fuse_norm_linear and h.dtype in (torch.float16, torch.bfloat16):
             for blk in self.block:
-                h, position_bias = blk.forward_fused(h, position_bias, encoder_hidden_states)
+                h, position_bias = blk.forward_fused(h, position_bias, encoder_hidden_states, packing)
             return self.final_layer_norm(h)
         if self.fuse_add_norm:
             pending = None  # the last sub-layer's output: its residual add happens inside the next pre-norm (SURVEY 8(f) n3)
             for blk in self.block:
-                h, pending, position_bias = blk.forward_deferred(h, pending, position_bias, encoder_hidden_states)
+                h, pending, position_bias = blk.forward_deferred(h, pending, position_bias, encoder_hidden_states, packing)
             return _pre_norm(self.final_layer_norm, h, pending)[1]
         for blk in self.block:
-            h, position_bias = blk(h, position_bias, encoder_hidden_states)
+            h, position_bias = blk(h, position_bias, encoder_hidden_states, packing)
         return self.final_layer_norm(h)
 
 
@@ -288,15 +304,94 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         return [self.encoder.block[0].self_attention_layer.self_attention.pe_encoding.relative_attention_bias.weight,
                 self.decoder.block[0].self_attention_layer.self_attention.pe_encoding.relative_attention_bias.weight]
 
-    def forward(self, input_ids, labels):
+    def forward(self, input_ids, labels, attention_mask=None, decoder_attention_mask=None, segment_ids=None, decoder_segment_ids=None):
+        """the training loss.  attention_mask / decoder_attention_mask: (B, L) bool or integer, non-zero = valid, right-padded;
+        segment_ids / decoder_segment_ids: (B, L) integer, several examples per row (0 = padding, then runs of 1, 2, ...; a row
+        holds as many decoder as encoder segments).  With any of them the model runs over the valid tokens only:
+        attention stays inside each example with positions of its own, and the mean runs over the non-ignored labels of valid
+        positions.  Without a decoder-side argument, row b's decoder length is max(1, 1 + the last index with labels != -100)."""
+        if attention_mask is not None or decoder_attention_mask is not None or segment_ids is not None or decoder_segment_ids is not None:
+            packed = self._pack(input_ids, labels, attention_mask, decoder_attention_mask, segment_ids, decoder_segment_ids)
+            if packed is not None:   # (None: nothing is padded and no row holds two examples -- the code below, bit for bit)
+                return self._forward_packed(*packed)
         enc = self.encoder(input_ids)
         dec = self.decoder(self._shift_right(labels), encoder_hidden_states=enc)
+        return self._loss(dec, labels)
+
+    def _loss(self, dec, labels):
         if self.config.fuse_lm_head_ce:
             from .lm_head_cross_entropy import lm_head_cross_entropy
             c = self.config
             return lm_head_cross_entropy(dec, self.lm_head.weight, labels, label_smoothing=c.label_smoothing,
                                          lse_square_scale=c.z_loss, reduction="mean")[0]
         return self.loss_fct(self.lm_head(dec), labels)
+
+    def packed_supported(self):
+        """raise NotImplementedError when this model cannot train on padded / packed batches (FlashT5Attention.packed_supported)"""
+        for stack in (self.encoder, self.decoder):
+            stack.block[0].self_attention_layer.self_attention.packed_supported()
+
+    def _pack(self, input_ids, labels, attention_mask, decoder_attention_mask, segment_ids, decoder_segment_ids):
+        """check the padding / segment arguments on the host, plan both sides on the device (packing.plan_pair: ONE host read) ->
+        (encoder PackPlan, decoder PackPlan, input_ids, labels), or None when the batch is neither padded nor packed"""
+        from .packing import plan_pair
+        for side, mask, seg in (("encoder", attention_mask, segment_ids), ("decoder", decoder_attention_mask, decoder_segment_ids)):
+            if mask is not None and seg is not None:
+                raise ValueError(f"forward: a padding mask and segment ids for the {side} side: segment ids already say what is "
+                                 "padding (0), pass one of them")
+        if segment_ids is not None and decoder_segment_ids is None:
+            raise ValueError("forward: segment_ids needs decoder_segment_ids (example i of a row's input belongs to example i of its "
+                             "labels, which the labels alone do not delimit)")
+        for name, t, like in (("attention_mask", attention_mask, input_ids), ("segment_ids", segment_ids, input_ids),
+                              ("decoder_attention_mask", decoder_attention_mask, labels),
+                              ("decoder_segment_ids", decoder_segment_ids, labels)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dim() != 2 or tuple(t.shape) != tuple(like.shape):
+                raise ValueError(f"forward: {name} must be a (B, L) = {tuple(like.shape)} tensor like the ids it describes, got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            if t.dtype.is_floating_point or t.dtype.is_complex or (name.endswith("segment_ids") and t.dtype == torch.bool):
+                raise ValueError(f"forward: {name} must be {'an integer' if name.endswith('segment_ids') else 'a bool or integer'} "
+                                 f"tensor, got {t.dtype}")
+        if input_ids.dim() != 2 or labels.dim() != 2 or input_ids.shape[0] != labels.shape[0]:
+            raise ValueError(f"forward: input_ids (B, L_enc) and labels (B, L_dec), got {tuple(input_ids.shape)} / {tuple(labels.shape)}")
+        self.packed_supported()
+        dev = input_ids.device
+        if segment_ids is not None:
+            enc_in = segment_ids.to(dev)
+        elif attention_mask is not None:
+            enc_in = attention_mask.to(dev) != 0
+        else:
+            enc_in = torch.ones(input_ids.shape, dtype=torch.bool, device=dev)
+        if decoder_segment_ids is not None:
+            dec_in = decoder_segment_ids.to(dev)
+        elif decoder_attention_mask is not None:
+            dec_in = decoder_attention_mask.to(dev) != 0
+        else:   # the labels delimit the row: everything up to the last label that is not ignored
+            cols = torch.arange(1, labels.shape[1] + 1, device=dev)
+            lens = ((labels != -100) * cols).amax(1, keepdim=True).clamp_(min=1)
+            dec_in = cols.unsqueeze(0) <= lens
+        ep, dp = plan_pair(enc_in, dec_in, names=("attention_mask / segment_ids", "decoder_attention_mask / decoder_segment_ids"))
+        B = input_ids.shape[0]
+        if ep.nseq == B and dp.nseq == B and ep.total == input_ids.numel() and dp.total == labels.numel():
+            return None
+        return ep, dp, input_ids, labels
+
+    def _forward_packed(self, ep, dp, input_ids, labels):
+        """the loss over the valid tokens only: ids and labels gathered through the plans' indices, both stacks over cu_seqlens,
+        the encoder output left packed for the cross-attention, the loss on the packed rows"""
+        from .packing import Packed
+        c = self.config
+        ids = input_ids.reshape(-1).index_select(0, ep.index).unsqueeze(0)      # (1, total_enc)
+        lab = labels.reshape(-1).index_select(0, dp.index)                      # (total_dec,)
+        # _shift_right per segment: a segment's first position gets the start token, the others the label before them
+        shifted = torch.cat([lab.new_full((1,), c.decoder_start_token_id), lab[:-1]])
+        shifted.index_fill_(0, dp.cu_seqlens[:-1].long(), c.decoder_start_token_id)
+        shifted = shifted.masked_fill(shifted == -100, c.pad_token_id).unsqueeze(0)
+        enc = self.encoder(ids, packing=Packed(ep.cu_seqlens, ep.max_seqlen))
+        dec = self.decoder(shifted, encoder_hidden_states=enc,
+                           packing=Packed(dp.cu_seqlens, dp.max_seqlen, ep.cu_seqlens, ep.max_seqlen))
+        return self._loss(dec, lab.unsqueeze(0))
 
     def init_decode_state(self, input_ids, max_length=32, attention_mask=None, prompt_length=1, kv_cache_dtype=None):
         """encoder output, cross K / V and empty self-attention caches of capacity max_length + prompt_length (generation.DecodeState);
@@ -370,9 +465,14 @@ def allreduce_gradients(model: nn.Module, group=None, average=True):
     return flat
 
 
-def train_step(model, input_ids, labels, optimizer=None, group=None, max_grad_norm=1.0):
-    """forward + backward (+ gradient all-reduce, clip like the reference's `max_grad_norm: 1.0`, optimizer step)"""
-    loss = model(input_ids, labels)
+def train_step(model, input_ids, labels, optimizer=None, group=None, max_grad_norm=1.0, attention_mask=None,
+               decoder_attention_mask=None, segment_ids=None, decoder_segment_ids=None):
+    """forward + backward (+ gradient all-reduce, clip like the reference's `max_grad_norm: 1.0`, optimizer step); the padding masks
+    / segment ids of `FAT5ForConditionalGeneration.forward` are handed on (none given: the call of before, whatever `model` is)"""
+    pad = dict(attention_mask=attention_mask, decoder_attention_mask=decoder_attention_mask, segment_ids=segment_ids,
+               decoder_segment_ids=decoder_segment_ids)
+    pad = {k: v for k, v in pad.items() if v is not None}
+    loss = model(input_ids, labels, **pad)
     loss.backward()
     allreduce_gradients(model, group)
     if optimizer is not None:

@@ -911,6 +911,39 @@ size_t fat5_sizeof_lookup_params(void);
 int fat5_lookup_draft(const fat5_lookup_params* p, void* hip_stream);
 
 /*
+ * Pack planner (pack_kernels.h): padding masks or T5X-style segment ids to what the packed (cu_seqlens) kernels take.
+ * `seg` is a contiguous (B, L) int32 device matrix: 0 = padding; a valid row is a run of 1s, then a run of 2s, ... up to n_b >= 1,
+ * then zeros to the end (ids start at 1 and rise by exactly 1; a 0 / 1 mask is n_b = 1).  seg_cap (1 .. 256) is the most segments
+ * a row may hold.  Outputs, all caller-owned device buffers written with plain stores (no atomics: the same bytes on every run):
+ *   cu_seqlens (B * seg_cap + 1,) int32: the exclusive prefix sums of the segment lengths in (row, segment) order -- nseq + 1
+ *              live entries; every entry past them holds `total`;
+ *   index      (B * L,) int64: its first `total` entries are the flat positions b * L + j of the valid tokens, row-major;
+ *   seg_count  (B,) int32: n_b;
+ *   status     (4,) int32: total, nseq, max_seqlen, flags.  flags: bit 0 a row with a hole, left padding, an id that does not
+ *              rise by 0 or 1 or does not start at 1; bit 1 a row without a valid position; bit 2 a row with more than seg_cap
+ *              segments; bit 3 a negative id.
+ * With a flag set the other outputs are still in bounds: a row contributes its leading run of positive ids, cut into segments
+ * wherever the id changes, the segments past seg_cap merged into the last one; every index is < B * L and cu_seqlens does not fall.
+ * Two launches on `hip_stream`, no workspace, nothing read back by the host (graph-replayable).
+ * Rejected with FAT5_EINVAL before anything is launched: NULL params, B < 1, L < 1, B * L >= 2^31, seg_cap outside [1, 256],
+ * B * seg_cap >= 2^31 - 1, a NULL pointer, seg not 16-byte aligned, index not 8-byte aligned, the int32 outputs not 4-byte aligned.
+ */
+typedef struct fat5_pack_params {
+  int32_t B;
+  int32_t L;
+  int32_t seg_cap;
+  int32_t reserved;
+  const int32_t* seg;
+  int32_t* cu_seqlens;
+  int64_t* index;
+  int32_t* seg_count;
+  int32_t* status;
+} fat5_pack_params;
+/* sizeof(fat5_pack_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_pack_params(void);
+int fat5_pack_plan(const fat5_pack_params* p, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)
