@@ -11,7 +11,8 @@ also the mixed pairs 32row + 64key and 64row + 32key) and the one-launch form (f
 SELF form); qdiag=0 / 1; dtable=runs / scan.  Their derivation is the section "The 64-wide bodies" below.
 Not covered: the DENSE 64-wide bodies (dq=64row-batch4; the DENSE form of the 64-key body; the dense one-launch form; the dbias routes
 "dq-kernel" and "dq-kernel+partials"): `attn_bwd_bound` raises for them, the case list holds none, and they stay with the max-norm tests
-(tests/test_dense64_gpu.py).  Also left to the existing tests: the packed (cu_seqlens) layout, unit ranges, zero and negative sm_scale,
+(tests/test_dense64_gpu.py).  The packed (cu_seqlens) layout: tests/attn_packed_fp64.py, which calls this file per sequence and
+`drpe_bound` once per batch.  Left to the existing tests: unit ranges, zero and negative sm_scale,
 head dimensions and dtypes the dispatcher rejects, the forward, any timing.
 
 The restatement.  Per (b, h), in fp64, from the given o and lse:  p = exp(s - lse) on visible keys, exact 0 elsewhere (a dense bias
@@ -131,7 +132,8 @@ def _knobs(B, H, M, N, D, R, causal, scale, bias, rpe1d, bucket):
                 red_b=bias is not None and bias.shape[0] == 1 and B > 1, red_h=bias is not None and bias.shape[1] == 1 and H > 1,
                 wq=torch.ones(N, dtype=torch.float64), wr=torch.ones(M, dtype=torch.float64), delta_shift=0, delta_true=False,
                 own_softmax=False, dk_noscale=False, dq_scale2=False, db_drop=False, db_dup=False, db_above=False, db_row_shift=0,
-                g_shift=0, g_far_band=False, g_head_shift=0, bucket_shift=0, ragged=False, lse_scale2=False, g_w=None, g_far_add=None, g_sign=1)
+                g_shift=0, g_far_band=False, g_head_shift=0, bucket_shift=0, ragged=False, lse_scale2=False, g_w=None, g_far_add=None, g_sign=1,
+                delta_over=None)
 
 
 def _bias_all(c, bias, rpe1d, R, M, N):
@@ -182,6 +184,8 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
         delta = (od * dod).sum(-1)
     if c["delta_shift"]:
         delta = delta[..., (torch.arange(M) + c["delta_shift"]).clamp(max=M - 1)]
+    if c["delta_over"] is not None:                                     # ((B, H, M) fp64: the delta the defect reads in place of its own -- the packed mutants)
+        delta = c["delta_over"]
     dP = dod @ vt
     dS = p * (dP - delta[..., None])
     a = p * (dod.abs() @ vt.abs() + delta.abs()[..., None])
@@ -436,6 +440,38 @@ def far_rounded_mask(bodies, M, N, R, causal):
     return m
 
 
+def _consts(dtype, D, bodies):
+    """the constants both parts of the bound share: (u_T, c_A, e_dS, e_dS of the 64-row dQ body, kv64, q64, qdiag)"""
+    dqb, kvb, qdiag = bodies.get("dq"), bodies.get("dkdv", ""), bodies.get("qdiag", "0")
+    kv64, q64 = kvb == "64key" or kvb == "64key-half" or kvb.startswith("64key-mixed:"), dqb == "64row"
+    cA = LN2 * (2 * D + 9) * U32 * (1 + E_EXP) / (1 - 2.0 ** -7)
+    return U_T[dtype], cA, E_EXP + (2 * D + 1) * U32, E_EXP + (2 * D + 5) * U32, kv64, q64, qdiag
+
+
+def drpe_bound(ref, dtype, D, bodies):
+    """the drpe1d / drpe_table part of `attn_bwd_bound`: {output: bound} from the entries' T_, TA_, TD_, TF_, n_, nF_ fields alone.  These are
+    linear in the terms an entry reduces, so a packed batch sums them over its sequences and calls this once (tests/attn_packed_fp64.py)."""
+    uT, cA, e_ds, e_ds_q64, kv64, q64, qdiag = _consts(dtype, D, bodies)
+    fp16 = dtype == torch.float16
+    out = {}
+    wide_sums = q64 if qdiag == "1" else kv64    # the body that forms the diagonal sums: the dQ one (QDG) or the dK/dV one
+    for x in ("drpe1d", "drpe_table"):
+        if x in ref:
+            T = ref["T_" + x]
+            err = (e_ds_q64 if (wide_sums and qdiag == "1") else e_ds) * T + cA * ref["TA_" + x] + D * U32 * ref["TD_" + x]
+            if wide_sums:
+                # the far bins of the pipelined trips are summed from the dS ROUNDED to the dtype (ones . dS MFMAs: k:484-487, k:848-858,
+                # k:1662-1674): u_T of every such term, at most the whole of the two far bins (TF); the band and the general steps add the
+                # fp32 dS (k:614, k:682-683 -- Dv, not the packed words --, k:1511, k:1564-1565)
+                err = err + uT * (ref["TF_" + x] + err)
+                if fp16:
+                    err = err + 2.0 ** -25 * ref["nF_" + x] + (2.0 ** -25 * ref["n_" + x] if qdiag == "1" else 0.0)
+            g = 2 * ref["n_" + x] + 8
+            err = err + (g * U32 / (1 - g * U32)) * (T + err)
+            out[x] = torch.where(T == 0, torch.zeros_like(err), err)
+    return out
+
+
 def attn_bwd_bound(ref, dtype, D, bodies, N, M):
     """{output: bound tensor} for an `attn_bwd_ref` result computed by the bodies `bodies` names (the dq=, dkdv=, fused=, dbias=, qdiag=,
     dtable= fields of fat5_attn_describe, as a dict) at head dimension D"""
@@ -480,21 +516,7 @@ def attn_bwd_bound(ref, dtype, D, bodies, N, M):
             ns = ref["nsum"]
             err = (1 + uT) * err + uT * T + _gamma(ns) * (1 + uT) * T + (ns * 2.0 ** -25 if fp16 else 0.0)
         out["dbias"] = close("dbias", err)
-    wide_sums = q64 if qdiag == "1" else kv64    # the body that forms the diagonal sums: the dQ one (QDG) or the dK/dV one
-    for x in ("drpe1d", "drpe_table"):
-        if x in ref:
-            T = ref["T_" + x]
-            err = (e_ds_q64 if (wide_sums and qdiag == "1") else e_ds) * T + cA * ref["TA_" + x] + D * U32 * ref["TD_" + x]
-            if wide_sums:
-                # the far bins of the pipelined trips are summed from the dS ROUNDED to the dtype (ones . dS MFMAs: k:484-487, k:848-858,
-                # k:1662-1674): u_T of every such term, at most the whole of the two far bins (TF); the band and the general steps add the
-                # fp32 dS (k:614, k:682-683 -- Dv, not the packed words --, k:1511, k:1564-1565)
-                err = err + uT * (ref["TF_" + x] + err)
-                if fp16:
-                    err = err + 2.0 ** -25 * ref["nF_" + x] + (2.0 ** -25 * ref["n_" + x] if qdiag == "1" else 0.0)
-            g = 2 * ref["n_" + x] + 8
-            err = err + (g * U32 / (1 - g * U32)) * (T + err)
-            out[x] = torch.where(T == 0, torch.zeros_like(err), err)
+    out.update(drpe_bound(ref, dtype, D, bodies))
     return out
 
 

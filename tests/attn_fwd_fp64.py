@@ -1,7 +1,8 @@
 """fp64 restatement of `fat5_attn_fwd` in the dense (B, H, S, D) layout (the contract above `fat5_attn_params` in include/fat5.h), a
 per-element error bound derived from the operation counts of the forward bodies, a float32 emulation of their arithmetic, and mutants:
 restatements with one realistic defect each, which the bound must tell from the truth.  CPU only; imports no GPU code.  Used by
-tests/test_attn_fwd_fp64_cpu.py and tests/test_attn_fwd_fp64_gpu.py.  Gradients, the packed layout and unit ranges are not covered.
+tests/test_attn_fwd_fp64_cpu.py and tests/test_attn_fwd_fp64_gpu.py.  Gradients and unit ranges are not covered; the packed (cu_seqlens)
+layout is covered by tests/attn_packed_fp64.py, which calls this file per sequence.
 
 The bound.  u = 2^-24 (fp32 unit roundoff); an addition inside an MFMA is charged 2 u = 2^-23 (its rounding mode is not documented: the
 charge covers truncation); u_T = 2^-8 (bf16) / 2^-11 (fp16), the unit roundoff of the input dtype; ulp_T(r) the spacing of the storage dtype at |r|.  All scores in log2 units,
