@@ -285,52 +285,14 @@ class FlashT5Attention(nn.Module):
 
         FP8 caches: `k_scale` / `v_scale` (B, L_cap, H) fp32, the scales of float8_e4m3fn caches (decode.py); None: 16-bit caches."""
         self.decode_supported()
-        from .decode import flash_attn_with_kvcache
+        from .decode import flash_attn_with_kvcache, flash_attn_with_kvcache_chunk
         B, M = hidden_states.shape[:2]
-        if M > 1:
-            return self._forward_decode_chunk(hidden_states, k_cache, v_cache, cache_seqlens, position_bias, position,
-                                              cache_batch_idx, cache_row_batch, cross_seqlens, chunk_seqlens, k_scale, v_scale)
-        if chunk_seqlens is not None:
+        if M > 1 and (cache_batch_idx is not None or cache_row_batch is not None):
+            raise ValueError("forward_decode: cache_batch_idx / cache_row_batch take one query row per step (beam search has no chunks)")
+        if M == 1 and chunk_seqlens is not None:
             raise ValueError("forward_decode: chunk_seqlens needs a chunk of M > 1 rows")
         if cross_seqlens is not None and cache_seqlens is not None:
             raise ValueError("forward_decode: cross_seqlens is for cross-attention (cache_seqlens None)")
-        H, Dh = self.n_heads, self.key_value_proj_dim
-        q = self.Wq(hidden_states).view(B, 1, H, Dh)
-        is_self = cache_seqlens is not None
-        k = v = None
-        if is_self:
-            k = self.Wk(hidden_states).view(B, 1, H, Dh)
-            v = self.Wv(hidden_states).view(B, 1, H, Dh)
-        rpe1d, radius = None, 0
-        if self.rotary:
-            if position is None:
-                raise ValueError("forward_decode with RoPE needs the step's position (a (1,) int64 device tensor)")
-            cos, sin, cos_k, sin_k = self.pe_encoding.tables(q.device, q.dtype)
-            rows = lambda t: None if t is None else t.index_select(0, position)  # noqa: E731  (device-side: capturable)
-            if is_self:
-                q, k, v = apply_rotary_emb_qkv(q, k, v, rows(cos), rows(sin), rows(cos_k), rows(sin_k), self.pe_encoding.interleaved)
-            else:
-                q = apply_rotary_emb(q, rows(cos), rows(sin), self.pe_encoding.interleaved)
-        elif is_self:
-            if position_bias is None:
-                raise ValueError("forward_decode: T5 self-attention needs position_bias=(rpe1d, radius) from block 0's forward_1d()")
-            rpe1d, radius = position_bias
-            if self.attention_type == "triton":  # (the dense path adds the bias after a cast to the activation dtype)
-                rpe1d = rpe1d.to(q.dtype).float()
-        fp8 = {} if k_scale is None else dict(k_scale=k_scale, v_scale=v_scale)
-        out = flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens if is_self else cross_seqlens, self.softmax_scale,
-                                      rpe1d, radius, cache_batch_idx=cache_batch_idx, cache_row_batch=cache_row_batch, **fp8)
-        return self.o(out.reshape(B, 1, self.inner_dim))
-
-    def _forward_decode_chunk(self, hidden_states, k_cache, v_cache, cache_seqlens, position_bias, position, cache_batch_idx,
-                              cache_row_batch, cross_seqlens=None, chunk_seqlens=None, k_scale=None, v_scale=None):
-        """forward_decode for M > 1 rows: the same projections, rotation and bias rule on the chunk kernel"""
-        from .decode import flash_attn_with_kvcache_chunk
-        if cache_batch_idx is not None or cache_row_batch is not None:
-            raise ValueError("forward_decode: cache_batch_idx / cache_row_batch take one query row per step (beam search has no chunks)")
-        if cross_seqlens is not None and cache_seqlens is not None:
-            raise ValueError("forward_decode: cross_seqlens is for cross-attention (cache_seqlens None)")
-        B, M = hidden_states.shape[:2]
         H, Dh = self.n_heads, self.key_value_proj_dim
         q = self.Wq(hidden_states).view(B, M, H, Dh)
         is_self = cache_seqlens is not None
@@ -343,7 +305,9 @@ class FlashT5Attention(nn.Module):
             if position is None:
                 raise ValueError("forward_decode with RoPE needs the step's position (a (1,) int64 device tensor)")
             cos, sin, cos_k, sin_k = self.pe_encoding.tables(q.device, q.dtype)
-            idx = (position + torch.arange(M, device=position.device)).clamp(0, cos.shape[0] - 1)  # (device-side: capturable)
+            idx = position  # (device-side: capturable; one row adds no launch, a chunk takes rows position .. position + M - 1)
+            if M > 1:
+                idx = (position + torch.arange(M, device=position.device)).clamp(0, cos.shape[0] - 1)
             rows = lambda t: None if t is None else t.index_select(0, idx)  # noqa: E731
             if is_self:
                 q, k, v = apply_rotary_emb_qkv(q, k, v, rows(cos), rows(sin), rows(cos_k), rows(sin_k), self.pe_encoding.interleaved)
@@ -356,15 +320,13 @@ class FlashT5Attention(nn.Module):
             if self.attention_type == "triton":  # (the dense path adds the bias after a cast to the activation dtype)
                 rpe1d = rpe1d.to(q.dtype).float()
         lens = cache_seqlens if is_self else cross_seqlens
-        if k_scale is not None:
-            out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, lens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
-                                                rpe_radius=radius, chunk_seqlens=chunk_seqlens, k_scale=k_scale, v_scale=v_scale)
-        elif chunk_seqlens is None:
-            out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, lens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
-                                                rpe_radius=radius)
+        fp8 = {} if k_scale is None else dict(k_scale=k_scale, v_scale=v_scale)
+        if M == 1:
+            out = flash_attn_with_kvcache(q, k_cache, v_cache, k, v, lens, self.softmax_scale, rpe1d, radius,
+                                          cache_batch_idx=cache_batch_idx, cache_row_batch=cache_row_batch, **fp8)
         else:
             out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, lens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
-                                                rpe_radius=radius, chunk_seqlens=chunk_seqlens)
+                                                rpe_radius=radius, chunk_seqlens=chunk_seqlens, **fp8)
         return self.o(out.reshape(B, M, self.inner_dim))
 
     def project_kv(self, key_value_states):

@@ -14,6 +14,11 @@ training forward (a bf16 model, or fp32 weights under bf16 autocast).  `cache_se
 every self-attention cache and incremented on the device at the end of each step; nothing a step reads comes from the host, so
 `graph=True` captures one step once and replays it per token.
 
+How the modes below share code: `_decoder_blocks` is the one pass through the decoder blocks (`decode_step` and `decode_chunk`
+add their own checks, length increment and head), `_step` is `decode_step` + `_pick` (processors, argmax or sampler, bookkeeping),
+`_run_steps` is the one eager / capture / replay loop -- greedy, sampled, beam and speculative decoding hand it their step and
+their stop predicate -- and `_prefill_prompt` is the one decoder-prompt prefill.
+
 Sampling (`do_sample=True`) replaces the argmax by `sample_logits` (one HIP launch: temperature, top-k, top-p and a Philox draw
 keyed by the call's seed with the token's position, cache_seqlens, as the counter), so it is captured and replayed the same way.
 
@@ -91,8 +96,9 @@ class DecodeState:
         return self.cache_seqlens[:1].long().clamp(0, self.capacity - 1)
 
 
-def _embed(model, ids):
-    h = model.shared(ids)
+def _embed(embedding, ids):
+    """`embedding` (the model's `shared`, a stack's `embed_tokens`) of the ids, in the dtype the stack's forward gives it"""
+    h = embedding(ids)
     if torch.is_autocast_enabled() and h.is_cuda:  # (FAT5Stack.forward's rule)
         h = h.to(torch.get_autocast_dtype("cuda"))
     return h
@@ -180,7 +186,7 @@ def _packed_encoder(stack, input_ids, pad):
     idx = torch.cat([torch.arange(n) + b * L for b, n in enumerate(lens)]).to(dev)
     cu = torch.tensor([0] + [sum(lens[:b + 1]) for b in range(B)], dtype=torch.int32).to(dev)
     mx, total = max(lens), sum(lens)
-    h = _embed_stack(stack, input_ids.reshape(-1).index_select(0, idx).unsqueeze(0))   # (1, total, d_model)
+    h = _embed(stack.embed_tokens, input_ids.reshape(-1).index_select(0, idx).unsqueeze(0))   # (1, total, d_model)
     bias = None
     for blk in stack.block:
         sa = blk.self_attention_layer
@@ -205,18 +211,11 @@ def _packed_encoder(stack, input_ids, pad):
     return enc.view(B, L, -1)
 
 
-def _embed_stack(stack, ids):
-    h = stack.embed_tokens(ids)
-    if torch.is_autocast_enabled() and h.is_cuda:  # (FAT5Stack.forward's rule)
-        h = h.to(torch.get_autocast_dtype("cuda"))
-    return h
-
-
 def _masked_bias_encoder(stack, input_ids, pad):
     """the encoder stack under the dense-bias type: block 0's (1, H, L, L) bias with the padded key columns at the dtype's minimum,
     as FlashT5Attention folds a mask in under use_masking, handed to every block; the padded rows of the result are zeroed"""
     B, L = input_ids.shape
-    h = _embed_stack(stack, input_ids)
+    h = _embed(stack.embed_tokens, input_ids)
     att = stack.block[0].self_attention_layer.self_attention
     bias = att.pe_encoding.compute_bias(L, L, device=h.device).to(h.dtype)
     bias = torch.where(pad.mask.view(B, 1, 1, L), bias, torch.finfo(h.dtype).min).contiguous()
@@ -299,6 +298,24 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     return state
 
 
+def _decoder_blocks(model, state, h, chunk_seqlens=None):
+    """hidden states (B, M, d_model) through every decoder block against the caches of `state` (self-attention, which appends the
+    M rows, cross-attention, feed-forward) -> (B, M, d_model) before the final norm; the lengths are the caller's to advance"""
+    pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
+    for i, blk in enumerate(model.decoder.block):
+        sa = blk.self_attention_layer
+        ssc, csc = state.scales(i)
+        h = h + sa.self_attention.forward_decode(sa.layer_norm(h), state.self_k[i], state.self_v[i], state.cache_seqlens,
+                                                 position_bias=state.position_bias, position=pos, cache_row_batch=state.row_batch,
+                                                 chunk_seqlens=chunk_seqlens, **ssc)
+        ca = blk.cross_attention_layer
+        h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos,
+                                                  cache_batch_idx=state.cross_batch_idx, cross_seqlens=state.cross_seqlens,
+                                                  chunk_seqlens=chunk_seqlens, **csc)
+        h = blk.ff_layer(h)
+    return h
+
+
 @torch.no_grad()
 def decode_step(model, state, token_ids):
     """one token per batch row (B,) or (B, 1) through the decoder against the caches -> logits (B, vocab) of the next position;
@@ -308,18 +325,7 @@ def decode_step(model, state, token_ids):
         raise ValueError(f"decode_step: the caches hold {state.capacity} positions and all of them are used (init_decode_state with a "
                          "larger max_length)")
     state.steps += 1
-    h = _embed(model, token_ids.reshape(B, 1))
-    pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
-    for i, blk in enumerate(model.decoder.block):
-        sa = blk.self_attention_layer
-        ssc, csc = state.scales(i)
-        h = h + sa.self_attention.forward_decode(sa.layer_norm(h), state.self_k[i], state.self_v[i], state.cache_seqlens,
-                                                 position_bias=state.position_bias, position=pos, cache_row_batch=state.row_batch,
-                                                 **ssc)
-        ca = blk.cross_attention_layer
-        h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos,
-                                                  cache_batch_idx=state.cross_batch_idx, cross_seqlens=state.cross_seqlens, **csc)
-        h = blk.ff_layer(h)
+    h = _decoder_blocks(model, state, _embed(model.shared, token_ids.reshape(B, 1)))
     h = model.decoder.final_layer_norm(h)
     state.cache_seqlens.add_(1)
     return model.lm_head(h)[:, 0]
@@ -354,17 +360,7 @@ def decode_chunk(model, state, token_ids, logits="all", chunk_seqlens=None):
                 chunk_seqlens.device != state.cache_seqlens.device):
             raise ValueError(f"decode_chunk: chunk_seqlens must be a ({B},) int32 tensor on {state.cache_seqlens.device}")
     state.steps += M
-    h = _embed(model, token_ids)
-    pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
-    for i, blk in enumerate(model.decoder.block):
-        sa = blk.self_attention_layer
-        ssc, csc = state.scales(i)
-        h = h + sa.self_attention.forward_decode(sa.layer_norm(h), state.self_k[i], state.self_v[i], state.cache_seqlens,
-                                                 position_bias=state.position_bias, position=pos, chunk_seqlens=chunk_seqlens, **ssc)
-        ca = blk.cross_attention_layer
-        h = h + ca.cross_attention.forward_decode(ca.layer_norm(h), state.cross_k[i], state.cross_v[i], None, position=pos,
-                                                  cross_seqlens=state.cross_seqlens, chunk_seqlens=chunk_seqlens, **csc)
-        h = blk.ff_layer(h)
+    h = _decoder_blocks(model, state, _embed(model.shared, token_ids), chunk_seqlens)
     state.cache_seqlens.add_(M if chunk_seqlens is None else chunk_seqlens.clamp(0, M))
     if logits == "none":
         return None
@@ -413,43 +409,33 @@ def _processed(logits, sequences, lengths, proc, log_softmax=False):
     return process_logits(logits, sequences, lengths, log_softmax=log_softmax, **proc)
 
 
-def _greedy_step(model, state, tok, labels, seen_eos, proc=None):
-    """decode_step + argmax: the token goes to `tok` and to column cache_seqlens of `labels` (a device-side index), and rows that
-    produced a 1 are marked in `seen_eos` -- nothing here reads the host, so the same code is captured as it is"""
-    _greedy_pick(decode_step(model, state, tok), state, tok, labels, seen_eos, proc)
+def _step(model, state, tok, labels, seen_eos, proc=None, sampling=None):
+    """decode_step + `_pick` -- nothing here reads the host, so the same code is captured as it is"""
+    _pick(decode_step(model, state, tok), state, tok, labels, seen_eos, proc, sampling)
 
 
-def _greedy_pick(logits, state, tok, labels, seen_eos, proc=None):
-    """_greedy_step after the decoder: `logits` (B, vocab) of the position cache_seqlens (already incremented) points at"""
+def _pick(logits, state, tok, labels, seen_eos, proc=None, sampling=None):
+    """a step after the decoder: `logits` (B, vocab) of the position cache_seqlens (already incremented) points at.  The
+    processors run first (before the warpers, as in HF), then the argmax, or with `sampling` = (temperature, top_k, top_p, seed)
+    `sample_logits` on the processed fp32 row; the Philox counter of row b is cache_seqlens[b] (the new token's position), read
+    on the device -- so a captured step draws a fresh uniform at every replay.  The token goes to `tok` and to column
+    cache_seqlens of `labels` (a device-side index), and rows that produced a 1 are marked in `seen_eos`"""
     logits = _processed(logits, labels, state.cache_seqlens, proc)
-    nxt = logits.argmax(-1)
+    if sampling is None:
+        nxt = logits.argmax(-1)
+    else:
+        from .sampling import sample_logits
+        temperature, top_k, top_p, seed = sampling
+        nxt = sample_logits(logits, temperature, top_k, top_p, seed=seed, offsets=state.cache_seqlens)
     tok.copy_(nxt)
     col = state.cache_seqlens.long().unsqueeze(1)  # (already incremented: the new token's column)
     labels.scatter_(1, col, nxt.unsqueeze(1))
     seen_eos.logical_or_(nxt == 1)
 
 
-def _sample_step(model, state, tok, labels, seen_eos, sampling, proc=None):
-    """decode_step + sample_logits, with _greedy_step's bookkeeping; the Philox counter of row b is cache_seqlens[b] after the
-    increment (the new token's position), read on the device -- so the captured step draws a fresh uniform at every replay.
-    The processors run before the warpers, as in HF: the sampler gets the processed fp32 row"""
-    _sample_pick(decode_step(model, state, tok), state, tok, labels, seen_eos, sampling, proc)
-
-
-def _sample_pick(logits, state, tok, labels, seen_eos, sampling, proc=None):
-    """_sample_step after the decoder (see _greedy_pick)"""
-    from .sampling import sample_logits
-    temperature, top_k, top_p, seed = sampling
-    logits = _processed(logits, labels, state.cache_seqlens, proc)
-    nxt = sample_logits(logits, temperature, top_k, top_p, seed=seed, offsets=state.cache_seqlens)
-    tok.copy_(nxt)
-    col = state.cache_seqlens.long().unsqueeze(1)
-    labels.scatter_(1, col, nxt.unsqueeze(1))
-    seen_eos.logical_or_(nxt == 1)
-
-
-def _spec_sampling(do_sample, temperature, top_k, top_p, seed):
-    """the `sampling` tuple of a speculative loop (None when greedy); a missing seed is drawn as in plain sampling"""
+def _sampling(do_sample, temperature, top_k, top_p, seed):
+    """the `sampling` tuple of a call whose warpers are checked already (None when greedy); a missing seed is one draw from
+    torch's default CPU generator"""
     if not do_sample:
         return None
     if seed is None:
@@ -495,21 +481,8 @@ def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, le
     bs.cache_row_batch = state.row_batch  # (one table: the decode kernel reads it, the beam step reorders it)
     tok = torch.zeros((B * k,), dtype=torch.long, device=dev)
     opts = (int(max_length), float(length_penalty), early_stopping)
-    g = None
-    steps = 0
-    try:
-        for _ in range(int(max_length)):
-            if g is not None:
-                g.replay()
-            else:
-                _beam_step(model, state, tok, bs, opts, proc)
-            steps += 1
-            if not bool(keep_going(bs.status, early_stopping)):
-                break
-            if graph and g is None and steps < max_length:
-                g = _capture_call(lambda: _beam_step(model, state, tok, bs, opts, proc))
-    finally:
-        del g
+    _run_steps(lambda: _beam_step(model, state, tok, bs, opts, proc), lambda: not bool(keep_going(bs.status, early_stopping)),
+               int(max_length), graph)
     seqs = bs.finished_seqs[:, :R].reshape(B * R, -1)
     T = int(bs.finished_lens[:, :R].max())
     out = seqs[:, :T + 1].clone()
@@ -642,47 +615,27 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     proc = _check_processors(model, max_length, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, P,
                              encoder_repetition_penalty, encoder_no_repeat_ngram_size, bad_words_ids, min_new_tokens,
                              forced_bos_token_id, forced_eos_token_id, input_ids.shape[-1])
-    if do_sample and (prompt_lookup_num_tokens is not None or assistant_model is not None):
+    if do_sample:  # (with beams do_sample is refused above; this is the one check of the warpers, whatever drafts)
         from .sampling import check_args as check_sampling_args
         check_sampling_args(temperature, top_k, top_p)
-    if prompt_lookup_num_tokens is not None:
-        from .speculative import check_lookup_generate_args, speculative_generate
-        check_lookup_generate_args(model, input_ids, max_length, prompt_lookup_num_tokens, max_matching_ngram_size, P, do_sample,
-                                   num_beams, proc is not None, assistant_model)
-        spec_sampling = _spec_sampling(do_sample, temperature, top_k, top_p, seed)
-        return speculative_generate(model, None, input_ids, attention_mask, max_length, graph, prompt_lookup_num_tokens, P,
-                                    decoder_input_ids, bool(return_stats), kv_cache_dtype, lookup_ngram=max_matching_ngram_size,
-                                    sampling=spec_sampling)
-    if assistant_model is not None:
-        from .speculative import check_generate_args, speculative_generate
-        check_generate_args(model, assistant_model, input_ids, max_length, num_assistant_tokens, P, do_sample, num_beams,
-                            proc is not None)
-        spec_sampling = _spec_sampling(do_sample, temperature, top_k, top_p, seed)
-        return speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, P,
-                                    decoder_input_ids, bool(return_stats), kv_cache_dtype, sampling=spec_sampling)
+    if prompt_lookup_num_tokens is not None or assistant_model is not None:
+        from .speculative import check_generate_args, check_lookup_generate_args, speculative_generate
+        lookup = prompt_lookup_num_tokens is not None
+        if lookup:
+            check_lookup_generate_args(model, input_ids, max_length, prompt_lookup_num_tokens, max_matching_ngram_size, P, do_sample,
+                                       num_beams, proc is not None, assistant_model)
+        else:
+            check_generate_args(model, assistant_model, input_ids, max_length, num_assistant_tokens, P, do_sample, num_beams,
+                                proc is not None)
+        return speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph,
+                                    prompt_lookup_num_tokens if lookup else num_assistant_tokens, P, decoder_input_ids,
+                                    bool(return_stats), kv_cache_dtype, lookup_ngram=max_matching_ngram_size if lookup else None,
+                                    sampling=_sampling(do_sample, temperature, top_k, top_p, seed))
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
                               early_stopping, return_scores, proc, kv_cache_dtype)
     proc = _proc_on_device(proc, input_ids.device, input_ids, attention_mask, dec_pad)
-    step = _greedy_step
-
-    def pick(logits, state, tok, labels, seen_eos):
-        _greedy_pick(logits, state, tok, labels, seen_eos, proc)
-    if proc is not None:
-        def step(model, state, tok, labels, seen_eos):
-            _greedy_step(model, state, tok, labels, seen_eos, proc)
-    if do_sample:
-        from .sampling import check_args
-        check_args(temperature, top_k, top_p)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64))
-        sampling = (float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF)
-
-        def step(model, state, tok, labels, seen_eos):
-            _sample_step(model, state, tok, labels, seen_eos, sampling, proc)
-
-        def pick(logits, state, tok, labels, seen_eos):  # noqa: F811
-            _sample_pick(logits, state, tok, labels, seen_eos, sampling, proc)
+    sampling = _sampling(do_sample, temperature, top_k, top_p, seed)
     B = input_ids.shape[0]
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask, prompt_length=P, kv_cache_dtype=kv_cache_dtype)
@@ -691,35 +644,20 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)
     steps = 0
     if decoder_input_ids is not None and dec_pad is None:
-        prompt = decoder_input_ids.to(dev)
-        labels[:, :P] = prompt
-        tok.copy_(prompt[:, P - 1])
-        if P > 1:
-            decode_chunk(model, state, prompt[:, :P - 1], logits="none")
+        _prefill_prompt(decoder_input_ids, P, labels, tok, (model, state))
     elif dec_pad is not None:
         # ragged prompts: every row's whole prompt in ONE chunk step, its first new token from the logits at its own last prompt
         # row; from here on row b sits at column P_b + steps, which the step reads from cache_seqlens on the device
         prompt = decoder_input_ids.to(dev).masked_fill(~dec_pad.mask, 0)
         labels[:, :P] = prompt
-    if dec_pad is not None and int(max_length) >= 1:
-        pick(decode_chunk(model, state, prompt, logits="last", chunk_seqlens=dec_pad.lengths_dev), state, tok, labels, seen_eos)
-        steps = 1
+        if int(max_length) >= 1:
+            _pick(decode_chunk(model, state, prompt, logits="last", chunk_seqlens=dec_pad.lengths_dev), state, tok, labels, seen_eos,
+                  proc, sampling)
+            steps = 1
     # (the prefill's token is a step like the others: the same stop check, one host read)
-    left = 0 if (steps and bool(seen_eos.all())) else int(max_length) - steps
-    g = None
-    try:
-        for _ in range(left):
-            if g is not None:
-                g.replay()
-            else:
-                step(model, state, tok, labels, seen_eos)
-            steps += 1
-            if bool(seen_eos.all()):
-                break
-            if graph and g is None and steps < max_length:  # (after the stop check: no capture when the first step ends it)
-                g = _capture(model, state, tok, labels, seen_eos, step)
-    finally:
-        del g
+    if not (steps and bool(seen_eos.all())):
+        steps = _run_steps(lambda: _step(model, state, tok, labels, seen_eos, proc, sampling), lambda: bool(seen_eos.all()),
+                           int(max_length), graph, steps)
     if dec_pad is not None and steps:  # (each row ends at its own last column: P_b + steps - 1)
         return finish_labels(labels[:, :steps + P], last=dec_pad.lengths_dev.long() + (steps - 1))
     return finish_labels(labels[:, :steps + P])
@@ -767,13 +705,42 @@ def _proc_on_device(proc, device, input_ids=None, enc_pad=None, dec_pad=None, nu
     return proc
 
 
-def _capture(model, state, tok, labels, seen_eos, step=_greedy_step):
-    """one decoding step (greedy by default) captured in a HIP graph (nothing runs during the capture: the state is unchanged)"""
-    return _capture_call(lambda: step(model, state, tok, labels, seen_eos))
+def _prefill_prompt(decoder_input_ids, P, labels, tok, *decoders):
+    """a (B, P) decoder prompt before the loop: the prompt goes into `labels`, its last token into `tok`, and its first P - 1
+    tokens fill the caches of every (model, state) pair in `decoders` in ONE chunk step each, without logits (a pair without a
+    state, the assistant's when the lookup drafts, is passed over)"""
+    prompt = decoder_input_ids.to(labels.device)
+    labels[:, :P] = prompt
+    tok.copy_(prompt[:, P - 1])
+    for model, state in decoders:
+        if P > 1 and state is not None:
+            decode_chunk(model, state, prompt[:, :P - 1], logits="none")
+
+
+def _run_steps(step, stopped, max_steps, graph, steps=0):
+    """The loop of every mode: `step()` (one token, one beam step, one speculative round; it reads nothing from the host) until
+    `stopped()` (the ONE host read per step) or `max_steps`, counting from `steps` -> the steps run.  The first step runs eagerly
+    (it also builds what a step allocates lazily); with `graph` the step is then captured once and replayed -- after the stop
+    check, so nothing is captured when the first step ends the call."""
+    g = None
+    try:
+        while steps < max_steps:
+            if g is not None:
+                g.replay()
+            else:
+                step()
+            steps += 1
+            if stopped():
+                break
+            if graph and g is None and steps < max_steps:
+                g = _capture_call(step)
+    finally:
+        del g
+    return steps
 
 
 def _capture_call(fn):
-    """fn() captured in a HIP graph"""
+    """fn() captured in a HIP graph (nothing runs during the capture: the state is unchanged)"""
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     ac = torch.is_autocast_enabled()

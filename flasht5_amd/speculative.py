@@ -88,6 +88,23 @@ def _check_devices(logits, draft, cache_seqlens, labels, tok, seen_eos, limit, d
             raise ValueError(f"speculative_accept: {name} must be on {logits.device}, got {t.device}")
 
 
+def _fill_spec_params(p, logits, draft, cache_seqlens, labels, tok, seen_eos, limit, limit_scalar, draft_seqlens, eos_token_id,
+                      n_accepted, n_new):
+    """the fields of `SpecParams` both verification ops fill alike (the sampled op's struct embeds one as `spec`); the workspace
+    is the op's own"""
+    B, M, V = logits.shape
+    p.B, p.M, p.V, p.dtype = B, M, V, _lib.dtype_code(logits.dtype)
+    p.logits, p.batch_stride, p.row_stride = logits.data_ptr(), logits.stride(0), logits.stride(1)
+    p.draft, p.draft_stride = draft.data_ptr(), draft.stride(0) if B > 1 else M - 1
+    p.cache_seqlens = cache_seqlens.data_ptr()
+    p.draft_seqlens = draft_seqlens.data_ptr() if draft_seqlens is not None else None
+    p.labels, p.labels_stride, p.ncols = labels.data_ptr(), labels.stride(0) if B > 1 else labels.shape[1], labels.shape[1]
+    p.eos_token_id = int(eos_token_id)
+    p.tok, p.seen_eos = tok.data_ptr(), seen_eos.data_ptr()
+    p.limit, p.limit_scalar = (limit.data_ptr(), 0) if limit is not None else (None, int(limit_scalar))
+    p.n_accepted, p.n_new = n_accepted.data_ptr(), n_new.data_ptr()
+
+
 @torch.library.custom_op("fat5::spec_accept", mutates_args=("cache_seqlens", "labels", "tok", "seen_eos", "draft_seqlens"),
                          device_types="cuda")
 def spec_accept_op(logits: torch.Tensor, draft: torch.Tensor, cache_seqlens: torch.Tensor, labels: torch.Tensor, tok: torch.Tensor,
@@ -108,16 +125,8 @@ def spec_accept_op(logits: torch.Tensor, draft: torch.Tensor, cache_seqlens: tor
     if B == 0:
         return n_accepted, n_new
     p = _lib.SpecParams()
-    p.B, p.M, p.V, p.dtype = B, M, V, _lib.dtype_code(logits.dtype)
-    p.logits, p.batch_stride, p.row_stride = logits.data_ptr(), logits.stride(0), logits.stride(1)
-    p.draft, p.draft_stride = draft.data_ptr(), draft.stride(0) if B > 1 else M - 1
-    p.cache_seqlens = cache_seqlens.data_ptr()
-    p.draft_seqlens = draft_seqlens.data_ptr() if draft_seqlens is not None else None
-    p.labels, p.labels_stride, p.ncols = labels.data_ptr(), labels.stride(0) if B > 1 else labels.shape[1], labels.shape[1]
-    p.eos_token_id = int(eos_token_id)
-    p.tok, p.seen_eos = tok.data_ptr(), seen_eos.data_ptr()
-    p.limit, p.limit_scalar = (limit.data_ptr(), 0) if limit is not None else (None, int(limit_scalar))
-    p.n_accepted, p.n_new = n_accepted.data_ptr(), n_new.data_ptr()
+    _fill_spec_params(p, logits, draft, cache_seqlens, labels, tok, seen_eos, limit, limit_scalar, draft_seqlens, eos_token_id,
+                      n_accepted, n_new)
     lib = _lib.load()
     need = lib.fat5_spec_accept_workspace_bytes(p)
     ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
@@ -192,16 +201,8 @@ def spec_accept_sampled_op(logits: torch.Tensor, draft: torch.Tensor, cache_seql
         return [n_accepted, n_new, sampled, aux]
     q = _lib.SpecSampleParams()
     p = q.spec
-    p.B, p.M, p.V, p.dtype = B, M, V, _lib.dtype_code(logits.dtype)
-    p.logits, p.batch_stride, p.row_stride = logits.data_ptr(), logits.stride(0), logits.stride(1)
-    p.draft, p.draft_stride = draft.data_ptr(), draft.stride(0) if B > 1 else M - 1
-    p.cache_seqlens = cache_seqlens.data_ptr()
-    p.draft_seqlens = draft_seqlens.data_ptr() if draft_seqlens is not None else None
-    p.labels, p.labels_stride, p.ncols = labels.data_ptr(), labels.stride(0) if B > 1 else labels.shape[1], labels.shape[1]
-    p.eos_token_id = int(eos_token_id)
-    p.tok, p.seen_eos = tok.data_ptr(), seen_eos.data_ptr()
-    p.limit, p.limit_scalar = (limit.data_ptr(), 0) if limit is not None else (None, int(limit_scalar))
-    p.n_accepted, p.n_new = n_accepted.data_ptr(), n_new.data_ptr()
+    _fill_spec_params(p, logits, draft, cache_seqlens, labels, tok, seen_eos, limit, limit_scalar, draft_seqlens, eos_token_id,
+                      n_accepted, n_new)
     if draft_logits is not None:
         q.draft_logits, q.draft_batch_stride, q.draft_row_stride = draft_logits.data_ptr(), draft_logits.stride(0), draft_logits.stride(1)
         if M - 1 == 1:   # (one row per batch element: its stride is never used)
@@ -322,37 +323,36 @@ def draft_tokens(assistant, draft_state, tok, draft, *, sampling=None, draft_log
 def check_generate_args(model, assistant_model, input_ids, max_length, num_assistant_tokens, prompt_length, do_sample, num_beams,
                         processors_active):
     """`generate(assistant_model=...)`'s host-side rejections, before either encoder runs"""
-    from .generation import _check_supported
     what = "generate: assistant_model (speculative decoding)"
+    _check_single_sequence(what, num_beams, processors_active)
+    check_args(num_assistant_tokens)
+    _check_models(what, "must be", (("the model", model), ("the assistant", assistant_model)), input_ids, max_length,
+                  num_assistant_tokens, "num_assistant_tokens", prompt_length, do_sample)
+
+
+def _check_single_sequence(what, num_beams, processors_active):
+    """what no drafter works with: beams, and logits processors"""
     if num_beams > 1:
         raise ValueError(f"{what} with num_beams > 1 is not supported: a beam has no single token for a draft to be checked against")
     if processors_active:
         raise ValueError(f"{what} with logits processors (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens) "
                          "is not supported: the chunk's rows would each need the sequence up to their own position")
-    check_args(num_assistant_tokens)
-    for m in (model, assistant_model):
+
+
+def _check_models(what, must_be, models, input_ids, max_length, gamma, gamma_name, prompt_length, do_sample):
+    """the rejections of a speculative loop's `models` (("the model", model), then the assistant when it drafts), whatever drafts:
+    the model type, one vocabulary, what the decode path refuses, the two RoPE limits (one rotary position per batch, the tables'
+    rows) and last -- the sampler, the drafter's draws and the verification kernels have no CPU path -- inputs of a sampled call
+    that are not on the GPU, refused here, before an encoder runs, not by the first launch"""
+    from .generation import _check_supported
+    for _, m in models:
         if not all(hasattr(m, a) for a in ("encoder", "decoder", "shared", "lm_head")):
-            raise ValueError(f"{what} must be a FAT5ForConditionalGeneration, got {type(m).__name__}")
-    V, Va = model.lm_head.weight.shape[0], assistant_model.lm_head.weight.shape[0]
+            raise ValueError(f"{what} {must_be} a FAT5ForConditionalGeneration, got {type(m).__name__}")
+    V, Va = (m.lm_head.weight.shape[0] for _, m in (models[0], models[-1]))
     if V != Va:
         raise ValueError(f"{what}: vocabulary mismatch, the model has {V} ids and the assistant {Va}")
-    _check_supported(model)
-    _check_supported(assistant_model)
-    _check_rotary(what, (("the model", model), ("the assistant", assistant_model)), input_ids, max_length, num_assistant_tokens,
-                  prompt_length)
-    _check_sampled_device(what, do_sample, input_ids)
-
-
-def _check_sampled_device(what, do_sample, input_ids):
-    """the last host-side check of a sampled speculative call: the sampler, the drafter's draws and the verification kernels
-    have no CPU path, so inputs that are not on the GPU are refused here, before an encoder runs, not by the first launch"""
-    if do_sample and not input_ids.is_cuda:
-        raise ValueError(f"{what} with do_sample=True needs input_ids (and both models) on the GPU, got {input_ids.device}: "
-                         "speculative sampling runs on HIP kernels only")
-
-
-def _check_rotary(what, models, input_ids, max_length, gamma, prompt_length, gamma_name="num_assistant_tokens"):
-    """the two RoPE limits of a speculative loop, whatever drafts: one rotary position per batch, and the tables' rows"""
+    for _, m in models:
+        _check_supported(m)
     cap = int(prompt_length) + int(max_length) + int(gamma) + 1
     for name, m in models:
         first = m.decoder.block[0].self_attention_layer.self_attention
@@ -364,29 +364,23 @@ def _check_rotary(what, models, input_ids, max_length, gamma, prompt_length, gam
         if cap > first.pe_encoding.max_sequence_length:
             raise ValueError(f"{what}: the cache of {cap} positions (prompt + max_length + {gamma_name} + 1) exceeds the "
                              f"rotary tables' {first.pe_encoding.max_sequence_length} rows of {name}")
+    if do_sample and not input_ids.is_cuda:
+        raise ValueError(f"{what} with do_sample=True needs input_ids (and both models) on the GPU, got {input_ids.device}: "
+                         "speculative sampling runs on HIP kernels only")
 
 
 def check_lookup_generate_args(model, input_ids, max_length, prompt_lookup_num_tokens, max_matching_ngram_size, prompt_length,
                                do_sample, num_beams, processors_active, assistant_model=None):
     """`generate(prompt_lookup_num_tokens=...)`'s host-side rejections, before the encoder runs"""
-    from .generation import _check_supported
     from .prompt_lookup import check_args as check_lookup_args
     what = "generate: prompt_lookup_num_tokens (prompt-lookup speculative decoding)"
     if assistant_model is not None:
         raise ValueError(f"{what} together with assistant_model is not supported: a round has one drafter")
-    if num_beams > 1:
-        raise ValueError(f"{what} with num_beams > 1 is not supported: a beam has no single token for a draft to be checked against")
-    if processors_active:
-        raise ValueError(f"{what} with logits processors (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens) "
-                         "is not supported: the chunk's rows would each need the sequence up to their own position")
+    _check_single_sequence(what, num_beams, processors_active)
     check_lookup_args(prompt_lookup_num_tokens, max_matching_ngram_size, None, "generate",
                       ("prompt_lookup_num_tokens", "max_matching_ngram_size"))
-    if not all(hasattr(model, a) for a in ("encoder", "decoder", "shared", "lm_head")):
-        raise ValueError(f"{what} must be called on a FAT5ForConditionalGeneration, got {type(model).__name__}")
-    _check_supported(model)
-    _check_rotary(what, (("the model", model),), input_ids, max_length, prompt_lookup_num_tokens, prompt_length,
-                  "prompt_lookup_num_tokens")
-    _check_sampled_device(what, do_sample, input_ids)
+    _check_models(what, "must be called on", (("the model", model),), input_ids, max_length, prompt_lookup_num_tokens,
+                  "prompt_lookup_num_tokens", prompt_length, do_sample)
 
 
 @torch.no_grad()
@@ -399,7 +393,7 @@ def speculative_generate(model, assistant_model, input_ids, attention_mask, max_
     `Padding` or None; its device lengths keep the padding of input_ids out of the lookup.  `sampling` = (temperature, top_k,
     top_p, seed) switches the round to speculative sampling: the assistant samples its drafts under a key of its own
     and hands its logits to the verification; the lookup's drafts are verified as one-hot"""
-    from .generation import _capture_call, decode_chunk, finish_labels, init_decode_state
+    from .generation import _prefill_prompt, _run_steps, finish_labels, init_decode_state
     lookup = assistant_model is None
     gamma, P, T_max = int(num_assistant_tokens), int(prompt_length), int(max_length)
     B, dev = input_ids.shape[0], input_ids.device
@@ -420,46 +414,26 @@ def speculative_generate(model, assistant_model, input_ids, attention_mask, max_
         src_seqlens = None if attention_mask is None else attention_mask.lengths_dev
         N, V = int(lookup_ngram), int(model.lm_head.weight.shape[0])
     if decoder_input_ids is not None:
-        prompt = decoder_input_ids.to(dev)
-        labels[:, :P] = prompt
-        tok.copy_(prompt[:, P - 1])
-        if P > 1:
-            decode_chunk(model, state, prompt[:, :P - 1], logits="none")
-            if not lookup:
-                decode_chunk(assistant_model, dstate, prompt[:, :P - 1], logits="none")
-
-    dl = [None]  # the assistant's logits of a sampled round: allocated by the first (eager) round, static from then on
+        _prefill_prompt(decoder_input_ids, P, labels, tok, (model, state), (assistant_model, dstate))
+    dl = None  # the assistant's logits of a sampled round: allocated by the first (eager) round, static from then on
 
     def one_round():
+        nonlocal dl
         if lookup:
             _, n_prop = prompt_lookup_draft(source, labels, state.cache_seqlens, tok, seen_eos, gamma, N, src_seqlens, V, out=draft)
         else:
             if stats is not None:
                 stats[0].add_((~seen_eos).sum())
-            dl[0] = draft_tokens(assistant_model, dstate, tok, draft, sampling=sampling, draft_logits=dl[0])
+            dl = draft_tokens(assistant_model, dstate, tok, draft, sampling=sampling, draft_logits=dl)
         n_acc, _ = speculative_round(model, state, tok, draft, labels, seen_eos, limit, draft_state=dstate, sampling=sampling,
-                                     draft_logits=dl[0])
+                                     draft_logits=dl)
         if stats is not None:
             if lookup:  # (a finished row proposes nothing; a filler the target agrees with is no accepted draft)
                 stats[0].add_(n_prop.sum())
                 n_acc = torch.minimum(n_acc, n_prop)
             stats[1].add_(n_acc.sum())
 
-    rounds = 0
-    g = None
-    try:
-        for _ in range(T_max):  # (every live row gains at least one token per round)
-            if g is not None:
-                g.replay()
-            else:
-                one_round()
-            rounds += 1
-            if bool(seen_eos.all()):
-                break
-            if graph and g is None and rounds < T_max:
-                g = _capture_call(one_round)
-    finally:
-        del g
+    rounds = _run_steps(one_round, lambda: bool(seen_eos.all()), T_max, graph)  # (every live row gains a token per round)
     T = int(state.cache_seqlens.max()) - (P - 1)  # the most new tokens any row produced
     out = finish_labels(labels[:, :P + T])
     if return_stats:

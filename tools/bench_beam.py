@@ -146,8 +146,8 @@ def run(Bs, k, max_length, L_enc, quick):
             gtok = torch.zeros(B * k, dtype=torch.long, device="cuda")
             labels = torch.zeros(B * k, gst.capacity, dtype=torch.long, device="cuda")
             seen = torch.zeros(B * k, dtype=torch.bool, device="cuda")
-            generation._greedy_step(m, gst, gtok, labels, seen)
-            g = generation._capture(m, gst, gtok, labels, seen)
+            generation._step(m, gst, gtok, labels, seen)
+            g = generation._capture_call(lambda: generation._step(m, gst, gtok, labels, seen))
             s.record()
             for _ in range(steps):
                 g.replay()

@@ -112,10 +112,10 @@ def e2e_rows(new_tokens=64, L_enc=512):
                 labels = torch.zeros((B, state.capacity), dtype=torch.long, device="cuda")
                 tok = torch.zeros((B,), dtype=torch.long, device="cuda")
                 eos = torch.zeros((B,), dtype=torch.bool, device="cuda")
-                generation._greedy_step(model, state, tok, labels, eos)  # (step 0 eager in both modes, as generate does)
-                g = generation._capture(model, state, tok, labels, eos) if graph else None
+                generation._step(model, state, tok, labels, eos)  # (step 0 eager in both modes, as generate does)
+                g = generation._capture_call(lambda: generation._step(model, state, tok, labels, eos)) if graph else None
                 torch.cuda.synchronize()
-                t = ev_time(lambda: [g.replay() if graph else generation._greedy_step(model, state, tok, labels, eos)
+                t = ev_time(lambda: [g.replay() if graph else generation._step(model, state, tok, labels, eos)
                                      for _ in range(new_tokens - 1)])
                 return t / (new_tokens - 1)
 

@@ -199,19 +199,19 @@ def e2e_rows(new_tokens=64, L_enc=512, reps=3):
                 tok = torch.zeros((B,), dtype=torch.long, device="cuda")
                 eos = torch.zeros((B,), dtype=torch.bool, device="cuda")
                 step(model, state, tok, labels, eos)
-                g = generation._capture(model, state, tok, labels, eos, step)
+                g = generation._capture_call(lambda: step(model, state, tok, labels, eos))
                 return _replay_ms(g, new_tokens - 1)
 
             steps = {
-                "greedy": lambda m, st, t, lb, e: generation._greedy_step(m, st, t, lb, e),
-                "greedy_proc": lambda m, st, t, lb, e: generation._greedy_step(m, st, t, lb, e, PROC),
-                "sample": lambda m, st, t, lb, e: generation._sample_step(m, st, t, lb, e, sampling),
-                "sample_proc": lambda m, st, t, lb, e: generation._sample_step(m, st, t, lb, e, sampling, PROC),
+                "greedy": lambda m, st, t, lb, e: generation._step(m, st, t, lb, e),
+                "greedy_proc": lambda m, st, t, lb, e: generation._step(m, st, t, lb, e, PROC),
+                "sample": lambda m, st, t, lb, e: generation._step(m, st, t, lb, e, None, sampling),
+                "sample_proc": lambda m, st, t, lb, e: generation._step(m, st, t, lb, e, PROC, sampling),
             }
             if EXT:
                 ext = _ext_proc(ids)
-                steps["greedy_ext"] = lambda m, st, t, lb, e: generation._greedy_step(m, st, t, lb, e, ext)
-                steps["sample_ext"] = lambda m, st, t, lb, e: generation._sample_step(m, st, t, lb, e, sampling, ext)
+                steps["greedy_ext"] = lambda m, st, t, lb, e: generation._step(m, st, t, lb, e, ext)
+                steps["sample_ext"] = lambda m, st, t, lb, e: generation._step(m, st, t, lb, e, ext, sampling)
             cached(steps["greedy"])  # warm-up
             ms = {k: [] for k in steps}
             for _ in range(reps):  # (alternated)

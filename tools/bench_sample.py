@@ -103,16 +103,16 @@ def e2e_rows(new_tokens=64, L_enc=512):
                 tok = torch.zeros((B,), dtype=torch.long, device="cuda")
                 eos = torch.zeros((B,), dtype=torch.bool, device="cuda")
                 step(model, state, tok, labels, eos)  # (step 0 eager, as generate does)
-                g = generation._capture(model, state, tok, labels, eos, step)
+                g = generation._capture_call(lambda: step(model, state, tok, labels, eos))
                 torch.cuda.synchronize()
                 return ev_time(lambda: [g.replay() for _ in range(new_tokens - 1)]) / (new_tokens - 1)
 
             def sample_step(model, state, tok, labels, eos):
-                generation._sample_step(model, state, tok, labels, eos, sampling)
+                generation._step(model, state, tok, labels, eos, sampling=sampling)
 
-            cached(generation._greedy_step)  # warm-up
+            cached(generation._step)  # warm-up
             for rep in range(3):  # (alternated: greedy, sampling, greedy, ...)
-                out.setdefault("greedy_ms", []).append(cached(generation._greedy_step) * 1e3)
+                out.setdefault("greedy_ms", []).append(cached(generation._step) * 1e3)
                 out.setdefault("sample_ms", []).append(cached(sample_step) * 1e3)
         g_ms, s_ms = min(out["greedy_ms"]), min(out["sample_ms"])
         rows[f"B{B}"] = {"greedy_ms_per_token": round(g_ms, 4), "sample_ms_per_token": round(s_ms, 4),
