@@ -20,6 +20,7 @@ from .cross_entropy_loss import cross_entropy_loss, CrossEntropyLoss  # noqa: E4
 from .lm_head_cross_entropy import lm_head_cross_entropy, LMHeadCrossEntropy  # noqa: E402
 from .fused_linear import rmsnorm_linear, linear_residual, RMSNormLinear, LinearResidual  # noqa: E402
 from .gated_act import gated_act, gated_act_packed  # noqa: E402
+from .dropout import dropout, dropout_add, dropout_add_rms_layernorm  # noqa: E402
 from .fire import fire_bias, FIRE  # noqa: E402
 from .rotary import (apply_rotary_emb, apply_rotary_emb_qkv, apply_rotary_emb_packed, rotary_tables,  # noqa: E402
                      RotaryPositionalEncoding)

@@ -213,6 +213,14 @@ class PackParams(ctypes.Structure):
     ]
 
 
+class DropoutDesc(ctypes.Structure):
+    """Mirror of `fat5_dropout_desc` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64), ("step", ctypes.c_void_p), ("elem_offset", ctypes.c_uint64), ("site", ctypes.c_uint32),
+        ("p", ctypes.c_float),
+    ]
+
+
 EXPORTS = (
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
@@ -232,6 +240,7 @@ EXPORTS = (
     "fat5_kv_quantize", "fat5_sizeof_kv_quant_params",
     "fat5_lookup_draft", "fat5_sizeof_lookup_params",
     "fat5_pack_plan", "fat5_sizeof_pack_params",
+    "fat5_dropout", "fat5_dropout_add_rmsnorm_fwd", "fat5_dropout_add_rmsnorm_bwd", "fat5_sizeof_dropout_desc",
 )
 
 _lib = None
@@ -395,6 +404,18 @@ def load():
     if lib.fat5_sizeof_pack_params() != ctypes.sizeof(PackParams):
         raise ImportError(f"fat5_pack_params layout mismatch: library {lib.fat5_sizeof_pack_params()} B, "
                           f"binding {ctypes.sizeof(PackParams)} B")
+    dd = ctypes.POINTER(DropoutDesc)
+    lib.fat5_dropout.restype = ctypes.c_int
+    lib.fat5_dropout.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, dd, i32, vp]
+    lib.fat5_dropout_add_rmsnorm_fwd.restype = ctypes.c_int
+    lib.fat5_dropout_add_rmsnorm_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, f32, dd, i32, i32, vp]
+    lib.fat5_dropout_add_rmsnorm_bwd.restype = ctypes.c_int
+    lib.fat5_dropout_add_rmsnorm_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, dd, i32, i32, vp,
+                                                 ctypes.c_size_t, vp]
+    lib.fat5_sizeof_dropout_desc.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_dropout_desc() != ctypes.sizeof(DropoutDesc):
+        raise ImportError(f"fat5_dropout_desc layout mismatch: library {lib.fat5_sizeof_dropout_desc()} B, "
+                          f"binding {ctypes.sizeof(DropoutDesc)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

@@ -64,6 +64,17 @@ inline int check_workspace(const char* what, const void* ws, size_t bytes, size_
   return FAT5_OK;
 }
 
+// workgroups of the RMSNorm backward kernels (api_rowwise.hip, api_dropout.hip) = fp32 partial dw rows in their workspace
+inline int rms_bwd_blocks(int64_t rows) {
+  // persistent 8-wave workgroups, one row per wave and trip: two per CU keep enough 16-byte
+  // loads in flight to cover the HBM latency (one per CU: 4.5 TB/s at (65536, 1024))
+  // (measured: 256 / 384 / 512 / 768 workgroups -> 4.48 / 4.98 / 5.08 / 4.78 TB/s; small inputs keep >= 2 rows per wave so that
+  //  the dw reduction over the workgroups' partial sums stays short)
+  const int cap = 512;
+  int64_t b = (rows + 15) / 16;
+  return (int)(b < cap ? b : cap);
+}
+
 // the logits warpers of sampling and speculative sampling
 inline int check_warpers(const char* what, float temperature, int top_k, float top_p) {
   if (!std::isfinite(temperature) || !(temperature > 0.f)) return fail(FAT5_EINVAL, "%s: temperature %g (finite and > 0)", what, (double)temperature);

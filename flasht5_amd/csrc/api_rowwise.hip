@@ -22,16 +22,6 @@ namespace {
     __VA_ARGS__                                    \
   });
 
-int rms_bwd_blocks(int64_t rows) {
-  // persistent 8-wave workgroups, one row per wave and trip: two per CU keep enough 16-byte
-  // loads in flight to cover the HBM latency (one per CU: 4.5 TB/s at (65536, 1024))
-  // (measured: 256 / 384 / 512 / 768 workgroups -> 4.48 / 4.98 / 5.08 / 4.78 TB/s; small inputs keep >= 2 rows per wave so that
-  //  the dw reduction over the workgroups' partial sums stays short)
-  const int cap = 512;
-  int64_t b = (rows + 15) / 16;
-  return (int)(b < cap ? b : cap);
-}
-
 int rmsnorm_bwd_impl(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, int64_t drs, void* dx,
                             void* dw, int64_t rows, int64_t n, int64_t dys, int64_t xs, int64_t dxs, int x_dtype, int w_dtype,
                             void* workspace, size_t workspace_bytes, void* stream_) {

@@ -14,8 +14,11 @@ A minimal encoder-decoder with the reference's structure (src/model/modeling_fla
 Generation: `generate` (greedy -- the reference's algorithm and return value --, sampled, or beam search) and `decode_step` run one new token per step through
 the decoder against per-layer KV caches (flasht5_amd/generation.py, the split-KV decode kernel), optionally replayed from a HIP graph.
 
-This is the step DRIVER of the hot path, not a model zoo: no heads, dropout (0 in every reference config),
-HF plumbing or checkpoint conversion.  Data parallelism = one process per GPU; `allreduce_gradients` is the step's one
+Dropout (`dropout_rate`, 0 in every reference pre-training config, 0.1 in fine-tuning recipes) is applied at the reference's six
+kinds of places with Philox masks recomputed inside HIP kernels (flasht5_amd/dropout.py): nothing is stored, and a
+captured `GraphedTrainStep` draws new masks at every replay because the step counter lives in device memory.
+
+This is the step DRIVER of the hot path, not a model zoo: no heads, HF plumbing or checkpoint conversion.  Data parallelism = one process per GPU; `allreduce_gradients` is the step's one
 exchange (RCCL over xGMI): a single flat fp32 all-reduce that carries the two `(32, H)` relative-position tables first.
 """
 import math
@@ -64,12 +67,19 @@ class FAT5Config:
     fuse_norm_linear: bool = False         # stacked projections (q | k | v, wi_0 | wi_1: one library GEMM each, packed gradients), the residual add in the
                                            # output projection's GEMM epilogue, fused backward passes around them (fused_linear.py)
     fuse_gated_act: bool = True            # act(wi_0 x) * wi_1 x in one kernel forward, one backward (gated_act.py / fat5_gated_act_*)
+    dropout_rate: float = 0.0              # the reference's six dropout sites (modeling_flash_t5.py :124/:143, :163, :316, :342, :440, :460), training only
+    dropout_seed: Optional[int] = None     # the Philox key of the masks; None: drawn from torch's default CPU generator when the model is built
     is_decoder: bool = False
 
     def __post_init__(self):
         if self.position_encoding_type == "FIRE" and self.attention_type == "fat5_rpe":
             raise ValueError("position_encoding_type='FIRE' needs attention_type='triton' (dense bias): FIRE's bias is not "
                              "Toeplitz once a row passes the threshold T, so fat5_rpe cannot carry it")
+        if not 0.0 <= float(self.dropout_rate) < 1.0:
+            raise ValueError(f"dropout_rate = {self.dropout_rate} outside [0, 1)")
+        if self.dropout_rate > 0 and self.fuse_norm_linear:
+            raise ValueError("dropout_rate > 0 with fuse_norm_linear: that path's residual add is a GEMM epilogue, which cannot carry "
+                             "a dropout mask (use fuse_add_norm, whose pre-norm kernel applies it, or the plain path)")
 
 
 class FAT5GatedAct(nn.Module):  # reference FlashT5DenseGatedAct / FlashT5DenseAct (:114-146)
@@ -109,10 +119,32 @@ def _cross_kw(packing):
                 kv_max_seqlen=packing.kv_max_seqlen)
 
 
-def _pre_norm(ln, h, pending):
-    """pre-norm of a sub-layer with the previous sub-layer's residual add folded in: (h + pending, layer_norm(h + pending))"""
+class _Drop:
+    """what the dropout sites of ONE training forward share: the rate, this rank's Philox key and the forward's own copy of the step
+    counter (an int64 device tensor the kernels read, forward and backward)"""
+    __slots__ = ("p", "key", "step")
+
+    def __init__(self, p, key, step):
+        self.p, self.key, self.step = p, key, step
+
+    def __call__(self, x, site):
+        from .dropout import dropout
+        return dropout(x, self.p, self.key, self.step, site)
+
+    def add(self, h, delta, site):
+        """h + dropout(delta): the residual add of a sub-layer whose output is dropped out at `site`"""
+        from .dropout import dropout_add
+        return dropout_add(delta, h, self.p, self.key, self.step, site)
+
+
+def _pre_norm(ln, h, pending, drop=None, pending_site=0):
+    """pre-norm of a sub-layer with the previous sub-layer's residual add folded in: (h + pending, layer_norm(h + pending));
+    with `drop` the pending output is dropped out (at the site of the sub-layer that produced it) inside the same kernel"""
     if pending is None:
         return h, ln(h)
+    if drop is not None:
+        from .dropout import dropout_add_rms_layernorm
+        return dropout_add_rms_layernorm(h, pending, ln.weight, ln.variance_epsilon, drop.p, drop.key, drop.step, pending_site)
     from .rms_norm import fused_add_rms_layernorm
     return fused_add_rms_layernorm(h, pending, ln.weight, ln.variance_epsilon)
 
@@ -124,7 +156,11 @@ class FAT5LayerFF(nn.Module):  # :148-164
         self.layer_norm = FlashT5LayerNorm(c.d_model, eps=c.layer_norm_epsilon)
         self.wo = nn.Linear(c.d_ff, c.d_model, bias=False)
 
-    def forward(self, h):
+    site_act = site = 0  # dropout sites: after the activation (in front of wo) and on the sub-layer's output (FAT5Stack numbers them)
+
+    def forward(self, h, drop=None):
+        if drop is not None:
+            return drop.add(h, self.wo(drop(self.act(self.layer_norm(h)), self.site_act)), self.site)
         return h + self.wo(self.act(self.layer_norm(h)))
 
     def forward_fused(self, h):
@@ -144,10 +180,11 @@ class FAT5LayerFF(nn.Module):  # :148-164
             t = a.act(t)
         return linear_residual(t, self.wo.weight, h)
 
-    def forward_deferred(self, h, pending):
+    def forward_deferred(self, h, pending, drop=None, pending_site=0):
         """(h, delta): the residual stream after the pending add, and this sub-layer's output whose add is left to the next pre-norm"""
-        h, n = _pre_norm(self.layer_norm, h, pending)
-        return h, self.wo(self.act(n))
+        h, n = _pre_norm(self.layer_norm, h, pending, drop, pending_site)
+        t = self.act(n)
+        return h, self.wo(t if drop is None else drop(t, self.site_act))
 
 
 class FAT5LayerSelfAttention(nn.Module):  # :297-318
@@ -156,16 +193,18 @@ class FAT5LayerSelfAttention(nn.Module):  # :297-318
         self.self_attention = FlashT5Attention(c, has_positional_encoding=has_positional_encoding, is_causal=c.is_decoder)
         self.layer_norm = FlashT5LayerNorm(c.d_model, eps=c.layer_norm_epsilon)
 
-    def forward(self, h, position_bias=None, packing=None):
+    site = 0  # dropout site of the sub-layer's output
+
+    def forward(self, h, position_bias=None, packing=None, drop=None):
         a, position_bias = self.self_attention(self.layer_norm(h), position_bias=position_bias, **_self_kw(packing))
-        return h + a, position_bias
+        return (h + a if drop is None else drop.add(h, a, self.site)), position_bias
 
     def forward_fused(self, h, position_bias=None, packing=None):
         return self.self_attention.forward_fused(h, self.layer_norm.weight, self.layer_norm.variance_epsilon, position_bias=position_bias,
                                                  **_self_kw(packing))
 
-    def forward_deferred(self, h, pending, position_bias=None, packing=None):
-        h, n = _pre_norm(self.layer_norm, h, pending)
+    def forward_deferred(self, h, pending, position_bias=None, packing=None, drop=None, pending_site=0):
+        h, n = _pre_norm(self.layer_norm, h, pending, drop, pending_site)
         a, position_bias = self.self_attention(n, position_bias=position_bias, **_self_kw(packing))
         return h, a, position_bias
 
@@ -176,16 +215,18 @@ class FAT5LayerCrossAttention(nn.Module):  # :321-349
         self.cross_attention = FlashT5Attention(c, has_positional_encoding=False)
         self.layer_norm = FlashT5LayerNorm(c.d_model, eps=c.layer_norm_epsilon)
 
-    def forward(self, h, key_value_states, packing=None):
+    site = 0  # dropout site of the sub-layer's output
+
+    def forward(self, h, key_value_states, packing=None, drop=None):
         a, _ = self.cross_attention(self.layer_norm(h), key_value_states=key_value_states, **_cross_kw(packing))
-        return h + a
+        return h + a if drop is None else drop.add(h, a, self.site)
 
     def forward_fused(self, h, key_value_states, packing=None):
         return self.cross_attention.forward_fused(h, self.layer_norm.weight, self.layer_norm.variance_epsilon, key_value_states=key_value_states,
                                                   **_cross_kw(packing))[0]
 
-    def forward_deferred(self, h, pending, key_value_states, packing=None):
-        h, n = _pre_norm(self.layer_norm, h, pending)
+    def forward_deferred(self, h, pending, key_value_states, packing=None, drop=None, pending_site=0):
+        h, n = _pre_norm(self.layer_norm, h, pending, drop, pending_site)
         a, _ = self.cross_attention(n, key_value_states=key_value_states, **_cross_kw(packing))
         return h, a
 
@@ -199,11 +240,21 @@ class FAT5Block(nn.Module):  # :352-392
             self.cross_attention_layer = FAT5LayerCrossAttention(c)
         self.ff_layer = FAT5LayerFF(c)
 
-    def forward(self, h, position_bias=None, encoder_hidden_states=None, packing=None):
-        h, position_bias = self.self_attention_layer(h, position_bias, packing)
+    def assign_sites(self, site):
+        """number this block's dropout sites in forward order from `site`; returns the next free number"""
+        self.self_attention_layer.site = site
+        site += 1
+        if self.is_decoder:
+            self.cross_attention_layer.site = site
+            site += 1
+        self.ff_layer.site_act, self.ff_layer.site = site, site + 1
+        return site + 2
+
+    def forward(self, h, position_bias=None, encoder_hidden_states=None, packing=None, drop=None):
+        h, position_bias = self.self_attention_layer(h, position_bias, packing, drop)
         if self.is_decoder and encoder_hidden_states is not None:
-            h = self.cross_attention_layer(h, encoder_hidden_states, packing)
-        return self.ff_layer(h), position_bias
+            h = self.cross_attention_layer(h, encoder_hidden_states, packing, drop)
+        return self.ff_layer(h, drop), position_bias
 
     def forward_fused(self, h, position_bias=None, encoder_hidden_states=None, packing=None):
         h, position_bias = self.self_attention_layer.forward_fused(h, position_bias, packing)
@@ -211,30 +262,54 @@ class FAT5Block(nn.Module):  # :352-392
             h = self.cross_attention_layer.forward_fused(h, encoder_hidden_states, packing)
         return self.ff_layer.forward_fused(h), position_bias
 
-    def forward_deferred(self, h, pending, position_bias=None, encoder_hidden_states=None, packing=None):
-        h, pending, position_bias = self.self_attention_layer.forward_deferred(h, pending, position_bias, packing)
+    def forward_deferred(self, h, pending, position_bias=None, encoder_hidden_states=None, packing=None, drop=None, pending_site=0):
+        """pending_site: the dropout site of the sub-layer that produced `pending` (the previous block's feed-forward)"""
+        h, pending, position_bias = self.self_attention_layer.forward_deferred(h, pending, position_bias, packing, drop, pending_site)
+        pending_site = self.self_attention_layer.site
         if self.is_decoder and encoder_hidden_states is not None:
-            h, pending = self.cross_attention_layer.forward_deferred(h, pending, encoder_hidden_states, packing)
-        h, pending = self.ff_layer.forward_deferred(h, pending)
+            h, pending = self.cross_attention_layer.forward_deferred(h, pending, encoder_hidden_states, packing, drop, pending_site)
+            pending_site = self.cross_attention_layer.site
+        h, pending = self.ff_layer.forward_deferred(h, pending, drop, pending_site)
         return h, pending, position_bias
 
 
 class FAT5Stack(nn.Module):  # :394-464
-    def __init__(self, c, embed_tokens, n_layers):
+    def __init__(self, c, embed_tokens, n_layers, first_site=0):
         super().__init__()
         self.embed_tokens = embed_tokens
         self.block = nn.ModuleList([FAT5Block(c, has_positional_encoding=(i == 0)) for i in range(n_layers)])
         self.final_layer_norm = FlashT5LayerNorm(c.d_model, eps=c.layer_norm_epsilon)
         self.fuse_add_norm = c.fuse_add_norm
         self.fuse_norm_linear = c.fuse_norm_linear
+        # dropout sites in forward order (DESIGN 4.21): the embeddings, every block's sub-layers, the final norm's output
+        self.site_embed = first_site
+        site = first_site + 1
+        for blk in self.block:
+            site = blk.assign_sites(site)
+        self.site_final = site
+        self.next_site = site + 1
 
-    def forward(self, input_ids, encoder_hidden_states=None, packing=None):
+    def forward(self, input_ids, encoder_hidden_states=None, packing=None, drop=None):
         """packing (packing.Packed): input_ids are the (1, total) valid tokens of a padded or packed batch, every attention layer
-        runs over cu_seqlens, and the output stays (1, total, d_model)"""
+        runs over cu_seqlens, and the output stays (1, total, d_model).  drop (_Drop): a training forward with dropout; None (what
+        every caller but the training loss passes) runs the code below as it always ran"""
         h = self.embed_tokens(input_ids)
         if torch.is_autocast_enabled() and h.is_cuda:  # :424-425
             h = h.to(torch.get_autocast_gpu_dtype())
         position_bias = None  # produced by block 0, shared by the others (:452-455)
+        if drop is not None:
+            h = drop(h, self.site_embed)  # :440
+            if self.fuse_add_norm:
+                pending, pending_site = None, 0
+                for blk in self.block:
+                    h, pending, position_bias = blk.forward_deferred(h, pending, position_bias, encoder_hidden_states, packing, drop, pending_site)
+                    pending_site = blk.ff_layer.site
+                h = _pre_norm(self.final_layer_norm, h, pending, drop, pending_site)[1]
+            else:
+                for blk in self.block:
+                    h, position_bias = blk(h, position_bias, encoder_hidden_states, packing, drop)
+                h = self.final_layer_norm(h)
+            return drop(h, self.site_final)  # :460
         if self.fuse_norm_linear and h.dtype in (torch.float16, torch.bfloat16):
             for blk in self.block:
                 h, position_bias = blk.forward_fused(h, position_bias, encoder_hidden_states, packing)
@@ -260,11 +335,31 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         dec = copy.copy(config)
         dec.is_decoder = True
         self.encoder = FAT5Stack(enc, self.shared, config.num_layers)
-        self.decoder = FAT5Stack(dec, self.shared, config.num_decoder_layers)
+        self.decoder = FAT5Stack(dec, self.shared, config.num_decoder_layers, first_site=self.encoder.next_site)
         self.lm_head = nn.Linear(config.d_model, config.vocab_size, bias=False)
         self.loss_fct = FlashT5CrossEntropyLoss(z_loss_factor=config.z_loss, label_smoothing=config.label_smoothing,
                                                 inplace_backward=config.crossentropy_inplace_backward)
         self.reset_parameters()
+        # dropout: the step counter is a buffer outside the state dict (reference checkpoints load strictly); a
+        # dropout_rate of 0 builds nothing and draws nothing
+        self.dropout_seed = config.dropout_seed
+        if config.dropout_rate > 0:
+            if self.dropout_seed is None:
+                self.dropout_seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64))
+            self.register_buffer("dropout_step", torch.zeros(1, dtype=torch.int64), persistent=False)
+
+    def _drop(self):
+        """the dropout context of this forward, or None (eval, or dropout_rate 0: no new launch, today's code path).  The sites of
+        the forward and of its backward read a COPY of the step counter; the counter itself is advanced on the device right away,
+        so a captured step holds both and every replay draws new masks."""
+        c = self.config
+        if not (self.training and c.dropout_rate > 0):
+            return None
+        from .dropout import rank_key
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        step = self.dropout_step.clone()
+        self.dropout_step.add_(1)
+        return _Drop(float(c.dropout_rate), rank_key(self.dropout_seed, rank), step)
 
     @torch.no_grad()
     def reset_parameters(self):
@@ -314,8 +409,9 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
             packed = self._pack(input_ids, labels, attention_mask, decoder_attention_mask, segment_ids, decoder_segment_ids)
             if packed is not None:   # (None: nothing is padded and no row holds two examples -- the code below, bit for bit)
                 return self._forward_packed(*packed)
-        enc = self.encoder(input_ids)
-        dec = self.decoder(self._shift_right(labels), encoder_hidden_states=enc)
+        drop = self._drop()
+        enc = self.encoder(input_ids, drop=drop)
+        dec = self.decoder(self._shift_right(labels), encoder_hidden_states=enc, drop=drop)
         return self._loss(dec, labels)
 
     def _loss(self, dec, labels):
@@ -388,9 +484,10 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         shifted = torch.cat([lab.new_full((1,), c.decoder_start_token_id), lab[:-1]])
         shifted.index_fill_(0, dp.cu_seqlens[:-1].long(), c.decoder_start_token_id)
         shifted = shifted.masked_fill(shifted == -100, c.pad_token_id).unsqueeze(0)
-        enc = self.encoder(ids, packing=Packed(ep.cu_seqlens, ep.max_seqlen))
+        drop = self._drop()   # (the masks index the packed (total, d_model) rows)
+        enc = self.encoder(ids, packing=Packed(ep.cu_seqlens, ep.max_seqlen), drop=drop)
         dec = self.decoder(shifted, encoder_hidden_states=enc,
-                           packing=Packed(dp.cu_seqlens, dp.max_seqlen, ep.cu_seqlens, ep.max_seqlen))
+                           packing=Packed(dp.cu_seqlens, dp.max_seqlen, ep.cu_seqlens, ep.max_seqlen), drop=drop)
         return self._loss(dec, lab.unsqueeze(0))
 
     def init_decode_state(self, input_ids, max_length=32, attention_mask=None, prompt_length=1, kv_cache_dtype=None):

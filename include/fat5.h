@@ -209,6 +209,50 @@ int fat5_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* 
                      size_t workspace_bytes, void* hip_stream);
 
 /*
+ * Dropout with a recomputed mask (dropout_kernels.h).  One call is described by (p, seed, step, site, elem_offset).
+ * For the element at logical row i, column c of a (rows, n) operand:
+ *   e = elem_offset + i * n + c   (64-bit; row strides do not enter);   block j = e >> 2, lane l = e & 3;
+ *   w = Philox4x32-10(key = (seed lo, seed hi), counter = (j lo, j hi, site, step mod 2^32));
+ *   u = (w[l] >> 8) * 2^-24;   the element is kept iff u >= p, compared as fp32 (both sides are exact);
+ *   s = 1.0f / (1.0f - p), one fp32 division;
+ *   dropout(x) = round_to_dtype(fp32(x) * s) where kept, +0 where dropped.
+ * `step` is read on the device, so a launch captured in a HIP graph draws a new mask at every replay once the caller advances the
+ * counter; p, seed, site and elem_offset are launch arguments.  The mask is never stored: a backward pass hands in the same
+ * descriptor and the same bits come out.
+ * Rejected with FAT5_EINVAL before anything is launched: a NULL descriptor, p outside [0, 1) (NaN included), a NULL or misaligned
+ * step, a dtype outside {FAT5_F32, FAT5_F16, FAT5_BF16}, a NULL tensor, rows or n < 1.
+ */
+typedef struct fat5_dropout_desc {
+  uint64_t seed;          /* the Philox key */
+  const int64_t* step;    /* DEVICE pointer to the step counter (8-byte aligned); its low 32 bits enter the counter */
+  uint64_t elem_offset;   /* e of the operand's first element */
+  uint32_t site;          /* which dropout call of the model this is */
+  float p;                /* drop probability, 0 <= p < 1 */
+} fat5_dropout_desc;
+/* sizeof(fat5_dropout_desc) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_dropout_desc(void);
+/* y = dropout(x), or with r given y = round(fp32(r) + fp32(dropout(x))): the dropped x is rounded to `dtype` before the add, so
+ * the result has the bits of the separate add.  x, r, y: (rows, n) with row strides in elements, unit inner stride; r may be NULL.
+ * The backward of either form is this entry point applied to dy without r.  16-byte accesses when n is a multiple of 8 and
+ * the rows are 16-byte aligned, element accesses otherwise; rows * n / 8 (/ 4 for fp32; rows * n on the element path) < 2^32. */
+int fat5_dropout(const void* x, const void* r, void* y, int64_t rows, int64_t n, int64_t x_row_stride, int64_t r_row_stride,
+                 int64_t y_row_stride, const fat5_dropout_desc* desc, int dtype, void* hip_stream);
+/* fat5_add_rmsnorm_fwd with the delta operand dropped out on the way in: h = round(x + dropout(delta)), y = rmsnorm(h) * w -- (h, y,
+ * rstd) are bit-identical to fat5_dropout on delta followed by fat5_add_rmsnorm_fwd, without the pass and the tensor between them.
+ * The mask is that of delta as a logical (rows, n) operand. */
+int fat5_dropout_add_rmsnorm_fwd(const void* x, const void* delta, const void* w, void* h, void* y, float* rstd, int64_t rows,
+                                 int64_t n, int64_t x_row_stride, int64_t delta_row_stride, int64_t h_row_stride,
+                                 int64_t y_row_stride, float eps, const fat5_dropout_desc* desc, int x_dtype, int w_dtype,
+                                 void* hip_stream);
+/* its backward: dx (the gradient of x) and dw are bit-identical to fat5_add_rmsnorm_bwd's; ddelta = dropout(dx) under the same mask,
+ * bit-identical to fat5_dropout on dx, written in the same pass.  Workspace: fat5_rmsnorm_bwd_workspace_bytes(rows, n). */
+int fat5_dropout_add_rmsnorm_bwd(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, void* dx,
+                                 void* ddelta, void* dw, int64_t rows, int64_t n, int64_t dy_row_stride, int64_t h_row_stride,
+                                 int64_t dres_row_stride, int64_t dx_row_stride, int64_t ddelta_row_stride,
+                                 const fat5_dropout_desc* desc, int x_dtype, int w_dtype, void* workspace, size_t workspace_bytes,
+                                 void* hip_stream);
+
+/*
  * Stacked projections of a T5 block: layer_norm -> Wq / Wk / Wv (src/model/modeling_flash_t5.py:304-318, :95-98) and
  * layer_norm -> wi_0 / wi_1 (:159-160) as ONE library GEMM on the stacked weight.  (Versions <= 113 exported fat5_linear_fused, a hand-written
  * MFMA GEMM with the norm in its prologue: slower than the library GEMM on every FAT5-base shape, removed in 114.)
