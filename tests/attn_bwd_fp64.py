@@ -9,9 +9,11 @@ table gradient in both reduction forms (dtable=runs / scan).  And the non-dense 
 and rpe1d / T5 table: dq=64row; dkdv=64key, 64key-half, 64key-mixed:*; separate launches (the statistics from either dQ kernel, so
 also the mixed pairs 32row + 64key and 64row + 32key) and the one-launch form (fused=1: attn_bwd_fused64_kernel, the dK/dV half in its
 SELF form); qdiag=0 / 1; dtable=runs / scan.  Their derivation is the section "The 64-wide bodies" below.
-Not covered: the DENSE 64-wide bodies (dq=64row-batch4; the DENSE form of the 64-key body; the dense one-launch form; the dbias routes
-"dq-kernel" and "dq-kernel+partials"): `attn_bwd_bound` raises for them, the case list holds none, and they stay with the max-norm tests
-(tests/test_dense64_gpu.py).  The packed (cu_seqlens) layout: tests/attn_packed_fp64.py, which calls this file per sequence and
+And the DENSE 64-wide bodies at D = 64: dq=64row-batch4 (csrc/attn_bwd_qdb64.h: dQ and the batch-reduced dbias, routes "dq-kernel" and
+"dq-kernel+partials") beside dkdv=32key or the DENSE form of dkdv=64key, as two launches or in one behind bwd_stat2_kernel (fused=1:
+attn_bwd_dfused64_kernel); and the DENSE 64-key body beside the 32-row dQ kernel with a dense bias of any broadcast kind (routes direct /
+staged / inkernel).  Their derivation is the section "The dense 64-wide bodies" below.
+Not covered: the packed (cu_seqlens) layout: tests/attn_packed_fp64.py, which calls this file per sequence and
 `drpe_bound` once per batch.  Left to the existing tests: unit ranges, zero and negative sm_scale,
 head dimensions and dtypes the dispatcher rejects, the forward, any timing.
 
@@ -103,6 +105,57 @@ The 64-wide bodies (k:LINE = csrc/attn_bwd64.h).  Same restatement, same T / TA 
           err_drpe = e_dS T + c_A TA + D u TD + u_T (TF + that) + [fp16: 2^-25 (nF + [qdiag=1: n])], then gamma_1(2 n + 8) (T + err)
   The far bins' bound is therefore u_T times the magnitudes of tens of thousands of terms of both signs: it sees a wrong diagonal or a
   missing band, but not one 32 x 64 block more or less in a large far bin (tests/test_attn_bwd_fp64_cpu.py lists those pairs).
+The dense 64-wide bodies (q:LINE = csrc/attn_bwd_qdb64.h; k, c as above).  Same restatement, same T / TA / TD, one more companion:
+  TB (a_ij replaced by a_ij |bias_ij|; dv: p_ij |bias_ij| |do_id|): what the selector's residual multiplies.
+  The selector.  The bias enters the scores on the matrix pipe: S' = K Q^T + B^T E (q:396-411; pipelined q:553, q:559, q:603, q:609; the 64-key body
+      k:522-537) with E = invf = 1.f / scale (q:304, k:413-417) split by split16 (c:97-117, q:306) into hi + lo, hi in the first four k-slots
+      of a row and lo in the next four (q:313-315).  bias x hi and bias x lo are products of two 16-bit values: exact in fp32 (8 + 8 / 11 + 11
+      significand bits).  What is lost is r = invf - (hi + lo): bf16 truncates both terms (c:98-107), fp16 rounds them (c:109-110); `split16_of`
+      restates that on the host and gives rel = |r| / |invf| EXACTLY for the case's scale and dtype -- 0 in the ONE instantiations (c:119-124:
+      lo = 0; scale 0.125, 1.0, -0.5), 2^-17.3 (0.3, -0.3, 1.3) and 2^-15.7 (0.0884) in bf16, at most 2^-23.6 in fp16.  In the exponent that is
+      |bias_ij| rel |invf scale| nats, invf scale = 1 + at most u: carried as c_B TB with c_B = rel (1 + 2^-23) / (1 - 2^-7), no worst-case constant.
+      The rounding of invf itself (q:304: u, relative, of the bias term) is counted below.
+  e_p, the dQ + dBias body.  S' accumulates from 0 (q:391; causal: 0 or -inf of the scale's sign, q:374-381) D products (q:393-395): 2 D u, and the
+      bias products: a row's hi and lo sit in ONE of the four (ONE: two) bias MFMAs, every other product of these MFMAs has a zero selector
+      and adds an exact 0: two more additions, 4 u (ONE: one, 2 u), each of at most (smag + bmag) / |scale|.  Then ONE FMA x = fma(S', c2, nL2) in
+      both iterations (general q:473, pipelined q:528): c2 = scale * kLog2e (q:356) 2 u; invf 1 u of bmag; nL2 = -L * kLog2e (q:182) 2 u of |L|;
+      the FMA u of at most A.  2 D + 4 + 2 + 1 + 2 + 1 = 2 D + 10.
+  e_p, the DENSE 64-key body.  S' starts at the fp32 quotient -L / scale (k:505-506) -- written by the dQ + dBias body's prologue (q:186), by
+      bwd_stat2_kernel in the one-launch form (q:803: `-Lq / a.scale`, one rounding, the same bits) or by the 32-row dQ kernel (b:120): 2 u of
+      |L| as for the non-dense body; D products 2 D u; the bias products 4 u; invf 1 u; x = S' * c2 (general k:569; pipelined k:820 with
+      cst = 0): c2 2 u, the product u.  2 + 2 D + 4 + 1 + 2 + 1 = 2 D + 10 as well.
+          dx <= (2 D + 10) u A_i + rel |bias_ij| log2e  in log2 units;  `attn_bwd_bound` asserts ln2 (2 D + 10) u A_max + rel bmax < 2^-7
+      so e_p a_ij <= [ln2 (2 D + 10) u A_i + rel |bias_ij|] (1 + 2^-23) / (1 - 2^-7) a_ij + 2^-23 a_ij: on TA, TB and T.  The constants of a body
+      apply to the outputs it forms: beside the 32-row dQ kernel dq and dbias keep (2 D + 9) and no TB, beside the 32-key body dk and dv do.
+  -delta.  dQ + dBias body: delta is the prologue's fmaf chain over the lane's 32 elements and the pair sum (q:171-179), in the one-launch form
+      the same chain in bwd_stat2_kernel (q:790-798); both at most D u sum |o do|, on TD.  -delta is the C operand of the first dP' MFMA as
+      ONE fp32 value (nd16, q:190, q:416, q:562) -- not the three 16-bit pieces of the 64-row body: no absolute term in fp16, D additions 2 D u,
+      the product p * dP' (q:475, q:530) u: e_dS = 2^-23 + (2 D + 1) u, the 32-wide bodies' value.  The 64-key body reads -delta from the
+      statistics (q:187, q:804: exact) into its accumulator (k:506): the same.
+  The clamp.  The bias words are clamped in their packed form in front of their MFMAs (bias_mfma_limit c:163-170, q:302; bias_clamp_frag c:174-177,
+      q:402, q:409, q:613-616; k:528, k:534, k:790-798): -inf and finfo.min become about -2e38 min(1, |scale|), times invf a finite S' of about
+      -2e38 / (of the scale's sign), times c2 far below the exponent range: p = exp2 = exactly 0 in both iterations, dS = 0 * dP' with dP' finite:
+      an exact 0.  The restatement calls an entry <= -1e38 masked; the bound there is 0.
+  dbias.  dS is rounded to the dtype per batch element (pack8 q:481, asm_cvt_pk q:533): u_T, and 2^-25 absolute in fp16.  The four waves' words
+      pass through LDS bit for bit (q:433-438, q:579) and are summed by two selector MFMAs per accumulator, 1.0 x word (q:452-457, q:567-570): at
+      most four terms, an MFMA addition 2 u.  "dq-kernel": one rounding (pack2, q:445).  "dq-kernel+partials": the fp32 sums leave as slabs (q:442-443)
+      and dbias_partial_reduce_kernel adds them in slab order (q:823-836: u each) and rounds once (q:836).  Both: gamma_2(nsum) over the nsum = B
+      terms of an entry, then u_T -- the staged route's shape with the MFMA's 2 u:
+          err_dbias = (1 + u_T) (e_dS T + c_A TA + c_B TB + D u TD) + u_T T + gamma_2(B) (1 + u_T) T + [fp16: B 2^-25]
+  Exact zeros, T = 0.  Above the causal diagonal inside a visited step: the C operand is -inf of the scale's sign (q:321, q:374-381), exp2 gives 0;
+      the general iteration also selects 0 (q:476-479).  Steps a row block never visits: "dq-kernel" stores zeros (q:705-711), the partial
+      reduction skips the slabs where `(n0 / 32) * 32 >= min(N, 64 rb + 64 + P)` (q:816-822: the unpadded sweep, for P of either sign; n_end <= 0
+      skips the whole block) and writes 0.  The steps a causal sweep is padded with (q:124) lie above the diagonal: masked like any other.  Dead rows
+      and rows of an idle wave: nL2 = -inf (q:182), p = 0 whatever S' holds; an idle wave (B % 4 != 0) runs on the last batch element (q:106-107),
+      adds zeros to the batch sum and stores no dq, delta or statistics (q:180, q:183, q:717).
+  Contractions and outputs.  dQ^T += K^T dS^T over the N keys of the sweep, the padded steps adding zeros (q:425, q:545): gamma_2(N + 1); * scale and
+      one rounding (q:728-729), whole rows through the wave's ring area bit for bit (q:730-738).  The DENSE 64-key body: as the non-dense one, its
+      outputs through the drained ring (k:1039-1050) bit for bit.  c_dq, c_dk, c_dv as above with e_dS and the body's c_A, c_B.
+The step classification of the dense bodies.  `steps_qdb64` restates q:120-124 and q:674-694 per 64-row block (the four waves share their rows):
+trips of four steps run the pipelined iteration -- unmasked while the step AFTER the trip is visible to all 64 rows (an iteration forms the next
+step's scores, q:681), masked afterwards (q:685) --, a key tail and whatever does not fill an aligned trip the general one (q:690); a causal sweep is
+padded to whole trips where `((nt + 3) & ~3) * 32 <= N` (q:124), and a block whose sweep ends at or before key 0 has no step.  `steps_kv64(dense=True)`
+is the loop of the bodies without a table (k:909-927).
 The step classification (`steps_kv64`, `steps_q64`) restates k:891-967 and k:1700-1753 on the host: which steps run in aligned trips of
 four (far-positive, far-negative, band, on the causal diagonal) and which run the general iteration.  The case list asserts its coverage
 with it, the emulation takes from it which dS feeds the far bins rounded, the mutants where a trip, a remainder or a pair's half lies.
@@ -111,6 +164,7 @@ diagonal or under a masking bias entry, a diagonal no visible score lies on) the
 """
 import math
 
+import numpy as np
 import torch
 
 from attn_fwd_fp64 import _bias_block, _visible, seam_key, U_T, U32, E_EXP, LOG2E, LN2, MASKED
@@ -119,6 +173,7 @@ from rowwise_fp64 import ulp
 DEAD_LSE = -1.0e30          # kDeadRowLse
 OUTPUTS = ("dq", "dk", "dv", "dbias", "drpe1d", "drpe_table")
 DBIAS_ROUTES = ("direct", "staged", "inkernel")
+QDB_ROUTES = ("dq-kernel", "dq-kernel+partials")   # (the dQ + dBias body: the final 16-bit tensor / fp32 slabs per group of four batch elements)
 
 
 def _gamma(n, k=1):
@@ -133,7 +188,7 @@ def _knobs(B, H, M, N, D, R, causal, scale, bias, rpe1d, bucket):
                 wq=torch.ones(N, dtype=torch.float64), wr=torch.ones(M, dtype=torch.float64), delta_shift=0, delta_true=False,
                 own_softmax=False, dk_noscale=False, dq_scale2=False, db_drop=False, db_dup=False, db_above=False, db_row_shift=0,
                 g_shift=0, g_far_band=False, g_head_shift=0, bucket_shift=0, ragged=False, lse_scale2=False, g_w=None, g_far_add=None, g_sign=1,
-                delta_over=None)
+                delta_over=None, bias_key_shift=0, sel_hi_only=False, db_w=None, db_keyswap=False, pad_unmasked=False, noclamp=False)
 
 
 def _bias_all(c, bias, rpe1d, R, M, N):
@@ -144,10 +199,99 @@ def _bias_all(c, bias, rpe1d, R, M, N):
     return torch.stack([torch.stack([_bias_block(dict(c, b=b, h=h), bias, rpe1d, R, M, N) for h in range(c["H"])]) for b in range(nb)])
 
 
+def split16_of(scale, dtype):
+    """`split16` (attn_common.h:97) of invf = 1.f / scale (q:304) on the host: dict(invf, hi, lo -- the two 16-bit selector terms as
+    exact doubles --, rel = |invf - (hi + lo)| / |invf|, exact in fp64 -- every quantity has at most 24 bits --, one = the ONE
+    instantiations' condition, attn_common.h:123).  bf16 truncates both terms, fp16 rounds them to nearest."""
+    invf = np.float32(1.0) / np.float32(scale)
+    if dtype == torch.bfloat16:
+        trunc = lambda x: (np.array([x], dtype=np.float32).view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)[0]
+        hi = trunc(invf)
+        lo = trunc(np.float32(invf - hi))
+    else:
+        with np.errstate(over="ignore"):
+            hi = np.float32(np.float16(invf))
+            lo = np.float32(np.float16(np.float32(invf - hi)))
+    hi, lo, x = float(hi), float(lo), float(invf)
+    return dict(invf=x, hi=hi, lo=lo, rel=abs(x - (hi + lo)) / abs(x), one=lo == 0.0)
+
+
+def bias_clamp_limit(scale, dtype):
+    """the most negative bias the matrix pipe is shown (bias_mfma_limit, attn_common.h:163-170): bf16 -min(2e38, 2e38 |scale|) truncated
+    to bf16, fp16 finfo.min"""
+    if dtype != torch.bfloat16:
+        return -65504.0
+    x = np.array([-min(np.float32(2.0e38), np.float32(2.0e38) * np.float32(abs(scale)))], dtype=np.float32)
+    return float((x.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)[0])
+
+
+def keyswap_index(N):
+    """key order with the chunks {4-7} and {8-11} of every whole 16-key group exchanged: the interleave of the dS exchange (q:322-325) undone wrongly"""
+    idx = torch.arange(N)
+    for g in range(0, N - 15, 16):
+        idx[g + 4:g + 8], idx[g + 8:g + 12] = torch.arange(g + 8, g + 12), torch.arange(g + 4, g + 8)
+    return idx
+
+
+def steps_qdb64(M, N, causal):
+    """The dQ + dBias body's own walk over its 32-key steps (attn_bwd_qdb64.h:120-124, :674-694), per 64-row block -- all four waves of a
+    workgroup share their rows, so there is one walk per block: dict(m0, nt0 = the steps below the diagonal, nt = those it runs (causal:
+    padded to whole trips where `((nt0 + 3) & ~3) * 32 <= N`), padded, refused (nt0 is no multiple of 4 and the condition fails), segs =
+    [(step, kind)] with kind in trip (unmasked, pipelined) / mtrip (the mask in the C operand, pipelined) / general, tail (a key tail))."""
+    P, out = N - M, []
+    for m0 in range(0, M, 64):
+        n_end = min(N, m0 + 64 + P) if causal else N                     # (q:119-120)
+        nt0 = (n_end + 31) // 32 if n_end > 0 else 0                     # (q:121)
+        nt, up = nt0, (nt0 + 3) & ~3
+        if causal and nt0 > 0 and up * 32 <= N:                          # (q:124)
+            nt = up
+        full = lambda u: u * 32 + 32 <= N                                # (q:675)
+        vis = lambda u: not causal or u * 32 + 31 <= m0 + P              # (q:676)
+        segs, t = [], 0
+        while t < nt:
+            while t % 4 == 0 and t + 4 <= nt and full(t + 3) and vis(t + 4):       # (q:681)
+                segs.append((t, "trip"))
+                t += 4
+            while t % 4 == 0 and t + 4 <= nt and full(t + 3) and not vis(t + 4):   # (q:685)
+                segs.append((t, "mtrip"))
+                t += 4
+            if t < nt and not (t % 4 == 0 and t + 4 <= nt and full(t + 3)):        # (q:690)
+                segs.append((t, "general"))
+                t += 1
+        out.append(dict(m0=m0, nt0=nt0, nt=nt, padded=nt > nt0, refused=bool(causal and nt0 > 0 and nt0 % 4 != 0 and nt == nt0), segs=segs,
+                        tail=nt > 0 and nt * 32 > N))
+    return out
+
+
+KINDS_QDB = ("unmasked trip", "masked trip", "general step", "key-tail step", "remainder behind the last trip", "padded causal trip",
+             "padding refused", "row block without steps")
+
+
+def kinds_of_qdb(blocks):
+    """which of KINDS_QDB occur in a `steps_qdb64` walk"""
+    got = set()
+    for b in blocks:
+        if b["nt"] == 0:
+            got.add("row block without steps")
+        if b["padded"]:
+            got.add("padded causal trip")
+        if b["refused"]:
+            got.add("padding refused")
+        if b["tail"]:
+            got.add("key-tail step")
+        trips = [t for t, k in b["segs"] if k != "general"]
+        for t, k in b["segs"]:
+            got.add({"trip": "unmasked trip", "mtrip": "masked trip", "general": "general step"}[k])
+            if k == "general" and trips and t > max(trips):
+                got.add("remainder behind the last trip")
+    return got
+
+
 def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R=0, bucket=None, num_buckets=0, mutant=None):
     """q, o, do (B, H, M, D), k / v (B, H, N, D) in bf16 / fp16 (any strides); lse (B, H, M) fp32; bias dense (B|1, H|1, M, N) or None; rpe1d
     (H, 2R + 1) fp32 or None; bucket (2R + 1) int ids or None.  Returns a dict: for X in dq, dk, dv and, where they exist, dbias, drpe1d,
-    drpe_table: X (fp64), T_X, TA_X, TD_X (see the module docstring; TA_dv / TD_dv: dv has no delta, TD_dv = 0); S_dv, S_dk, S_dq the fp16
+    drpe_table: X (fp64), T_X, TA_X, TD_X (see the module docstring; TA_dv / TD_dv: dv has no delta, TD_dv = 0); with a dense bias also TB_X of dq, dk, dv,
+    dbias, and sel_rel / sel_one (`split16_of` of the scale in q's dtype); S_dv, S_dk, S_dq the fp16
     absolute-term sums; nsum (dbias) and n_drpe1d / n_drpe_table term counts; TF_ / nF_ of drpe1d and the table: T and the count restricted to the two far bins; per row (B, H, M): smag, bmag, lse_abs, smax / smin (the
     extremes of s - lse over the live keys, 0 on rows without one), dsmax (the largest |dS_ij|), dead; applied (the mutant changed something
     a correct kernel computes)."""
@@ -162,10 +306,21 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
     qd, kd, vd, od, dod = (t.double() for t in (q, k, v, o, do))
     kt, vt = kd.transpose(-1, -2), vd.transpose(-1, -2)
     vis = _visible(c, M, N)
+    if c["pad_unmasked"]:                                               # (the steps a causal row block is padded with, q:124, seen unmasked)
+        vis = vis.clone()
+        for blk in steps_qdb64(M, N, True):
+            if blk["padded"]:
+                vis[blk["m0"]:blk["m0"] + 64, 32 * blk["nt0"]:32 * blk["nt"]] = True
     qk = (qd @ kt) * scale
     bt = _bias_all(c, bias, rpe1d, R, M, N)
-    s = qk if bt is None else qk + bt
+    if bias is not None and c["bias_key_shift"]:
+        bt = bt[..., (torch.arange(N) + c["bias_key_shift"]).clamp(max=N - 1)]
     masked = ((bt <= MASKED) & vis) if bias is not None else torch.zeros(1, 1, M, N, dtype=torch.bool)
+    sel = split16_of(scale, q.dtype)
+    bts = bt
+    if bias is not None and c["sel_hi_only"]:                           # (bias * hi in place of bias * (hi + lo): q:314)
+        bts = torch.where(bt <= MASKED, bt, bt * (sel["hi"] / sel["invf"]))
+    s = qk if bt is None else qk + bts
     L = lse.double()
     dead = ~(L >= DEAD_LSE)
     ok = vis & ~masked & ~dead[..., None]                               # (B, H, M, N): the scores that carry weight
@@ -177,6 +332,15 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
     L0 = torch.where(dead, torch.zeros_like(L), Lu)
     x = torch.where(ok, s - L0[..., None], ninf)
     p = torch.exp(x)
+    poison = None
+    if bias is not None and c["noclamp"]:                               # (-inf * 0 = NaN for the other rows of the 32-row operand: c:153-157)
+        isninf = (bt == -math.inf).expand(B, H, M, N)
+        poison = torch.zeros_like(isninf)
+        for r0 in range(0, M, 32):
+            blk = isninf[:, :, r0:r0 + 32].long()
+            poison[:, :, r0:r0 + 32] = (blk.sum(2, keepdim=True) - blk) > 0
+        poison = poison & vis
+        p = torch.where(poison, torch.full_like(p, math.nan), p)
     if c["delta_true"]:
         od_true = torch.nan_to_num(torch.softmax(torch.where(vis & ~masked, s, ninf), -1)) @ vd
         delta = (od_true * dod).sum(-1)
@@ -195,7 +359,12 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
     A = (smag + bmag + L0.abs()) * LOG2E
     pd = p * (od.abs() * dod.abs()).sum(-1)[..., None]
     mags = (a, a * A[..., None], pd)                                    # -> T, TA, TD
-    out = dict(smag=smag, bmag=bmag, lse_abs=L0.abs(), dead=dead, applied=False)
+    tags = ("T", "TA", "TD")
+    if bias is not None:                                                # -> TB: a_ij |bias_ij|, the carrier of the selector's residual
+        babs = torch.where(ok, bt.abs().expand_as(s), zero)             # (a masking entry carries no weight: 0, not 0 * inf)
+        mags = mags + (torch.where(ok, a, zero) * babs,)
+        tags = tags + ("TB",)
+    out = dict(smag=smag, bmag=bmag, lse_abs=L0.abs(), dead=dead, applied=False, sel_rel=sel["rel"], sel_one=sel["one"])
     anyok = ok.any(-1)
     out["smax"] = torch.where(anyok, x.amax(-1), torch.zeros_like(L)) if N else torch.zeros_like(L)
     out["smin"] = torch.where(anyok, torch.where(ok, x, -ninf).amin(-1), torch.zeros_like(L)) if N else torch.zeros_like(L)
@@ -207,12 +376,14 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
     out["T_dv"] = p.transpose(-1, -2) @ dod.abs()
     out["TA_dv"] = (p * A[..., None]).transpose(-1, -2) @ dod.abs()
     out["TD_dv"] = torch.zeros_like(out["T_dv"])
+    if bias is not None:
+        out["TB_dv"] = (torch.where(ok, p, zero) * babs).transpose(-1, -2) @ dod.abs()   # (p_ij |bias_ij| |do_id|)
     out["S_dv"] = okf.transpose(-1, -2) @ dod.abs()
     out["dk"] = ((dS * wr).transpose(-1, -2) @ qd) * (1.0 if c["dk_noscale"] else scale)
     out["dq"] = ((dS * wq) @ kd) * (scale * scale if c["dq_scale2"] else scale)
     if c["ragged"] and M >= 2:
         out["dq"][:, :, M - 1] = out["dq"][:, :, M - 2]
-    for tag, m in zip(("T", "TA", "TD"), mags):
+    for tag, m in zip(tags, mags):
         out[tag + "_dk"] = (m.transpose(-1, -2) @ qd.abs()) * abs(scale)
         out[tag + "_dq"] = (m @ kd.abs()) * abs(scale)
     out["S_dk"] = (okf.transpose(-1, -2) @ qd.abs()) * abs(scale)
@@ -220,12 +391,14 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
     # ---- dbias ----
     if bias is not None:
         def red(t, mut=False):
-            if bias.shape[0] == 1 and B > 1:
+            if bias.shape[0] == 1 and (B > 1 or (mut and c["db_w"] is not None)):   # (B = 1: three idle waves run on the one element)
                 w = torch.ones(B, dtype=torch.float64)
                 if mut and c["db_drop"]:
                     w[B - 1] = 0
                 if mut and c["db_dup"] and B > 4:
                     w[4] = 2
+                if mut and c["db_w"] is not None:
+                    w = w * c["db_w"](B)
                 t = (t * w[:, None, None, None]).sum(0, keepdim=True)
             if bias.shape[1] == 1 and H > 1:
                 t = t.sum(1, keepdim=True)
@@ -235,8 +408,10 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
             dsb = dS[:, :, (torch.arange(M) + c["db_row_shift"]).clamp(max=M - 1)]
         if c["db_above"]:
             dsb = torch.where(vis, dsb, dP - delta[..., None])
+        if c["db_keyswap"]:                                             # (chunks {4-7} and {8-11} of every whole 16-key group: q:322-325)
+            dsb = dsb[..., keyswap_index(N)]
         out["dbias"] = red(dsb, True)
-        for tag, m in zip(("T", "TA", "TD"), mags):
+        for tag, m in zip(tags, mags):
             out[tag + "_dbias"] = red(m)
         out["nsum"] = (B if bias.shape[0] == 1 else 1) * (H if bias.shape[1] == 1 else 1)
     # ---- drpe1d, drpe_table ----
@@ -247,7 +422,7 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
         gidx = ((c["g_sign"] * rel + c["g_shift"]).clamp(-R, R) + R).reshape(-1)
         wg = (rel.abs() <= R).double() if c["g_far_band"] else torch.ones(M, N, dtype=torch.float64)
         gw = c["g_w"](B, H, M, N) if c["g_w"] is not None else None       # (B, H, M, N) weights of the dS terms in the diagonal sums
-        X = torch.stack([(dS * wg if gw is None else dS * wg * gw).sum(0)] + [m.sum(0) for m in mags])   # (4, H, M, N), summed over the batch
+        X = torch.stack([(dS * wg if gw is None else dS * wg * gw).sum(0)] + [m.sum(0) for m in mags[:3]])   # (4, H, M, N), summed over the batch
         g = torch.zeros(4, H, n1, dtype=torch.float64).index_add_(2, gidx, X.reshape(4, H, -1))
         fadd = c["g_far_add"](M, N) if c["g_far_add"] is not None else None   # ((M, N) mask, bin): these dS terms once more, into a far bin
         if fadd is not None:
@@ -286,6 +461,11 @@ def attn_bwd_ref(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R
         ch = ch or ((c["dk_noscale"] or c["dq_scale2"]) and scale != 1.0 and bool(ok0.any()))
         ch = ch or ((c["db_drop"] or c["db_dup"] or c["db_row_shift"] != 0) and bool(ok0.any()))
         ch = ch or (c["db_above"] and bool((~vis0).any()))
+        ch = ch or (c["db_w"] is not None and bool((c["db_w"](B) != 1).any()) and bool(ok0.any()))
+        ch = ch or (c["db_keyswap"] and N >= 16 and bool(ok0.any()))
+        ch = ch or (poison is not None and bool(poison.any()))
+        # (the low term matters where leaving it out moves a probability by more than four roundings of the dtype)
+        ch = ch or (c["sel_hi_only"] and bias is not None and abs(1 - sel["hi"] / sel["invf"]) * float(torch.where(ok0, bt.abs().expand_as(s), zero).max()) > 4 * U_T[q.dtype])
         ch = ch or (c["g_shift"] != 0 and bool(ok0.any())) or (c["g_head_shift"] != 0 and bool(ok0.any()))
         ch = ch or (c["g_far_band"] and bool(((torch.arange(N)[None, :] - torch.arange(M)[:, None]).abs() > R)[None, None].logical_and(ok0).any()))
         ch = ch or (c["bucket_shift"] != 0 and bool((bk != bk0).any()) and bool(ok0.any()))
@@ -329,10 +509,13 @@ def _walk(ns, far, band, masked, mk=None):
     return segs
 
 
-def steps_kv64(M, N, R, causal, rpe, half=False):
+def steps_kv64(M, N, R, causal, rpe, half=False, dense=False):
     """The dK/dV body's own classification of its 32-row query steps (attn_bwd64.h:244-256, :891-967), restated on the host: one entry per
     (key block, wave, pair): dict(kw0, mt0, ns, segs).  BNK = 128 keys per workgroup in the half-length form (two pairs, each half of the
-    steps), 256 otherwise; a wave owns the 64 keys from kw0."""
+    steps), 256 otherwise; a wave owns the 64 keys from kw0.  `dense`: the DENSE 256-key body -- the loop of the bodies without a table
+    (k:909-927: trips on the causal diagonal with the mask in the C operand, then the all-visible ones, anything else general), its
+    pipelined iterations with eight (ONE: four) more score MFMAs (k:653-656); it has no half-length form (k:67)."""
+    assert not (dense and (rpe or half))
     P, out = N - M, []
     ctab = rpe and causal and -R <= P < R                                # (k:134: the table carries the mask)
     bnk = 128 if half else 256
@@ -411,8 +594,12 @@ def layout_of(bodies, M, N, R, causal, rpe):
     """the step walks of the 64-wide bodies a case runs: dict(kv=[...] or None, q=[...] or None, kvh=[...] (the half-length walks of a mixed
     launch) or None)"""
     kv = bodies.get("dkdv", "")
-    lay = dict(kv=None, kvh=None, q=None)
-    if kv == "64key" or kv.startswith("64key-mixed"):
+    lay = dict(kv=None, kvh=None, q=None, qdb=None)
+    if bodies.get("dq") == "64row-batch4":
+        lay["qdb"] = steps_qdb64(M, N, causal)
+    if kv == "64key" and "dbias" in bodies:
+        lay["kv"] = steps_kv64(M, N, 0, causal, False, dense=True)
+    elif kv == "64key" or kv.startswith("64key-mixed"):
         lay["kv"] = steps_kv64(M, N, R, causal, rpe)
     if kv == "64key-half" or kv.startswith("64key-mixed"):
         lay["kvh"] = steps_kv64(M, N, R, causal, rpe, half=True)
@@ -476,21 +663,33 @@ def attn_bwd_bound(ref, dtype, D, bodies, N, M):
     """{output: bound tensor} for an `attn_bwd_ref` result computed by the bodies `bodies` names (the dq=, dkdv=, fused=, dbias=, qdiag=,
     dtable= fields of fat5_attn_describe, as a dict) at head dimension D"""
     dqb, kvb, qdiag = bodies.get("dq"), bodies.get("dkdv", ""), bodies.get("qdiag", "0")
-    kv64, q64 = kvb == "64key" or kvb == "64key-half" or kvb.startswith("64key-mixed:"), dqb == "64row"
-    if dqb not in ("32row", "64row") or not (kvb == "32key" or kv64):
-        raise NotImplementedError(f"not covered: {bodies} (the dense 64-wide bodies; see the module docstring)")
-    if (kv64 or q64) and ("dbias" in ref or D != 64):
-        raise NotImplementedError(f"not covered: {bodies} with a dense bias (the DENSE form of the 64-key body, dq-kernel routes; see the module docstring)")
+    kv64, q64, qdb = kvb == "64key" or kvb == "64key-half" or kvb.startswith("64key-mixed:"), dqb == "64row", dqb == "64row-batch4"
+    dense, route = "dbias" in ref, bodies.get("dbias")
+    if dqb not in ("32row", "64row", "64row-batch4") or not (kvb == "32key" or kv64):
+        raise NotImplementedError(f"not covered: {bodies}")
+    if (kv64 or q64 or qdb) and D != 64:
+        raise NotImplementedError(f"not covered: {bodies} at D = {D} (the 64-wide bodies exist at D = 64 only)")
+    if dense and (q64 or (kv64 and kvb != "64key")):   # (the DENSE 64-key body has the 256-key form only, k:67; the 64-row dQ body no dense form, k:1143)
+        raise NotImplementedError(f"not covered: {bodies} with a dense bias: no such body")
+    if qdb != (route in QDB_ROUTES) or (qdb and not dense):   # (dq-kernel routes are the batch4 body's own stores, q:440-462)
+        raise NotImplementedError(f"not covered: {bodies}: the routes {QDB_ROUTES} and dq=64row-batch4 exist together only")
+    if bodies.get("fused") == "1" and dense and (kv64 or qdb) and not (kv64 and qdb):   # (attn_bwd_dfused64_kernel holds both bodies, q:754-766)
+        raise NotImplementedError(f"not covered: {bodies}")
     if qdiag != "0" and not (q64 and kv64):   # (QDG exists in the 64-row dQ body beside the NODIAG 64-key one only: k:104-105, k:1133)
         raise NotImplementedError(f"not covered: {bodies}")
     fp16 = dtype == torch.float16
     uT = U_T[dtype]
     kap = LN2 * (2 * D + 9) * U32
+    dkv, dq_ = dense and kv64, qdb                                     # which side runs a dense 64-wide body
+    kapd = LN2 * (2 * D + 10) * U32                                    # (its two more MFMA additions and the rounding of 1 / scale: "The dense 64-wide bodies")
+    rel = ref.get("sel_rel", 0.0) if (dkv or dq_) else 0.0             # the selector's relative residual: exact, per (scale, dtype); 0 in the ONE kernels
     Amax = max(float((ref["smag"] + ref["bmag"] + ref["lse_abs"]).max()) * LOG2E, 0.0) if ref["smag"].numel() else 0.0
-    assert kap * Amax < 2.0 ** -7, "scores beyond the range the derivation of e_p covers"
+    bmax = float(ref["bmag"].max()) if ref["bmag"].numel() else 0.0
+    assert (kapd if (dkv or dq_) else kap) * Amax + rel * bmax < 2.0 ** -7, "scores beyond the range the derivation of e_p covers"
     assert float(ref["smin"].min() if ref["smin"].numel() else 0.0) * LOG2E > -120.0, "a weight would be flushed by v_exp_f32: outside the derivation"
     assert not fp16 or float(ref["dsmax"].max() if ref["dsmax"].numel() else 0.0) < 60000.0, "dS would overflow fp16: outside the derivation"
-    cA = kap * (1 + E_EXP) / (1 - 2.0 ** -7)
+    lin = (1 + E_EXP) / (1 - 2.0 ** -7)
+    cA, cAd, cB = kap * lin, kapd * lin, rel * lin
     e_ds = E_EXP + (2 * D + 1) * U32
     e_ds_q64 = E_EXP + (2 * D + 5) * U32        # (-delta as three 16-bit pieces through one more MFMA in the general steps: k:1255-1260, k:1454)
     hand = U32 if (kvb == "64key-half" or kvb.startswith("64key-mixed:")) else 0.0   # (the second pair's dK^T / dV^T added in fp32: k:1033-1034)
@@ -499,35 +698,43 @@ def attn_bwd_bound(ref, dtype, D, bodies, N, M):
         b = err + 0.5 * ulp(ref[x].abs() + err, dtype)
         return torch.where(ref["T_" + x] == 0, torch.zeros_like(b), b)
 
+    def comp(x, wide):   # the companions of output x: c_A TA + c_B TB + D u TD, with the constants of the body that forms x's probabilities
+        t = (cAd if wide else cA) * ref["TA_" + x] + D * U32 * ref["TD_" + x]
+        return t + cB * ref["TB_" + x] if (wide and rel) else t
+
     out = {}
-    for x, n, e in (("dv", M, E_EXP + hand), ("dk", M, e_ds + U32 + hand), ("dq", N, (e_ds_q64 if q64 else e_ds) + U32)):
+    for x, n, e, wide in (("dv", M, E_EXP + hand, dkv), ("dk", M, e_ds + U32 + hand, dkv), ("dq", N, (e_ds_q64 if q64 else e_ds) + U32, dq_)):
         cT = (1 + uT) * (1 + e + _gamma(n + 1, 2)) - 1
-        err = cT * ref["T_" + x] + (1 + uT) * (cA * ref["TA_" + x] + D * U32 * ref["TD_" + x])
+        err = cT * ref["T_" + x] + (1 + uT) * comp(x, wide)
         if fp16:
             err = err + (2.0 if (x == "dq" and q64) else 1.0) * 2.0 ** -25 * ref["S_" + x]   # (64row: the last 16-bit piece of -delta is absolute too, k:1259)
         out[x] = close(x, err)
-    if "dbias" in ref:
-        route = bodies.get("dbias")
-        if route not in DBIAS_ROUTES:
+    if dense:
+        if route not in DBIAS_ROUTES + QDB_ROUTES:
             raise NotImplementedError(f"not covered: dbias={route}")
         T = ref["T_dbias"]
-        err = e_ds * T + cA * ref["TA_dbias"] + D * U32 * ref["TD_dbias"]
+        err = e_ds * T + comp("dbias", dq_)
         if route != "direct":
+            # staged / inkernel: fp32 additions of the nsum rounded dS (r:53-72, d:226).  dq-kernel: two selector MFMAs sum the four waves'
+            # rounded words (q:452-457, an MFMA addition 2 u), + partials: the slabs in slab order (q:823-836, u each): gamma_2(nsum) covers both
             ns = ref["nsum"]
-            err = (1 + uT) * err + uT * T + _gamma(ns) * (1 + uT) * T + (ns * 2.0 ** -25 if fp16 else 0.0)
+            err = (1 + uT) * err + uT * T + _gamma(ns, 2 if dq_ else 1) * (1 + uT) * T + (ns * 2.0 ** -25 if fp16 else 0.0)
         out["dbias"] = close("dbias", err)
     out.update(drpe_bound(ref, dtype, D, bodies))
     return out
 
 
 def emulate(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R=0, bucket=None, num_buckets=0, dbias_route="direct", stats=None,
-            rounded_sums=None):
+            rounded_sums=None, dense64=None):
     """What the bodies do arithmetically, in float32 torch ops (not in their summation order): scores, p, delta, dP and dS in fp32;
     P and dS rounded to the dtype before the three contractions; dbias from the rounded dS (summed in fp32 and rounded once where the
     route reduces); the diagonal sums from the fp32 dS; one output rounding.  Returns {output: tensor}.
     The 64-wide setting: `stats` = "stat2" (the score accumulator starts at the fp32 quotient -L / scale, k:1250) or "self" (at L times the
     fp32 reciprocal -1 / scale, k:317, k:339), and the exponent is exp2(fma-like (q k - L/scale) (scale log2e) + bias log2e) as in k:819-820;
-    `rounded_sums` = an (M, N) bool mask of the scores whose dS enters the diagonal sums rounded to the dtype (`far_rounded_mask`)."""
+    `rounded_sums` = an (M, N) bool mask of the scores whose dS enters the diagonal sums rounded to the dtype (`far_rounded_mask`).
+    The dense 64-wide setting: `dense64` = the sides that run a dense 64-wide body, a subset of ("q", "kv"): "q" forms dq and dbias
+    (the rounded dS summed in fp32, rounded once) from exp2(fma(S', c2, -L log2e)), "kv" forms dk and dv from exp2((S' - L / scale) c2),
+    with S' = q k + bias hi + bias lo in fp32, the bias clamped as `bias_clamp_frag` does."""
     B, H, M, D = q.shape
     N = k.shape[2]
     dt = q.dtype
@@ -557,16 +764,28 @@ def emulate(q, k, v, o, lse, do, sm_scale, causal, bias=None, rpe1d=None, R=0, b
             x2 = x2 + (f(rpe1d) * torch.tensor(LOG2E, dtype=torch.float32))[:, rel][None]
         p = torch.where(ok, torch.exp2(x2), torch.zeros(()))
     delta = (f(o) * f(do)).sum(-1, keepdim=True)
-    ds = p * (f(do) @ f(v).transpose(-1, -2) - delta)
-    pr, dsr = f(p.to(dt)), f(ds.to(dt))
-    out = dict(dv=(pr.transpose(-1, -2) @ f(do)).to(dt), dk=((dsr.transpose(-1, -2) @ f(q)) * scale).to(dt), dq=((dsr @ f(k)) * scale).to(dt))
+    dpd = f(do) @ f(v).transpose(-1, -2) - delta
+    pq = pkv = p
+    if dense64:   # the bias through the selector: S' = q k + clamp(bias) hi + clamp(bias) lo in fp32 (q:396-411, k:522-537)
+        sel = split16_of(float(scale), dt)
+        bc = f(bias).clamp(min=bias_clamp_limit(float(scale), dt))
+        sp = f(q) @ f(k).transpose(-1, -2) + bc * torch.tensor(sel["hi"], dtype=torch.float32) + bc * torch.tensor(sel["lo"], dtype=torch.float32)
+        L0 = torch.where(L >= DEAD_LSE, L, torch.zeros(()))
+        c2 = scale * torch.tensor(LOG2E, dtype=torch.float32)
+        if "q" in dense64:    # exp2(fma(S', c2, -L log2e))  (q:473, q:528)
+            pq = torch.where(ok, torch.exp2(sp * c2 + (-L0 * torch.tensor(LOG2E, dtype=torch.float32))[..., None]), torch.zeros(()))
+        if "kv" in dense64:   # S' starts at the one fp32 quotient -L / scale (q:186, q:803, b:120); x = S' c2 (k:569, k:820 with cst = 0)
+            pkv = torch.where(ok, torch.exp2((sp + (-(L0 / scale))[..., None]) * c2), torch.zeros(()))
+    ds, dskv = pq * dpd, pkv * dpd
+    pr, dsr, dskvr = f(pkv.to(dt)), f(ds.to(dt)), f(dskv.to(dt))
+    out = dict(dv=(pr.transpose(-1, -2) @ f(do)).to(dt), dk=((dskvr.transpose(-1, -2) @ f(q)) * scale).to(dt), dq=((dsr @ f(k)) * scale).to(dt))
     if bias is not None:
         t = dsr
         if bias.shape[0] == 1 and B > 1:
             t = t.sum(0, keepdim=True)
         if bias.shape[1] == 1 and H > 1:
             t = t.sum(1, keepdim=True)
-        assert dbias_route in DBIAS_ROUTES and (dbias_route != "direct" or t is dsr)
+        assert dbias_route in DBIAS_ROUTES + QDB_ROUTES and (dbias_route != "direct" or t is dsr)
         out["dbias"] = t.to(dt)
     if rpe1d is not None:
         n1 = 2 * R + 1
@@ -805,4 +1024,76 @@ MUTANTS64 = {
     "a far bin with the band's blocks added": _m_far_band,
     "the mirrored diagonal index with the wrong sign": lambda L: _set("g_sign", -1) if (L["bodies"].get("qdiag") == "1" and L.get("drpe")) else None,
     "the partial row behind a 256-key workgroup of a mixed launch counted twice": _m_mixed_row,
+}
+
+
+# Defects only the DENSE 64-wide bodies can have; as MUTANTS64, each takes the case's layout and returns a mutant or None.
+def _qdb(L):
+    return L["bodies"].get("dq") == "64row-batch4"
+
+
+def _dense64(L):
+    return _qdb(L) or (L["bodies"].get("dkdv") == "64key" and "dbias" in L["bodies"])
+
+
+def _batch_w(pick):
+    def f(L):
+        if not _qdb(L):
+            return None
+        w = pick(L["B"])
+        return None if w is None else _set("db_w", lambda c: (lambda B: w))
+    return f
+
+
+def _w_idle(B):      # the idle waves of the last group run on the last batch element (q:106-107): it counts again
+    if B % 4 == 0:
+        return None
+    w = torch.ones(B, dtype=torch.float64)
+    w[B - 1] = 2.0
+    return w
+
+
+def _w_slab(g, value):
+    def f(B):
+        if B <= 4 or 4 * g >= B:
+            return None
+        w = torch.ones(B, dtype=torch.float64)
+        w[4 * g:4 * g + 4] = value
+        return w
+    return f
+
+
+def _w_elem(which):   # one batch element at the edge of a group left out of the sum
+    def f(B):
+        b = {"first": 4 * ((B - 1) // 4), "last": min(3, B - 1), "lastgroup": B - 1}[which]
+        w = torch.ones(B, dtype=torch.float64)
+        w[b] = 0.0
+        return w if B > 1 else None
+    return f
+
+
+MUTANTS_DENSE64 = {
+    "the selector's low term dropped": lambda L: _set("sel_hi_only", True) if _dense64(L) else None,
+    "an idle wave that contributes": _batch_w(_w_idle),
+    "the last slab left out of the partial reduction": _batch_w(lambda B: _w_slab((B - 1) // 4, 0.0)(B)),
+    "the first slab added twice": _batch_w(_w_slab(0, 2.0)),
+    "dbias without the first element of the last batch group": _batch_w(_w_elem("first")),
+    "dbias without the last element of the first batch group": _batch_w(_w_elem("last")),
+    "dbias key chunks 4-7 and 8-11 exchanged": lambda L: _set("db_keyswap", True, lambda c: c["N"] >= 16) if _qdb(L) else None,
+    "the bias tile of the neighbouring 32-key step": lambda L: _set("bias_key_shift", 32, lambda c: c["N"] > 32) if _dense64(L) else None,
+    "the bias tile of the next 64-row block": lambda L: _set("row_shift", 64, lambda c: c["M"] > 64) if _dense64(L) else None,
+    "a padded causal step that is not masked": lambda L: (_set("pad_unmasked", True) if (_qdb(L) and any(b["padded"] for b in L["walks"]["qdb"])) else None),
+    "the clamp in front of the bias MFMAs missing": lambda L: _set("noclamp", True) if _dense64(L) else None,
+    "dQ without one 32-key step of a trip": lambda L: (_keys(32 * (_first(L["walks"]["qdb"], ("trip", "mtrip"))[1] + 2), 32 * (_first(L["walks"]["qdb"], ("trip", "mtrip"))[1] + 3), 0.0)
+                                                      if (_qdb(L) and _first(L["walks"]["qdb"], ("trip", "mtrip"))) else None),
+    # one key / row at a boosted seam: the second step's first key, a trip's (128), a 256-key workgroup's; the second step's first row, a 64-row block's, a trip's
+    "dQ without key 32": lambda L: _keys(32, 33, 0.0) if _dense64(L) else None,
+    "dQ without key 128": lambda L: _keys(128, 129, 0.0) if _dense64(L) else None,
+    "dQ without key 256": lambda L: _keys(256, 257, 0.0) if _dense64(L) else None,
+    "dK/dV without query row 32": lambda L: _rows(32, 33, 0.0) if _dense64(L) else None,
+    "dK/dV without query row 64": lambda L: _rows(64, 65, 0.0) if _dense64(L) else None,
+    "dK/dV without query row 128": lambda L: _rows(128, 129, 0.0) if _dense64(L) else None,
+    "dK/dV without the last step of a trip": lambda L: _m_trip_last(L) if _dense64(L) else None,
+    "dK/dV without the remainder steps": lambda L: _m_remainder(L) if _dense64(L) else None,
+    "-L/scale formed with the scale instead of its reciprocal": lambda L: _set("lse_scale2", True) if (_dense64(L) and L["walks"]["kv"]) else None,
 }

@@ -15,7 +15,12 @@
     values, the far bins of the pipelined trips from the rounded dS); and twelve more mutants break what only these bodies have (a trip's last
     step, the remainder, the second pair's half, the hand-over, a key step of the dQ trips, the key tail, the 8-row statistic groups, 1 / scale,
     the far bins, the mirrored diagonal index, the partial rows of a mixed launch).
-The dense 64-wide bodies are not covered (tests/attn_bwd_fp64.py).
+  * for the dense 64-wide cases (dq=64row-batch4, the DENSE 64-key body, the dense one-launch form): the restatement of split16 on the host agrees with
+    hand-checked splits; `steps_qdb64` and the dense setting of `steps_kv64` agree with hand-worked examples and find every kind of step in the case list
+    (padded causal trips, a refused padding and row blocks without a step included); `emulate` runs in its dense setting (the bias through the two-term
+    selector in fp32, -L through the FMA or as the start value, dbias from the rounded dS summed in fp32); and the mutants of MUTANTS_DENSE64 break what
+    only these bodies have (the selector's low term, an idle wave, a slab, a batch element at a group's edge, the key interleave of the dbias store, the
+    bias tile's step or row block, the mask of a padded step, the clamp in front of the bias MFMAs).
 """
 import functools
 
@@ -28,7 +33,7 @@ import oracle
 from test_attn_bwd_fp64_gpu import CASES, inputs, reference, describe, compared
 
 IDS = [c["id"] for c in CASES]
-DETECTED = {name: {} for name in list(G.MUTANTS) + list(G.MUTANTS64)}   # mutant -> {case id: caught} over the cases where it applied
+DETECTED = {name: {} for name in list(G.MUTANTS) + list(G.MUTANTS64) + list(G.MUTANTS_DENSE64)}   # mutant -> {case id: caught} over the cases where it applied
 EMU = {}                                      # group -> {output: [worst ratio of `emulate`, its case]}
 
 # (mutant, case id): why the bound cannot see this defect on this case.  Nothing else is excused.
@@ -144,7 +149,7 @@ def _rpe(case):
 
 def _layout(case):
     """what the mutants of the 64-wide bodies need of a case: its bodies and their step walks"""
-    return dict(bodies=case["bodies"], walks=G.layout_of(case["bodies"], case["M"], case["N"], case["R"], case["causal"], _rpe(case)), B=case["B"], H=case["H"],
+    return dict(bodies=case["bodies"], walks=G.layout_of(case["bodies"], case["M"], case["N"], case["R"], case["causal"], _rpe(case) and not case["dense64"]), B=case["B"], H=case["H"],
                 M=case["M"], N=case["N"], R=case["R"], drpe=_rpe(case))
 
 
@@ -153,6 +158,12 @@ def _mutants(case):
     if case["wide"]:
         lay = _layout(case)
         for name, make in G.MUTANTS64.items():
+            m = make(lay)
+            if m is not None:
+                muts[name] = m
+    if case["dense64"]:
+        lay = _layout(case)
+        for name, make in G.MUTANTS_DENSE64.items():
             m = make(lay)
             if m is not None:
                 muts[name] = m
@@ -172,8 +183,10 @@ def test_the_case_list_is_what_the_issue_asks_for():
         return {c[key] for c in CASES if c["group"] == group}
     OLD = ("w2", "w4", "causal", "t5", "dbias", "pert", "fused32")
     assert {c["bodies"]["dq"] for c in CASES if c["group"] in OLD} == {"32row"} and {c["bodies"]["dkdv"] for c in CASES if c["group"] in OLD} == {"32key"}
-    assert sum(c["group"] in OLD for c in CASES) == 63 and all(c["wide"] == (c["group"] not in OLD) for c in CASES)
+    assert sum(c["group"] in OLD for c in CASES) == 63 and all(c["wide"] == (c["group"] not in OLD) for c in CASES if not c["dense64"])
+    assert sum(not c["dense64"] for c in CASES) == 151
     _the_64_wide_groups(of)
+    _the_dense_64_wide_groups(of)
     assert {1, 31, 32, 33, 64, 65, 129} <= of("w2", "M") and {1, 63, 64, 65, 127, 128, 129, 200} <= of("w2", "N")
     assert of("w2", "D") == {16, 32, 64, 128} and {1, 8, 128} <= of("w2", "R")
     assert {"none", "rpe", "11", "1h", "b1", "bh"} <= of("w2", "bias") | of("causal", "bias")
@@ -196,6 +209,63 @@ def test_the_case_list_is_what_the_issue_asks_for():
     assert any(c["bias"].endswith("-min") for c in CASES)
     assert any(c["dtype"] == torch.bfloat16 and c["D"] == 64 and c["N"] % 8 and c["bias"] == "1h" and "V_QDB64_ON" in c["bits"] for c in CASES)   # the fallback
     assert max(c["B"] * c["H"] * c["M"] * c["N"] for c in CASES) <= 700 * 700 * 12
+
+
+def _the_dense_64_wide_groups(of):
+    """the dense 64-wide groups: batch groups, rows, keys, causal sweeps, the workgroup decode, scales, bias kinds, forms -- and by the host restatement of both
+    bodies' step loops every kind of step"""
+    X = [c for c in CASES if c["dense64"]]
+    Q = [c for c in X if c["bodies"]["dq"] == "64row-batch4"]
+    K = [c for c in X if c["bodies"]["dq"] == "32row"]
+    assert 0 < len(X) <= 80 and all(c["D"] == 64 and c["N"] % 8 == 0 and c["B"] * c["H"] * c["M"] * c["N"] <= 2 ** 20 for c in X)
+    assert {c["group"] for c in X} == {"qdb", "qdbkv", "dfused", "dplain", "dkv64", "dcausal"}
+    for g, dq, kv, fused in (("qdb", "64row-batch4", "32key", "0"), ("qdbkv", "64row-batch4", "64key", "0"), ("dfused", "64row-batch4", "64key", "1"),
+                             ("dplain", "64row-batch4", "64key", "1"), ("dkv64", "32row", "64key", "0")):
+        assert {(c["bodies"]["dq"], c["bodies"]["dkdv"], c["bodies"]["fused"]) for c in X if c["group"] == g} == {(dq, kv, fused)}, g
+    assert all(c["bodies"]["dbias"] == ("dq-kernel" if c["B"] <= 4 else "dq-kernel+partials") for c in Q)
+    assert {c["bodies"]["dbias"] for c in K} == set(G.DBIAS_ROUTES) and {c["bias"][:2] for c in K} == {"1h", "bh", "11", "b1"}
+    assert {c["B"] for c in Q} >= {1, 2, 3, 4, 5, 6, 8, 9}
+    assert {c["M"] for c in Q} >= {1, 63, 64, 65, 130} and {c["N"] for c in Q} >= {8, 24, 32, 40, 128, 136, 160, 264}
+    assert {c["M"] for c in K} >= {90, 128, 160, 300} and {c["N"] for c in K} >= {64, 72, 256, 264, 520}
+    for cs, name in ((Q, "qdb"), (K, "dkv64")):
+        assert {c["N"] - c["M"] for c in cs if c["causal"]} >= {0, 1, 100, -1, -100}, name
+    for part in (False, True):   # the final tensor and the slabs, for P > 0 and P < 0
+        ps = {(c["N"] > c["M"]) - (c["N"] < c["M"]) for c in Q if c["causal"] and (c["B"] > 4) == part}
+        assert ps >= {1, -1}, part
+    assert any(c["causal"] and c["M"] == c["N"] == 256 for c in Q) and any(c["causal"] and c["M"] == c["N"] == 248 for c in Q)
+    wg = lambda c: c["H"] * ((c["B"] + 3) // 4) * ((c["M"] + 63) // 64)
+    assert any(wg(c) > 8 and wg(c) % 8 for c in Q) and any(wg(c) < 8 for c in Q)
+    assert any(c["causal"] and (c["H"] * ((c["B"] + 3) // 4)) % 8 == 0 for c in Q) and any(c["causal"] and (c["H"] * ((c["B"] + 3) // 4)) % 8 for c in Q)
+    assert {c["scale"] for c in X} == {0.125, 1.0, -0.5, 0.3, 1.3, 0.0884, -0.3}
+    for c in X:   # ONE exactly where 1 / scale is a single 16-bit term
+        assert G.split16_of(c["scale"], c["dtype"])["one"] == (c["scale"] in (0.125, 1.0, -0.5)), c["id"]
+    for cs in (Q, K):
+        assert {c["dtype"] for c in cs} == {torch.bfloat16, torch.float16} and {c["scale"] for c in cs} >= {0.125, 1.0, -0.5, 0.3, 1.3, 0.0884, -0.3}
+    kinds = {c["bias"] for c in Q}
+    assert kinds >= {"1h", "1h-min", "1h-inf", "1h-big", "1h-view"} and {c["bias"] for c in K} >= {"1h-min", "1h-inf", "1h-big"}
+    assert all(c["dtype"] == torch.bfloat16 and not G.split16_of(c["scale"], c["dtype"])["one"] for c in X if c["bias"].endswith("-big"))
+    assert any(c["causal"] and c["bias"].endswith("-inf") for c in Q)
+    F1 = [c for c in X if c["bodies"]["fused"] == "1"]
+    assert any((c["B"] * c["H"] * ((c["N"] + 255) // 256)) % 8 for c in F1) and any((c["B"] * c["H"] * ((c["N"] + 255) // 256)) % 8 == 0 for c in F1)
+    plain = [c for c in X if not c["bits"]]
+    assert len(plain) >= 2 and all(c["bodies"]["fused"] == "1" for c in plain) and any((c["B"], c["H"], c["M"], c["N"]) == (2, 8, 128, 128) for c in plain)
+    assert sum(c["pert"] for c in X) >= 6 and any(c["pert"] for c in F1) and sum(c["split"] for c in X) >= 4 and sum(c["strided"] for c in X) >= 4
+    # every kind of step, per body
+    kq, kk = set(), set()
+    for c in X:
+        lay = G.layout_of(c["bodies"], c["M"], c["N"], 0, c["causal"], False)
+        if lay["qdb"] is not None:
+            kq |= G.kinds_of_qdb(lay["qdb"])
+        if lay["kv"] is not None:
+            kk |= G.kinds_of(lay["kv"])
+    assert kq == set(G.KINDS_QDB), set(G.KINDS_QDB) - kq
+    want = {"far-negative trip", "causal-diagonal trip", "general step", "remainder behind the last trip", "fewer steps than ring slots", "key-tail wave"}
+    assert kk == want, (want - kk, kk - want)   # (without a table the all-visible trips carry the name of the far-negative ones)
+    from test_attn_bwd_fp64_gpu import seams_dense64
+    for c in X:
+        rows, keys = seams_dense64(c)
+        assert set(range(0, c["M"], 64)) <= set(rows) and set(range(0, c["N"], 128)) <= set(keys) and set(range(0, c["N"], 256)) <= set(keys)
+        assert set(range(0, c["M"], 32)) <= set(rows) and set(range(0, c["N"], 32)) <= set(keys)
 
 
 def _the_64_wide_groups(of):
@@ -256,13 +326,38 @@ def _the_64_wide_groups(of):
         assert all(r in rows for r in ((nst - nst % 4) * 32, (nst + 1) // 2 * 32) if r < c["M"])
 
 
-def test_the_bound_still_raises_for_the_dense_64_wide_bodies():
+def test_the_bound_raises_for_impossible_bodies_and_returns_for_the_dense_64_wide_ones():
     i = next(i for i, c in enumerate(CASES) if c["group"] == "dbias" and c["D"] == 64)
     case, (t, ref, _) = CASES[i], _truth(i)
-    for bodies in (dict(dq="64row-batch4", dkdv="64key", fused="1", qdiag="0", dbias="dq-kernel"), dict(dq="64row-batch4", dkdv="32key", fused="0", qdiag="0", dbias="dq-kernel+partials"),
-                   dict(dq="32row", dkdv="64key", fused="0", qdiag="0", dbias="staged"), dict(dq="32row", dkdv="32key", fused="0", qdiag="0", dbias="dq-kernel")):
+    for bodies, D in ((dict(dq="32row", dkdv="32key", fused="0", qdiag="0", dbias="dq-kernel"), 64), (dict(dq="32row", dkdv="64key", fused="0", qdiag="0", dbias="dq-kernel+partials"), 64),
+                      (dict(dq="64row-batch4", dkdv="64key", fused="1", qdiag="0", dbias="staged"), 64), (dict(dq="32row", dkdv="64key", fused="0", qdiag="0", dbias="somewhere"), 64),
+                      (dict(dq="64row-batch4", dkdv="64key", fused="1", qdiag="1", dbias="dq-kernel"), 64), (dict(dq="32row", dkdv="64key", fused="0", qdiag="1", dbias="staged"), 64),
+                      (dict(dq="64row-batch4", dkdv="32key", fused="0", qdiag="0", dbias="dq-kernel"), 128), (dict(dq="32row", dkdv="64key", fused="0", qdiag="0", dbias="staged"), 32),
+                      (dict(dq="64row", dkdv="64key", fused="1", qdiag="0", dbias="staged"), 64), (dict(dq="32row", dkdv="64key-half", fused="0", qdiag="0", dbias="staged"), 64),
+                      (dict(dq="64row-batch4", dkdv="32key", fused="1", qdiag="0", dbias="dq-kernel"), 64)):
         with pytest.raises(NotImplementedError):
-            G.attn_bwd_bound(ref, case["dtype"], 64, bodies, case["N"], case["M"])
+            G.attn_bwd_bound(ref, case["dtype"], D, bodies, case["N"], case["M"])
+    for bodies in (dict(dq="64row-batch4", dkdv="32key", fused="0", qdiag="0", dbias="dq-kernel"), dict(dq="64row-batch4", dkdv="64key", fused="0", qdiag="0", dbias="dq-kernel+partials"),
+                   dict(dq="64row-batch4", dkdv="64key", fused="1", qdiag="0", dbias="dq-kernel"), dict(dq="32row", dkdv="64key", fused="0", qdiag="0", dbias="staged")):
+        b = G.attn_bwd_bound(ref, case["dtype"], 64, bodies, case["N"], case["M"])
+        assert sorted(b) == ["dbias", "dk", "dq", "dv"] and all(bool(torch.isfinite(x).all()) for x in b.values())
+
+
+def test_the_selector_split_restates_split16():
+    """hand-checked: 1 / 0.125 = 8 and 1 / -0.5 = -2 are one term; 1 / 0.3 in bf16 truncates to 3.328125 + 0.005187988..., in fp16 rounds to 3.333984375 - 0.00065088..."""
+    for dt_ in (torch.bfloat16, torch.float16):
+        for sc in (0.125, 1.0, -0.5):
+            s = G.split16_of(sc, dt_)
+            assert s["one"] and s["rel"] == 0.0 and s["hi"] == 1.0 / sc
+    s = G.split16_of(0.3, torch.bfloat16)
+    assert s["hi"] == 3.328125 and 0 < s["lo"] < 2.0 ** -7 and not s["one"] and 0 < s["rel"] < 2.0 ** -14
+    assert s["hi"] == float(torch.tensor(s["hi"]).bfloat16()) and s["lo"] == float(torch.tensor(s["lo"]).bfloat16())
+    s = G.split16_of(0.3, torch.float16)
+    assert s["hi"] == float(torch.tensor(1 / 0.3).half()) and s["lo"] == float(torch.tensor(s["invf"] - s["hi"]).half()) and s["rel"] < 2.0 ** -21
+    for sc in (0.3, 1.3, 0.0884, -0.3):
+        assert 2.0 ** -18 < G.split16_of(sc, torch.bfloat16)["rel"] < 2.0 ** -14, sc
+    assert G.bias_clamp_limit(0.3, torch.bfloat16) == float(torch.tensor(-2.0e38 * 0.3).view(torch.int32).bitwise_and(-65536).view(torch.float32))
+    assert G.bias_clamp_limit(1.3, torch.bfloat16) < -1.99e38 and G.bias_clamp_limit(1.3, torch.float16) == -65504.0
 
 
 def test_the_step_classification_on_hand_worked_examples():
@@ -283,6 +378,36 @@ def test_the_step_classification_on_hand_worked_examples():
     # half-length form, 9 steps: the pairs walk 5 and 4 (+ 1 empty) steps
     hs = [(x["pair"], x["mt0"], x["ns"]) for x in G.steps_kv64(288, 128, 0, False, False, half=True) if x["kw0"] == 0]
     assert hs == [(0, 0, 5), (1, 5, 5)]
+    # ---- the dQ + dBias body (one walk per 64-row block) ----
+    kinds = lambda b: [k for _, k in b["segs"]]
+    # N = 264, not causal: two trips and a 8-key tail step; N = 160: one trip and one whole general step; N = 24: one partial step
+    (b,) = G.steps_qdb64(64, 264, False)
+    assert kinds(b) == ["trip", "trip", "general"] and b["tail"] and b["nt"] == 9 and not b["padded"]
+    (b,) = G.steps_qdb64(1, 160, False)
+    assert kinds(b) == ["trip", "general"] and not b["tail"]
+    (b,) = G.steps_qdb64(63, 24, False)
+    assert kinds(b) == ["general"] and b["tail"]
+    # causal, M = N = 256: block 0 sees 64 keys = 2 steps, padded to one trip of 4 (128 <= 256), all of it on or above the diagonal: masked;
+    # block 1: 4 steps, masked; block 2: 6 steps padded to 8 (256 <= 256), both trips masked -- an iteration forms the scores of the NEXT step, so a trip is
+    # unmasked only if step t + 4 is visible to all 64 rows (q:681), and keys 128..159 are not to row 128; block 3: 8 steps, keys ..159 lie below row 192
+    bs = G.steps_qdb64(256, 256, True)
+    assert [(b["nt0"], b["nt"], b["padded"]) for b in bs] == [(2, 4, True), (4, 4, False), (6, 8, True), (8, 8, False)]
+    assert [kinds(b) for b in bs] == [["mtrip"], ["mtrip"], ["mtrip", "mtrip"], ["trip", "mtrip"]]
+    # ... M = N = 248: block 2 would need 8 steps = 256 keys > 248: refused, its steps 4 and 5 run the general iteration; block 3 (rows 192..247) sees all 248 keys:
+    # 8 steps, the last a key tail, so the second trip is not whole: four general steps
+    bs = G.steps_qdb64(248, 248, True)
+    assert [(b["nt0"], b["nt"], b["refused"]) for b in bs] == [(2, 4, False), (4, 4, False), (6, 6, True), (8, 8, False)]
+    assert kinds(bs[2]) == ["mtrip", "general", "general"] and kinds(bs[3]) == ["trip"] + ["general"] * 4 and bs[3]["tail"]
+    # M = 300, N = 40, causal (P = -260): rows 0..259 are dead; blocks 0..3 end at keys <= 0: no step; block 4 (rows 256..299) sees 40 keys: two steps, the second a tail
+    bs = G.steps_qdb64(300, 40, True)
+    assert [b["nt"] for b in bs] == [0, 0, 0, 0, 2] and kinds(bs[4]) == ["general", "general"] and bs[4]["tail"] and bs[4]["refused"]
+    # ---- the DENSE 64-key body: the loop of the bodies without a table ----
+    w = {x["kw0"]: [k for _, k in x["segs"]] for x in G.steps_kv64(256, 264, 0, False, False, dense=True)}
+    assert w[0] == ["far-", "far-"] and w[192] == ["far-", "far-"] and w[256] == ["general"] * 8   # (the second workgroup's 8 keys: a key-tail wave)
+    w = {x["kw0"]: [k for _, k in x["segs"]] for x in G.steps_kv64(256, 256, 0, True, False, dense=True)}
+    assert w[0] == ["diag", "far-"] and w[128] == ["diag", "diag"]   # (the workgroup's waves share its first row: keys 128.. stay on the diagonal)
+    with pytest.raises(AssertionError):
+        G.steps_kv64(256, 256, 0, False, False, half=True, dense=True)
 
 
 @pytest.mark.parametrize("i", range(len(CASES)), ids=IDS)
@@ -391,6 +516,8 @@ def test_correct_arithmetic_satisfies_the_bound(i):
         kw["stats"] = "self" if case["bodies"]["fused"] == "1" else "stat2"
         if t["rpe"] is not None:
             kw["rounded_sums"] = G.far_rounded_mask(case["bodies"], case["M"], case["N"], case["R"], case["causal"])
+    if case["dense64"]:   # the dense 64-wide setting: the bias through the two-term selector, -L through the FMA (dQ + dBias) / as the start value (64-key)
+        kw["dense64"] = (("q",) if case["bodies"]["dq"] == "64row-batch4" else ()) + (("kv",) if case["bodies"]["dkdv"] == "64key" else ())
     emu = G.emulate(t["q"], t["k"], t["v"], t["o"], t["lse"], t["do"], case["scale"], case["causal"], t["bias"], t["rpe"], case["R"], t["bucket"],
                     32 if t["bucket"] is not None else 0, case["bodies"].get("dbias", "direct"), **kw)
     r = G.ratios(emu, ref, bound)

@@ -18,12 +18,22 @@ dtable=runs), qdiag (V_QDIAG_ON and V_QDIAG_OFF on the same inputs) and causal64
 the table inside the band, with a table far from the diagonal).  sm_scale is 0.125, 1.0 or 0.3 (no exact reciprocal); q is scaled so that the
 scores spread alike.  Shapes sit around the trip (128 rows), ring (4 steps), wave (64 keys) and workgroup (128 / 256 keys, 256 rows) boundaries;
 tests/test_attn_bwd_fp64_cpu.py asserts with the host restatement of the kernels' step classification that every kind of step occurs.
-Not covered: the DENSE 64-wide bodies (64row-batch4, the DENSE form of the 64-key body, the dense one-launch form, dbias dq-kernel /
-dq-kernel+partials; see tests/attn_bwd_fp64.py); they stay with the max-norm tests.
+Covered (csrc/attn_bwd_qdb64.h and the DENSE form of the 64-key body of csrc/attn_bwd64.h, D = 64, a dense bias): groups qdb (dq=64row-batch4 beside the 32-key body:
+B = 1 .. 9 -- three, two, one and no idle waves, two and three fp32 slabs --, rows 1 .. 130, keys 8 .. 264 around the step (32) and trip (128) boundaries, the
+eight-chunk workgroup cut with a remainder), qdbkv (both dense bodies as two launches), dfused (one launch behind bwd_stat2_kernel, the dK/dV workgroup count
+mostly no multiple of eight), dplain (NO variant bit: what a plain model call takes, (2, 8, 128, 128) among them), dkv64 (the DENSE 64-key body beside the 32-row dQ
+kernel: bias kinds 1h / bh / 11 / b1, dbias routes direct / staged / inkernel) and dcausal (each form at N - M in {0, 1, 100, -1, -100}; M = N = 256 with padded
+sweeps, 248 with the padding refused, M >> N with row blocks that have no step; the final tensor and the slabs).  sm_scale rotates through 0.125, 1.0, -0.5 (one
+selector term) and 0.3, 1.3, 0.0884, -0.3 (two).  Bias kinds beyond the plain one: -min (finfo.min on half the keys and on whole rows), -inf (the same written as
+-inf, single entries included), -big (|bias| up to 64 through a two-term bf16 selector: the cases on which the selector's residual term of the bound is largest) and -view (a
+(1, H, M, N) view of a tensor with row pitch N + 64, whose padding must stay untouched).  These cases fill the workspace with 0xFF bytes before every run, so the
+statistics and the fp32 slabs hold NaN wherever the call does not write.
 
 The value rows at key 0, N - 1 and the block seam and the `do` rows 0, M - 1 and the first rows of the last 32- / 64-row blocks carry 32
 times the others' magnitude -- in the 64-wide cases also the keys at every wave start (64 w: the 128- and 256-key block starts among them) and the
-rows at every trip start (multiples of 128), at the first step behind the last aligned trip and at the first step of the second pair's half --,
+rows at every trip start (multiples of 128), at the first step behind the last aligned trip and at the first step of the second pair's half; in the dense
+64-wide cases every step start (multiples of 32 rows and keys: the 64-row blocks, the 128-key trips and the 256-key workgroups among them) and row 2 of the first
+and the last element of every batch group --,
 so that one dropped key or row there moves the gradients beyond the bound (tests/test_attn_bwd_fp64_cpu.py proves that on these very inputs,
 without a GPU).  Every case asserts its bodies through fat5_attn_describe before it launches.
 
@@ -219,8 +229,76 @@ def _build_cases():
     add64("kv64h", KVH + Q32, "32row", "64key-half", 1, 2, 256, 256, F16, bias="rpe", R=64, scale=0.3)
     add64("sep64", KV + ("V_Q64_ON",) + SEP, "64row", "64key", 1, 2, 128, 256, F16, bias="rpe", R=64, scale=0.3)
     add64("causal64", ONE, "64row", "64key", 1, 2, 256, 256, F16, fused=1, causal=True, bias="rpe", R=64, qdiag=1, scale=0.3, tag="-fused64")
+    # ================================================================================================================================
+    # The DENSE 64-wide bodies (D = 64): dq=64row-batch4 (csrc/attn_bwd_qdb64.h), the DENSE form of dkdv=64key (csrc/attn_bwd64.h), both in one launch
+    # ================================================================================================================================
+    SC7 = (0.125, 1.0, -0.5, 0.3, 1.3, 0.0884, -0.3)   # (the first three: 1 / scale is one 16-bit term -- the ONE kernels; the others need two)
+    QDB, QDBKV, DFUSED, DKV = ("V_QDB64_ON", "V_KV64_OFF"), ("V_QDB64_ON", "V_KV64_ON", "V_FUSED64_OFF"), ("V_QDB64_ON", "V_KV64_ON", "V_FUSED64_ON"), ("V_KV64_ON", "V_QDB64_OFF")
+    nd = [0]
+
+    def addd(group, bits, B, H, M, N, dtype=None, causal=False, bias="1h", scale=None, route=None, pert=False, split=False, strided=False, tag=""):
+        i = nd[0]
+        nd[0] += 1
+        scale = SC7[i % 7] if scale is None else scale
+        dtype = dt(i) if dtype is None else dtype
+        if bits is DKV:
+            dq, dkdv, fused = "32row", "64key", 0
+            route = route or ("direct" if bias[:2] == "bh" else "staged")
+            if route == "inkernel":
+                bits = bits + ("V_DBIAS_INKERNEL",)
+            elif route == "staged":
+                bits = bits + ("V_DBIAS_STAGED",)
+        else:
+            dq, dkdv, fused = "64row-batch4", "32key" if bits is QDB else "64key", int(bits is DFUSED or group == "dplain")
+            route = "dq-kernel" if B <= 4 else "dq-kernel+partials"
+        cid = (f"{group}{tag}-{B}x{H}x{M}x{N}-{_name(dtype)}-{bias}-s{scale}{'-causal' if causal else ''}{'-strided' if strided else ''}{'-pert' if pert else ''}"
+               f"{'-stages' if split else ''}{'-' + route if dq == '32row' and bias[:2] != 'bh' else ''}{'-plain' if not bits else ''}")
+        out.append(dict(id=cid, group=group, bodies=dict(dq=dq, dkdv=dkdv, fused=str(fused), qdiag="0", dbias=route), bits=bits, B=B, H=H, M=M, N=N, D=64, dtype=dtype,
+                        causal=causal, bias=bias, R=0, scale=scale, strided=strided, pert=pert, split=split, wide=False, dense64=True))
+
+    # ---- qdb: the dQ + dBias body beside the 32-key dK/dV body.  Batch groups (idle waves, slabs), rows, keys, the workgroup decode ----
+    for i, (B, M, N) in enumerate(((1, 1, 8), (2, 63, 24), (3, 64, 32), (4, 65, 40), (5, 130, 128), (6, 64, 136), (8, 65, 160), (9, 63, 264))):
+        addd("qdb", QDB, B, 2, M, N, bias=("1h", "1h", "1h-inf", "1h", "1h-view", "1h", "1h", "1h")[i], strided=i % 3 == 1, split=i == 5, pert=i == 6)
+    addd("qdb", QDB, 4, 3, 192, 64)                                  # H ngrp n_mblk = 9: the eight-chunk cut with a remainder
+    addd("qdb", QDB, 2, 2, 130, 192, BF16, bias="1h-min", scale=0.3)   # finfo.min on half the keys, and on all keys of some rows
+    addd("qdb", QDB, 3, 2, 65, 136, BF16, bias="1h-big", scale=0.3)    # |bias| up to 64 through a two-term selector: its residual term at its largest
+    addd("qdb", QDB, 5, 2, 64, 160, BF16, bias="1h-big", scale=1.3)
+    addd("qdb", QDB, 2, 2, 64, 128, F16, bias="1h-inf", scale=0.0884)
+    # ---- qdbkv: both dense 64-wide bodies as two launches (the dK/dV body on the dQ kernel's statistics) ----
+    for i, (B, M, N, bias) in enumerate(((2, 130, 264, "1h"), (4, 64, 128, "1h-view"), (5, 65, 136, "1h"), (3, 128, 256, "1h-inf"), (1, 160, 72, "1h"), (6, 90, 64, "1h"))):
+        addd("qdbkv", QDBKV, B, 2, M, N, bias=bias, split=i == 2, pert=i == 3, strided=i == 0)
+    # ---- dfused: one launch behind the statistics kernel; B H ceil(N / 256) no multiple of 8 (the padding exits) but for the last ----
+    for i, (B, H, M, N, bias) in enumerate(((3, 2, 130, 264, "1h"), (2, 3, 64, 128, "1h"), (5, 2, 65, 136, "1h-inf"), (9, 1, 128, 256, "1h"), (1, 3, 300, 72, "1h"),
+                                            (2, 2, 160, 520, "1h-view"), (4, 2, 90, 264, "1h-big"), (2, 4, 128, 160, "1h"))):
+        addd("dfused", DFUSED, B, H, M, N, bias=bias, pert=i in (1, 5), split=i == 3, strided=i == 4, dtype=BF16 if bias == "1h-big" else None,
+             scale=0.3 if bias == "1h-big" else None)
+    addd("dplain", (), 2, 8, 128, 128, BF16, scale=0.125)             # no variant bit: what a plain model call takes
+    addd("dplain", (), 4, 2, 192, 264, F16, scale=1.0)
+    addd("dplain", (), 6, 2, 65, 136, BF16, scale=0.3, pert=True)
+    # ---- dkv64: the DENSE 64-key dK/dV body beside the 32-row dQ kernel: every broadcast kind, every dbias route of that kernel ----
+    for i, (B, M, N, bias, route, causal) in enumerate(((2, 90, 64, "bh", None, False), (2, 128, 72, "1h", "staged", False), (2, 160, 256, "11", "staged", False),
+                                                        (2, 300, 264, "b1", "staged", False), (2, 128, 520, "1h", "inkernel", False), (1, 300, 256, "bh", None, True),
+                                                        (2, 160, 264, "1h-min", "staged", False), (5, 130, 64, "1h-inf", "inkernel", False), (2, 256, 256, "bh", None, True),
+                                                        (2, 129, 72, "1h-big", "staged", False))):
+        addd("dkv64", DKV, B, 2, M, N, bias=bias, route=route, causal=causal, split=i == 3, pert=i == 4, strided=i == 1,
+             dtype=BF16 if bias in ("1h-min", "1h-big") else None, scale=0.3 if bias in ("1h-min", "1h-big") else None)
+    # ---- dcausal: bottom-right masks, N - M in {0, 1, 100, -1, -100} per form; the final tensor (B <= 4) and the slabs (B > 4) for P > 0 and P < 0 ----
+    for f, (name, bits) in enumerate((("qdb", QDB), ("dfused", DFUSED), ("dkv64", DKV))):
+        for i, d in enumerate((0, 1, 100, -1, -100)):
+            M, N = 136 - d, 136
+            addd("dcausal", bits, (2, 5, 3, 6, 4)[(i + f) % 5] if bits is not DKV else 2, 2, M, N, causal=True, bias=("1h", "bh")[i % 2] if bits is DKV else "1h",
+                 pert=(i + f) == 3, strided=(i + f) == 4, tag="-" + name)
+    addd("dcausal", QDB, 5, 2, 36, 136, causal=True, tag="-qdb")     # P = 100 into the slabs
+    addd("dcausal", QDB, 6, 2, 236, 136, causal=True, tag="-qdb")    # P = -100 into the slabs: dead rows, row blocks without steps
+    addd("dcausal", QDB, 2, 2, 256, 256, causal=True, tag="-qdb")    # the sweeps of blocks 0 and 2 padded to whole trips
+    addd("dcausal", DFUSED, 5, 2, 256, 256, causal=True, tag="-dfused")
+    addd("dcausal", QDB, 2, 2, 248, 248, causal=True, tag="-qdb")    # ... and the padding refused for the third block (6 -> 8 steps = 256 keys > 248)
+    addd("dcausal", DFUSED, 3, 2, 300, 40, causal=True, tag="-dfused")   # M >> N: row blocks with nt = 0
+    addd("dcausal", DFUSED, 2, 8, 128, 128, causal=True, tag="-dfused")  # (H ngrp) % 8 == 0: the row-block-major order
+    addd("dcausal", QDB, 4, 2, 192, 192, causal=True, bias="1h-inf", tag="-qdb")
     for c in out:
         c.setdefault("wide", False)   # (wide: a case of the 64-wide groups)
+        c.setdefault("dense64", False)   # (dense64: a case of the dense 64-wide groups)
     assert len({c["id"] for c in out}) == len(out)
     return out
 
@@ -246,6 +324,12 @@ def seams64(case):
     return sorted(r for r in rows if r < M), list(range(0, N, 64))
 
 
+def seams_dense64(case):
+    """(rows, keys) of the dense 64-wide bodies' seams: every step start (multiples of 32 rows and of 32 keys), which covers the trip starts (128 keys of the
+    dQ + dBias body, 128 rows of the 64-key body), the 64-row blocks and the 256-key workgroups"""
+    return list(range(0, case["M"], 32)), list(range(0, case["N"], 32))
+
+
 def bucket_map(case):
     if case["bias"][:2] != "t5":
         return None
@@ -265,13 +349,17 @@ def inputs(case):
         return torch.randn(B, H, S, D, generator=g).to(dtype)
 
     q, k, v, do = rnd(M), rnd(N), rnd(N), rnd(M)
-    rows64, keys64 = seams64(case) if case["wide"] else ([], [])
-    if case["wide"] and case["scale"] != 0.125:   # (the same spread of scores at every sm_scale: the softmax stays as flat as in the other cases)
+    rows64, keys64 = seams64(case) if case["wide"] else (seams_dense64(case) if case["dense64"] else ([], []))
+    if (case["wide"] or case["dense64"]) and case["scale"] != 0.125:   # (the same spread of scores at every sm_scale: the softmax stays as flat as in the other cases)
         q.copy_((q.float() * (0.125 / case["scale"])).to(dtype))
     for j in ({0, N - 1, F.seam_key(N)} | set(keys64)) - {None}:
         v[:, :, j] = (v[:, :, j].float() * BOOST).to(dtype)
     for m in sorted(set(boosted_rows(M)) | set(rows64)):
         do[:, :, m] = (do[:, :, m].float() * BOOST).to(dtype)
+    if case["dense64"]:   # the first and the last element of every batch group (four elements per dQ workgroup), on a row nothing else boosts
+        for b in sorted({x for g4 in range(0, B, 4) for x in (g4, min(g4 + 3, B - 1))}):
+            if M > 2:
+                do[b, :, 2] = (do[b, :, 2].float() * BOOST).to(dtype)
     bias = rpe = None
     kind = case["bias"]
     bucket = bucket_map(case)
@@ -285,6 +373,17 @@ def inputs(case):
         if kind.endswith("-min"):
             bias[..., N // 2:] = torch.finfo(dtype).min
             bias[:, :, 7::64, :] = torch.finfo(dtype).min
+        elif kind.endswith("-inf"):   # -inf as the additive mask: a run of keys, single entries (one per 32-row operand and more), whole rows
+            bias[..., N // 4:N // 2] = -float("inf")
+            bias[:, :, 3::16, 1::8] = -float("inf")
+            bias[:, :, 5::32, :] = -float("inf")
+        elif kind.endswith("-big"):   # |bias| up to 64, flat within a row (the softmax stays as flat as elsewhere): row offsets of both signs in [40, 62]
+            off = (40.0 + 22.0 * torch.rand(M, generator=g)) * (1.0 - 2.0 * (torch.arange(M) % 2))
+            bias = (bias.float() * 0.5 + off[:, None]).to(dtype)
+        elif kind.endswith("-view"):  # a (1, H, M, N) view of a wider tensor: row pitch N + 64
+            wide_ = torch.full(bias.shape[:3] + (N + 64,), SENTINEL, dtype=dtype)
+            wide_[..., :N] = bias
+            bias = wide_[..., :N]
     fwd = F.attn_fwd_ref(q, k, v, case["scale"], case["causal"], bias, rpe, case["R"])
     o = torch.empty_like(q).copy_(fwd["o"].to(dtype))
     lse = fwd["lse"].float()
@@ -326,7 +425,8 @@ def describe(case):
         sb, sh = DENSE_SHAPE[kind[:2]]
         nh = 1 if sh else H
         p.bias_mode, p.bias, p.dbias = _lib.BIAS_DENSE, 16, 16
-        p.bias_stride[0], p.bias_stride[1], p.bias_stride[2] = (0 if sb else nh * M * N), (0 if sh else M * N), N
+        pitch = N + 64 if kind.endswith("-view") else N
+        p.bias_stride[0], p.bias_stride[1], p.bias_stride[2] = (0 if sb else nh * M * pitch), (0 if sh else M * pitch), pitch
         p.dbias_batch, p.dbias_heads = (1 if sb else B), nh
     elif kind != "none":
         p.bias_mode, p.rpe1d, p.rpe_radius = _lib.BIAS_RPE1D, 16, case["R"]
@@ -371,6 +471,11 @@ def test_backward_within_the_fp64_bound(case):
     ref = reference(case, t)
     bound = G.attn_bwd_bound(ref, case["dtype"], case["D"], case["bodies"], case["N"], case["M"])
     dev = {key: (x.to("cuda") if x is not None else None) for key, x in t.items()}
+    if case["bias"].endswith("-view"):   # (a copy to the device would pack the rows: build the wider tensor there)
+        wide_ = torch.full(t["bias"].shape[:3] + (case["N"] + 64,), SENTINEL, dtype=case["dtype"], device="cuda")
+        wide_[..., :case["N"]] = t["bias"].to("cuda")
+        dev["bias"] = wide_[..., :case["N"]]
+        assert dev["bias"].stride(2) == case["N"] + 64
     if case["strided"]:
         assert dev["q"].stride() == t["q"].stride() and dev["do"].stride() == t["do"].stride() and _lib.kernel_ready(dev["q"])   # (never copied)
     plan = AttentionPlan(dev["q"], dev["k"], dev["v"], dev["do"], bias=dev["bias"], rpe1d=dev["rpe"], radius=case["R"], causal=case["causal"],
@@ -396,6 +501,8 @@ def test_backward_within_the_fp64_bound(case):
         for x in (plan.dq, plan.dk, plan.dv, plan.dbias):
             if x is not None:
                 x.fill_(SENTINEL)   # (every element has to be written)
+        if case["dense64"] and plan.ws is not None and plan.ws.numel():
+            plan.ws.view(torch.uint8).fill_(255)   # (NaN patterns in the statistics and in the fp32 slabs: nothing may be read that this call did not write)
         if case["split"]:
             for stage in (1, 2, 4):   # FAT5_BWD_DQ, FAT5_BWD_DKDV, FAT5_BWD_REDUCE
                 plan.backward(stage)
@@ -414,6 +521,8 @@ def test_backward_within_the_fp64_bound(case):
         assert torch.equal(_bits(now), _bits(x)), f"{case['id']}: the call changed {key}"
     for buf in guards:
         assert bool((buf[:, :, case["H"]] == SENTINEL).all()), f"{case['id']}: written outside the gradient's view"
+    if case["bias"].endswith("-view"):
+        assert bool((wide_[..., case["N"]:] == SENTINEL).all()), f"{case['id']}: the bias tensor's padding changed"
     outs = compared(case, ref)
     assert sorted(got) == sorted(outs)
     for x in outs:
