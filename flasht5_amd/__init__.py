@@ -33,6 +33,7 @@ from .logits_process import process_logits, pack_bad_words  # noqa: E402
 from .speculative import speculative_accept, speculative_round, draft_tokens  # noqa: E402
 from .prompt_lookup import prompt_lookup_draft  # noqa: E402
 from .packing import pack_plan, plan_pair, PackPlan  # noqa: E402
+from .ul2 import ul2_lengths, ul2_tables, ul2_collate, UL2Collator, UL2Tables  # noqa: E402
 from .attention_module import FlashT5Attention  # noqa: E402
 from .modules import FlashT5LayerNorm, FlashT5CrossEntropyLoss  # noqa: E402
 from .adamw_scaled import AdamWScale  # noqa: E402

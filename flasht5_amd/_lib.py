@@ -213,6 +213,22 @@ class PackParams(ctypes.Structure):
     ]
 
 
+class Ul2Params(ctypes.Structure):
+    """Mirror of `fat5_ul2_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("L", ctypes.c_int32), ("max_length", ctypes.c_int32), ("max_labels_length", ctypes.c_int32),
+        ("num_denoisers", ctypes.c_int32), ("num_sentinels", ctypes.c_int32), ("random_chunk", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("sentinel_first_id", ctypes.c_int64), ("eos_token_id", ctypes.c_int64), ("pad_token_id", ctypes.c_int64), ("seed", ctypes.c_uint64),
+        ("tokens", ctypes.c_void_p), ("tokens_stride", ctypes.c_int64), ("lengths", ctypes.c_void_p), ("step", ctypes.c_void_p),
+        ("mu", ctypes.c_void_p), ("r", ctypes.c_void_p), ("max_spans", ctypes.c_void_p), ("tokens_len", ctypes.c_void_p),
+        ("prefix_off", ctypes.c_void_p), ("prefix_ids", ctypes.c_void_p), ("cum_prop", ctypes.c_void_p),
+        ("noise_mask", ctypes.c_void_p), ("noise_mask_stride", ctypes.c_int64), ("denoiser_in", ctypes.c_void_p),
+        ("input_ids", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("attention_mask", ctypes.c_void_p),
+        ("decoder_attention_mask", ctypes.c_void_p), ("enc_len", ctypes.c_void_p), ("dec_len", ctypes.c_void_p),
+        ("denoiser", ctypes.c_void_p), ("status", ctypes.c_void_p),
+    ]
+
+
 class DropoutDesc(ctypes.Structure):
     """Mirror of `fat5_dropout_desc` (include/fat5.h) -- field order must match exactly."""
     _fields_ = [
@@ -240,6 +256,7 @@ EXPORTS = (
     "fat5_kv_quantize", "fat5_sizeof_kv_quant_params",
     "fat5_lookup_draft", "fat5_sizeof_lookup_params",
     "fat5_pack_plan", "fat5_sizeof_pack_params",
+    "fat5_ul2_collate", "fat5_sizeof_ul2_params",
     "fat5_dropout", "fat5_dropout_add_rmsnorm_fwd", "fat5_dropout_add_rmsnorm_bwd", "fat5_sizeof_dropout_desc",
 )
 
@@ -404,6 +421,12 @@ def load():
     if lib.fat5_sizeof_pack_params() != ctypes.sizeof(PackParams):
         raise ImportError(f"fat5_pack_params layout mismatch: library {lib.fat5_sizeof_pack_params()} B, "
                           f"binding {ctypes.sizeof(PackParams)} B")
+    lib.fat5_ul2_collate.restype = ctypes.c_int
+    lib.fat5_ul2_collate.argtypes = [ctypes.POINTER(Ul2Params), ctypes.c_void_p]
+    lib.fat5_sizeof_ul2_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_ul2_params() != ctypes.sizeof(Ul2Params):
+        raise ImportError(f"fat5_ul2_params layout mismatch: library {lib.fat5_sizeof_ul2_params()} B, "
+                          f"binding {ctypes.sizeof(Ul2Params)} B")
     dd = ctypes.POINTER(DropoutDesc)
     lib.fat5_dropout.restype = ctypes.c_int
     lib.fat5_dropout.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, dd, i32, vp]

@@ -988,6 +988,91 @@ size_t fat5_sizeof_pack_params(void);
 int fat5_pack_plan(const fat5_pack_params* p, void* hip_stream);
 
 /*
+ * UL2 span-corruption collator (ul2_kernels.h): what the reference's DataCollatorForUL2MLM
+ * (src/data/data_collator_ul2.py) does to one example per row, on raw token rows that already live on the device.  Row b of
+ * `tokens` (B, L) int64, rows tokens_stride elements apart, holds n_b = lengths[b] tokens (read as clamped to [0, L]).
+ * D = num_denoisers (1 .. 256) denoisers are described by device arrays: mu, r (D,) fp64; max_spans, tokens_len (D,) int32
+ * (tokens_len: the longest example the denoiser takes, read as clamped to [0, 4096]); prefix_off (D + 1,) int32 offsets into
+ * prefix_ids int64 (prefix_ids may be NULL when prefix_off[D] is 0); cum_prop (D,) fp32 cumulative normalised proportions.
+ *
+ * Random words: W(c0, stream) = Philox4x32-10(key = (seed low 32 bits, seed high 32 bits), counter = (c0, b, stream, step[0] mod 2^32)),
+ * `step` one int64 in device memory, read by the kernel.
+ *   Row draw: w = W(0, 0); u = (w[0] >> 8) * 2^-24 (fp32, exact); d = the first index with u < cum_prop[d], D - 1 without one.
+ *     n_b > tokens_len[d]: start = random_chunk ? umulhi(w[1], n_b - tokens_len[d]) : 0 and n = tokens_len[d]; else start = 0, n = n_b.
+ *     (umulhi(w, m) < m: like the reference's randint(0, m), the last possible start is never drawn.)  The row's tokens are
+ *     t[i] = tokens[b][start + i], i < n.
+ *   Span counts, in fp64 with rint = round-half-to-even:  max_spans[d] == 1 (the S-denoiser): mask[i] = (i >= rint(n / mu)), no
+ *     draw.  Otherwise noise = clamp(rint(n * r), 1, n - 1); spans = max(1, min(max_spans, num_sentinels, rint(noise / mu), noise,
+ *     n - noise)).  (The last three terms bite only where the reference raises or emits ids outside the sentinel range.)
+ *   Segmentation(items, stream): a uniform composition of `items` into `spans` positive parts.  Position i in [0, items - 1) has
+ *     the 64-bit key (W(i >> 2, stream)[i & 3] << 32) | i; the spans - 1 smallest keys are the cut points; a cut at i starts a
+ *     new part at item i + 1.  Noise part lengths = Segmentation(noise, 1), non-noise part lengths = Segmentation(n - noise, 2).
+ *     The mask lays the parts out as non-noise_0, noise_0, non-noise_1, noise_1, ...
+ *   Given-mask mode (noise_mask (B, L) uint8, rows noise_mask_stride bytes apart, and denoiser_in (B,) int32, both non-NULL or
+ *     both NULL): nothing is drawn and `step` is not read; d = denoiser_in[b] (clamped to [0, D)), start = 0, n = n_b with no
+ *     upper bound, mask[i] = noise_mask[b][i] != 0.
+ *   Streams: walking i = 0 .. n - 1, a run starts where i == 0 or mask[i] != mask[i - 1].  The start of a noise run appends the
+ *     next sentinel to the encoder stream, the start of a non-noise run the next sentinel to the decoder stream; the k-th
+ *     sentinel of a stream (k from 0) is sentinel_first_id - k.  Then t[i] goes to the decoder stream if mask[i], else to the
+ *     encoder stream -- unless t[i] == eos_token_id, which is dropped (as the reference drops it).
+ *     input_ids[b] = the prefix ids of d, the encoder stream, eos_token_id, then pad_token_id up to max_length;
+ *     labels[b]    = the decoder stream, eos_token_id, then -100 up to max_labels_length.
+ *     enc_len[b] / dec_len[b] = the columns in front of the padding; attention_mask[b][j] = j < enc_len[b] and
+ *     decoder_attention_mask[b][j] = j < dec_len[b] (one byte each, 0 / 1); denoiser[b] = d.
+ * status (4,) int32 = {the OR of every row's flags, the rows with a flag, max enc_len, max dec_len}.  Flags -- whatever the
+ * inputs hold, every access is in bounds and every output element is written:
+ *   1  the encoder side was longer than max_length: cut to max_length, its last column forced to eos_token_id;
+ *   2  the same for the decoder side and max_labels_length;
+ *   4  a token t[i] equals pad_token_id or lies in [sentinel_first_id - num_sentinels + 1, sentinel_first_id]; the row is still
+ *      processed literally;
+ *   8  n < 2 (n_b < 2, or tokens_len[d] < 2): the row emits prefix + eos / eos only.
+ * Outputs are contiguous caller-owned device buffers written with plain stores (no atomics: the same bytes on every run).  Two
+ * launches on `hip_stream`, no workspace, nothing read back by the host (graph-replayable).
+ * Rejected with FAT5_EINVAL before anything is launched: NULL params, B < 1, L < 1, max_length < 1, max_labels_length < 1,
+ * num_denoisers outside [1, 256], num_sentinels < 1, a negative stride, noise_mask without denoiser_in or the reverse, a NULL or
+ * misaligned pointer (8 bytes for int64 / fp64 arrays, 4 for int32 / fp32; `step` may be NULL in given-mask mode).
+ */
+typedef struct fat5_ul2_params {
+  int32_t B;
+  int32_t L;
+  int32_t max_length;
+  int32_t max_labels_length;
+  int32_t num_denoisers;
+  int32_t num_sentinels;
+  int32_t random_chunk;         /* 0 / 1 */
+  int32_t reserved;
+  int64_t sentinel_first_id;
+  int64_t eos_token_id;
+  int64_t pad_token_id;
+  uint64_t seed;
+  const int64_t* tokens;
+  int64_t tokens_stride;        /* elements */
+  const int32_t* lengths;
+  const int64_t* step;
+  const double* mu;
+  const double* r;
+  const int32_t* max_spans;
+  const int32_t* tokens_len;
+  const int32_t* prefix_off;
+  const int64_t* prefix_ids;
+  const float* cum_prop;
+  const uint8_t* noise_mask;    /* given-mask mode, else NULL */
+  int64_t noise_mask_stride;    /* bytes */
+  const int32_t* denoiser_in;   /* given-mask mode, else NULL */
+  int64_t* input_ids;           /* (B, max_length) */
+  int64_t* labels;              /* (B, max_labels_length) */
+  uint8_t* attention_mask;      /* (B, max_length) */
+  uint8_t* decoder_attention_mask; /* (B, max_labels_length) */
+  int32_t* enc_len;             /* (B,) */
+  int32_t* dec_len;             /* (B,) */
+  int32_t* denoiser;            /* (B,) */
+  int32_t* status;              /* (4,) */
+} fat5_ul2_params;
+/* sizeof(fat5_ul2_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_ul2_params(void);
+int fat5_ul2_collate(const fat5_ul2_params* p, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)
