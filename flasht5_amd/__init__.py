@@ -28,6 +28,7 @@ from .positional_encoding import (relative_position_bucket, compute_bias, rpe1d_
                                   RelativePositionalEncoding)
 
 from .decode import flash_attn_with_kvcache, flash_attn_with_kvcache_chunk, quantize_kv  # noqa: E402
+from .w8 import quantize_weight, w8_linear  # noqa: E402
 from .sampling import sample_logits  # noqa: E402
 from .logits_process import process_logits, pack_bad_words  # noqa: E402
 from .speculative import speculative_accept, speculative_round, draft_tokens  # noqa: E402

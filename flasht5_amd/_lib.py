@@ -229,6 +229,24 @@ class Ul2Params(ctypes.Structure):
     ]
 
 
+class W8QuantParams(ctypes.Structure):
+    """Mirror of `fat5_w8_quant_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("N", ctypes.c_int64), ("K", ctypes.c_int32), ("dtype", ctypes.c_int32), ("w", ctypes.c_void_p), ("w_stride", ctypes.c_int64),
+        ("out", ctypes.c_void_p), ("out_stride", ctypes.c_int64), ("scale", ctypes.c_void_p),
+    ]
+
+
+class W8LinearParams(ctypes.Structure):
+    """Mirror of `fat5_w8_linear_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("R", ctypes.c_int64), ("N", ctypes.c_int64), ("K", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("x_stride", ctypes.c_int64), ("w8", ctypes.c_void_p), ("w_stride", ctypes.c_int64),
+        ("scale", ctypes.c_void_p), ("norm_weight", ctypes.c_void_p), ("eps", ctypes.c_float), ("reserved", ctypes.c_int32),
+        ("residual", ctypes.c_void_p), ("residual_stride", ctypes.c_int64), ("y", ctypes.c_void_p), ("y_stride", ctypes.c_int64),
+    ]
+
+
 class DropoutDesc(ctypes.Structure):
     """Mirror of `fat5_dropout_desc` (include/fat5.h) -- field order must match exactly."""
     _fields_ = [
@@ -257,6 +275,7 @@ EXPORTS = (
     "fat5_lookup_draft", "fat5_sizeof_lookup_params",
     "fat5_pack_plan", "fat5_sizeof_pack_params",
     "fat5_ul2_collate", "fat5_sizeof_ul2_params",
+    "fat5_w8_quantize", "fat5_sizeof_w8_quant_params", "fat5_w8_linear", "fat5_sizeof_w8_linear_params",
     "fat5_dropout", "fat5_dropout_add_rmsnorm_fwd", "fat5_dropout_add_rmsnorm_bwd", "fat5_sizeof_dropout_desc",
 )
 
@@ -427,6 +446,13 @@ def load():
     if lib.fat5_sizeof_ul2_params() != ctypes.sizeof(Ul2Params):
         raise ImportError(f"fat5_ul2_params layout mismatch: library {lib.fat5_sizeof_ul2_params()} B, "
                           f"binding {ctypes.sizeof(Ul2Params)} B")
+    for fn, size_fn, struct, name in ((lib.fat5_w8_quantize, lib.fat5_sizeof_w8_quant_params, W8QuantParams, "fat5_w8_quant_params"),
+                                      (lib.fat5_w8_linear, lib.fat5_sizeof_w8_linear_params, W8LinearParams, "fat5_w8_linear_params")):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
+        size_fn.restype = ctypes.c_size_t
+        if size_fn() != ctypes.sizeof(struct):
+            raise ImportError(f"{name} layout mismatch: library {size_fn()} B, binding {ctypes.sizeof(struct)} B")
     dd = ctypes.POINTER(DropoutDesc)
     lib.fat5_dropout.restype = ctypes.c_int
     lib.fat5_dropout.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, dd, i32, vp]

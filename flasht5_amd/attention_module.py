@@ -285,21 +285,29 @@ class FlashT5Attention(nn.Module):
 
         FP8 caches: `k_scale` / `v_scale` (B, L_cap, H) fp32, the scales of float8_e4m3fn caches (decode.py); None: 16-bit caches."""
         self.decode_supported()
-        from .decode import flash_attn_with_kvcache, flash_attn_with_kvcache_chunk
         B, M = hidden_states.shape[:2]
+        H, Dh = self.n_heads, self.key_value_proj_dim
+        q = self.Wq(hidden_states).view(B, M, H, Dh)
+        k = v = None
+        if cache_seqlens is not None:
+            k = self.Wk(hidden_states).view(B, M, H, Dh)
+            v = self.Wv(hidden_states).view(B, M, H, Dh)
+        return self.o(self.attend_decode(q, k, v, k_cache, v_cache, cache_seqlens, position_bias, position, cache_batch_idx,
+                                         cache_row_batch, cross_seqlens, chunk_seqlens, k_scale, v_scale))
+
+    def attend_decode(self, q, k, v, k_cache, v_cache, cache_seqlens=None, position_bias=None, position=None, cache_batch_idx=None,
+                      cache_row_batch=None, cross_seqlens=None, chunk_seqlens=None, k_scale=None, v_scale=None):
+        """`forward_decode` between its projections: q (B, M, H, D) and, for self-attention, the new k / v rows (B, M, H, D; strided
+        views are taken as they are) -> the attention output (B, M, inner_dim) in front of `o`; the arguments are forward_decode's"""
+        from .decode import flash_attn_with_kvcache, flash_attn_with_kvcache_chunk
+        B, M = q.shape[:2]
         if M > 1 and (cache_batch_idx is not None or cache_row_batch is not None):
             raise ValueError("forward_decode: cache_batch_idx / cache_row_batch take one query row per step (beam search has no chunks)")
         if M == 1 and chunk_seqlens is not None:
             raise ValueError("forward_decode: chunk_seqlens needs a chunk of M > 1 rows")
         if cross_seqlens is not None and cache_seqlens is not None:
             raise ValueError("forward_decode: cross_seqlens is for cross-attention (cache_seqlens None)")
-        H, Dh = self.n_heads, self.key_value_proj_dim
-        q = self.Wq(hidden_states).view(B, M, H, Dh)
         is_self = cache_seqlens is not None
-        k = v = None
-        if is_self:
-            k = self.Wk(hidden_states).view(B, M, H, Dh)
-            v = self.Wv(hidden_states).view(B, M, H, Dh)
         rpe1d, radius = None, 0
         if self.rotary:
             if position is None:
@@ -327,7 +335,7 @@ class FlashT5Attention(nn.Module):
         else:
             out = flash_attn_with_kvcache_chunk(q, k_cache, v_cache, k, v, lens, self.softmax_scale, causal=is_self, rpe1d=rpe1d,
                                                 rpe_radius=radius, chunk_seqlens=chunk_seqlens, **fp8)
-        return self.o(out.reshape(B, M, self.inner_dim))
+        return out.reshape(B, M, self.inner_dim)
 
     def project_kv(self, key_value_states):
         """the cross-attention K / V of an encoder output (B, L_enc, d_model) as (B, L_enc, H, D) caches for `forward_decode`:

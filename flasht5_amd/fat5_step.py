@@ -490,11 +490,19 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
                            packing=Packed(dp.cu_seqlens, dp.max_seqlen, ep.cu_seqlens, ep.max_seqlen), drop=drop)
         return self._loss(dec, lab.unsqueeze(0))
 
-    def init_decode_state(self, input_ids, max_length=32, attention_mask=None, prompt_length=1, kv_cache_dtype=None):
+    def init_decode_state(self, input_ids, max_length=32, attention_mask=None, prompt_length=1, kv_cache_dtype=None, weight_dtype=None):
         """encoder output, cross K / V and empty self-attention caches of capacity max_length + prompt_length (generation.DecodeState);
-        kv_cache_dtype="fp8": the caches as e4m3fn bytes plus one fp32 scale per row and head"""
+        kv_cache_dtype="fp8": the caches as e4m3fn bytes plus one fp32 scale per row and head; weight_dtype="fp8": the state's steps
+        read the FP8 decoder weights of `quantize_decoder_weights`"""
         from .generation import init_decode_state
-        return init_decode_state(self, input_ids, max_length, attention_mask, prompt_length=prompt_length, kv_cache_dtype=kv_cache_dtype)
+        return init_decode_state(self, input_ids, max_length, attention_mask, prompt_length=prompt_length, kv_cache_dtype=kv_cache_dtype,
+                                 weight_dtype=weight_dtype)
+
+    def quantize_decoder_weights(self):
+        """the FP8 (e4m3fn bytes + one fp32 scale per output row) copies of the decoder weights a cached step reads, built once and
+        kept on the model; rebuilt when a source weight changed (w8.quantize_decoder_weights)"""
+        from .w8 import quantize_decoder_weights
+        return quantize_decoder_weights(self)
 
     def decode_chunk(self, state, token_ids, logits="all", chunk_seqlens=None):
         """M tokens per row (B, M) through the cached decoder in one step -> logits (B, M, vocab) ("all"), (B, vocab) ("last") or
@@ -513,7 +521,7 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
                  decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
                  decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
                  encoder_repetition_penalty=1.0, encoder_no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
-                 forced_bos_token_id=None, forced_eos_token_id=None):
+                 forced_bos_token_id=None, forced_eos_token_id=None, weight_dtype=None):
         """greedy (or, with do_sample=True, temperature / top-k / top-p sampled) decoding with a KV cache; returns what the
         reference's generate returns; num_beams > 1: HF's beam search; repetition_penalty / no_repeat_ngram_size / min_length /
         suppress_tokens / encoder_repetition_penalty / encoder_no_repeat_ngram_size / bad_words_ids / min_new_tokens /
@@ -521,7 +529,8 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         in one chunk step; assistant_model: speculative greedy decoding, num_assistant_tokens drafted per round and verified in one
         chunk step; attention_mask / decoder_attention_mask: right-padded inputs and ragged decoder prompts; kv_cache_dtype="fp8": the K / V
         caches as e4m3fn bytes plus per-row scales, in every mode; prompt_lookup_num_tokens / max_matching_ngram_size: speculative greedy
-        decoding drafted by an n-gram search of the input and the output so far, one launch per round (generation.generate)"""
+        decoding drafted by an n-gram search of the input and the output so far, one launch per round; weight_dtype="fp8": the decoder
+        weights of a step as e4m3fn bytes plus per-row scales, every projection one fused HIP launch (generation.generate)"""
         from .generation import generate
         return generate(self, input_ids, attention_mask, max_length, graph, do_sample=do_sample, temperature=temperature,
                         top_k=top_k, top_p=top_p, seed=seed, num_beams=num_beams, num_return_sequences=num_return_sequences,
@@ -534,7 +543,7 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
                         encoder_repetition_penalty=encoder_repetition_penalty,
                         encoder_no_repeat_ngram_size=encoder_no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                         min_new_tokens=min_new_tokens, forced_bos_token_id=forced_bos_token_id,
-                        forced_eos_token_id=forced_eos_token_id)
+                        forced_eos_token_id=forced_eos_token_id, weight_dtype=weight_dtype)
 
 
 def allreduce_gradients(model: nn.Module, group=None, average=True):

@@ -53,6 +53,10 @@ None take the code path above.
 FP8 KV caches (`kv_cache_dtype="fp8"`): the self-attention caches are allocated as e4m3fn bytes plus one fp32 scale
 per (row, position, head), the cross-attention K / V are quantised once by `quantize_kv`, and every decode launch reads bytes and
 scales and quantises the rows it appends: (D + 4) / (2 D) of the cache bytes, in every mode above.  None: nothing here runs.
+
+FP8 weights (`weight_dtype="fp8"`): the decoder weights a step reads are quantised once per model (flasht5_amd/w8.py)
+and the state's steps run `_decoder_blocks_w8` beside `_decoder_blocks`: each projection one `w8_linear` launch with its RMSNorm
+in front and its residual add behind, 9 launches per block where the default path makes about 19.  None: nothing here runs.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -81,6 +85,7 @@ class DecodeState:
     self_v_scale: Optional[List[torch.Tensor]] = None
     cross_k_scale: Optional[List[torch.Tensor]] = None
     cross_v_scale: Optional[List[torch.Tensor]] = None
+    w8: Optional[object] = None   # FP8 weights (weight_dtype="fp8"): the model's w8.DecoderW8; the step then runs `_decoder_blocks_w8`
 
     def scales(self, i):
         """forward_decode's keywords for layer i -> (self-attention's, cross-attention's); empty without FP8 caches"""
@@ -238,7 +243,8 @@ def encode(model, input_ids, pad=None):
 
 
 @torch.no_grad()
-def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1, prompt_length=1, kv_cache_dtype=None):
+def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1, prompt_length=1, kv_cache_dtype=None,
+                      weight_dtype=None):
     """Run the encoder, project every decoder layer's cross-attention K / V once and allocate self-attention caches of capacity
     `max_length + prompt_length` (a decoder prompt of `prompt_length` tokens, the start token included, then max_length new ones).
     `attention_mask` (B, L), right-padded, is applied: it is validated with one host read before the encoder runs
@@ -247,8 +253,12 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     num_beams > 1: the encoder and the cross K / V stay at B rows; the self-attention caches, the lengths and the history table
     get B * num_beams rows (row b * k + j: beam j of input b).
     kv_cache_dtype="fp8" (alias "fp8_e4m3"): the self-attention caches are float8_e4m3fn bytes with zeroed fp32 scales beside them,
-    the cross-attention K / V are quantised once (`quantize_kv`); anything but these and None raises before the encoder runs."""
+    the cross-attention K / V are quantised once (`quantize_kv`); anything but these and None raises before the encoder runs.
+    weight_dtype="fp8" (alias "fp8_e4m3"): the state's steps read the model's FP8 decoder weights
+    (`quantize_decoder_weights`, built once per model) through `w8_linear`; checked, like the decoder's dtype and shapes, before
+    the encoder runs."""
     fp8 = check_kv_cache_dtype(kv_cache_dtype, "init_decode_state")
+    w8 = _check_weight_dtype(model, weight_dtype, "init_decode_state")
     _check_supported(model)
     first = model.decoder.block[0].self_attention_layer.self_attention
     cap = int(max_length) + int(prompt_length)
@@ -290,6 +300,9 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     state = DecodeState(enc, self_k, self_v, cross_k, cross_v, torch.zeros((Bk,), dtype=torch.int32, device=dev), pb, cap)
     if fp8:
         state.self_k_scale, state.self_v_scale, state.cross_k_scale, state.cross_v_scale = sks, svs, cks, cvs
+    if w8:
+        from .w8 import quantize_decoder_weights
+        state.w8 = quantize_decoder_weights(model)
     if num_beams > 1:
         state.cross_batch_idx = torch.arange(Bk, dtype=torch.int32, device=dev) // int(num_beams)
         state.row_batch = torch.zeros((Bk, cap), dtype=torch.int32, device=dev)
@@ -316,6 +329,60 @@ def _decoder_blocks(model, state, h, chunk_seqlens=None):
     return h
 
 
+def _check_weight_dtype(model, weight_dtype, what="generate"):
+    """None, or "fp8" / "fp8_e4m3" -> whether the step reads FP8 decoder weights; with them the decoder's dtype and shapes are
+    checked too (host only: nothing has run yet)"""
+    from .w8 import check_decoder_weights, check_weight_dtype
+    if not check_weight_dtype(weight_dtype, what):
+        return False
+    check_decoder_weights(model, what)
+    return True
+
+
+def _decoder_blocks_w8(model, state, h, chunk_seqlens=None):
+    """`_decoder_blocks` over the FP8 weights of `state.w8`: per block norm + qkv, self-attention, o + residual,
+    norm + q, cross-attention, o + residual, norm + wi, the gated activation, wo + residual -- every projection ONE `w8_linear`
+    launch with its RMSNorm in front and its residual add behind"""
+    from . import w8 as w8m   # (looked up per call: the entry point can be wrapped)
+    from .gated_act import gated_act_packed
+    pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
+    B, M = h.shape[:2]
+    for i, (blk, lw) in enumerate(zip(model.decoder.block, state.w8.layers)):
+        sa, ca, ff = blk.self_attention_layer, blk.cross_attention_layer, blk.ff_layer
+        ssc, csc = state.scales(i)
+        att = sa.self_attention
+        H, D, inner = att.n_heads, att.key_value_proj_dim, att.inner_dim
+        qkv = w8m.w8_linear(h, *lw.qkv, norm_weight=sa.layer_norm.weight, eps=sa.layer_norm.variance_epsilon)
+        q, k, v = (qkv[..., j * inner:(j + 1) * inner].view(B, M, H, D) for j in range(3))
+        o = att.attend_decode(q, k, v, state.self_k[i], state.self_v[i], state.cache_seqlens, position_bias=state.position_bias,
+                              position=pos, cache_row_batch=state.row_batch, chunk_seqlens=chunk_seqlens, **ssc)
+        h = w8m.w8_linear(o, *lw.self_o, residual=h)
+        att = ca.cross_attention
+        q = w8m.w8_linear(h, *lw.cross_q, norm_weight=ca.layer_norm.weight, eps=ca.layer_norm.variance_epsilon).view(B, M, H, D)
+        o = att.attend_decode(q, None, None, state.cross_k[i], state.cross_v[i], None, position=pos,
+                              cache_batch_idx=state.cross_batch_idx, cross_seqlens=state.cross_seqlens, chunk_seqlens=chunk_seqlens,
+                              **csc)
+        h = w8m.w8_linear(o, *lw.cross_o, residual=h)
+        g = w8m.w8_linear(h, *lw.wi, norm_weight=ff.layer_norm.weight, eps=ff.layer_norm.variance_epsilon)
+        t = gated_act_packed(g, ff.act.act_name) if ff.act.glu else ff.act.act(g)
+        h = w8m.w8_linear(t, *lw.wo, residual=h)
+    return h
+
+
+def _blocks(model, state, h, chunk_seqlens=None):
+    """the decoder pass of this state: the default loop, or the FP8-weight one"""
+    return (_decoder_blocks if state.w8 is None else _decoder_blocks_w8)(model, state, h, chunk_seqlens)
+
+
+def _head(model, state, h):
+    """final norm + lm_head of the rows of h"""
+    if state.w8 is None:
+        return model.lm_head(model.decoder.final_layer_norm(h))
+    from . import w8 as w8m
+    ln = model.decoder.final_layer_norm
+    return w8m.w8_linear(h, *state.w8.lm_head, norm_weight=ln.weight, eps=ln.variance_epsilon)
+
+
 @torch.no_grad()
 def decode_step(model, state, token_ids):
     """one token per batch row (B,) or (B, 1) through the decoder against the caches -> logits (B, vocab) of the next position;
@@ -325,6 +392,10 @@ def decode_step(model, state, token_ids):
         raise ValueError(f"decode_step: the caches hold {state.capacity} positions and all of them are used (init_decode_state with a "
                          "larger max_length)")
     state.steps += 1
+    if state.w8 is not None:
+        h = _decoder_blocks_w8(model, state, _embed(model.shared, token_ids.reshape(B, 1)))
+        state.cache_seqlens.add_(1)
+        return _head(model, state, h)[:, 0]
     h = _decoder_blocks(model, state, _embed(model.shared, token_ids.reshape(B, 1)))
     h = model.decoder.final_layer_norm(h)
     state.cache_seqlens.add_(1)
@@ -360,16 +431,16 @@ def decode_chunk(model, state, token_ids, logits="all", chunk_seqlens=None):
                 chunk_seqlens.device != state.cache_seqlens.device):
             raise ValueError(f"decode_chunk: chunk_seqlens must be a ({B},) int32 tensor on {state.cache_seqlens.device}")
     state.steps += M
-    h = _decoder_blocks(model, state, _embed(model.shared, token_ids), chunk_seqlens)
+    h = _blocks(model, state, _embed(model.shared, token_ids), chunk_seqlens)
     state.cache_seqlens.add_(M if chunk_seqlens is None else chunk_seqlens.clamp(0, M))
     if logits == "none":
         return None
     if logits == "last":
         if chunk_seqlens is not None:   # row b's own last token, selected on the device
             at = (chunk_seqlens.long() - 1).clamp(0, M - 1).view(B, 1, 1).expand(B, 1, h.shape[-1])
-            return model.lm_head(model.decoder.final_layer_norm(h.gather(1, at)))[:, 0]
-        return model.lm_head(model.decoder.final_layer_norm(h[:, -1:]))[:, 0]
-    return model.lm_head(model.decoder.final_layer_norm(h))
+            return _head(model, state, h.gather(1, at))[:, 0]
+        return _head(model, state, h[:, -1:])[:, 0]
+    return _head(model, state, h)
 
 
 def _check_prompt(model, input_ids, decoder_input_ids, num_beams, decoder_attention_mask=None):
@@ -471,11 +542,12 @@ def _beam_step(model, state, tok, bs, opts, proc=None):
 
 
 def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, length_penalty, early_stopping, return_scores,
-                   proc=None, kv_cache_dtype=None):
+                   proc=None, kv_cache_dtype=None, weight_dtype=None):
     from .beam import new_state, keep_going
     B = input_ids.shape[0]
     dev = input_ids.device
-    state = init_decode_state(model, input_ids, max_length, attention_mask, num_beams=k, kv_cache_dtype=kv_cache_dtype)
+    state = init_decode_state(model, input_ids, max_length, attention_mask, num_beams=k, kv_cache_dtype=kv_cache_dtype,
+                              weight_dtype=weight_dtype)
     bs = new_state(B, k, int(max_length) + 1, state.capacity, dev)
     proc = _proc_on_device(proc, dev, input_ids, attention_mask, None, k)
     bs.cache_row_batch = state.row_batch  # (one table: the decode kernel reads it, the beam step reorders it)
@@ -498,7 +570,7 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
              decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
              decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
              encoder_repetition_penalty=1.0, encoder_no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
-             forced_bos_token_id=None, forced_eos_token_id=None):
+             forced_bos_token_id=None, forced_eos_token_id=None, weight_dtype=None):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -598,8 +670,19 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     counts the tokens the lookup proposed for unfinished rows, `accepted` those of them that became output).  Rejected on the
     host before the encoder runs: an assistant_model beside it, num_beams > 1, any active logits processor, a
     ragged decoder prompt, a non-int or out-of-range prompt_lookup_num_tokens / max_matching_ngram_size, a model the decode
-    path refuses, RoPE at B > 1, and a cache beyond the rotary tables."""
+    path refuses, RoPE at B > 1, and a cache beyond the rotary tables.
+
+    `weight_dtype`: None (everything above, unchanged: the same launches, the same bits) or "fp8" (alias "fp8_e4m3"):
+    the decoder weights a cached step reads -- self-attention [Wq; Wk; Wv] and o, cross-attention Wq and o, [wi_0; wi_1], wo and
+    lm_head, the assistant's too -- are read as float8_e4m3fn bytes with one fp32 scale per output row, quantised once per model
+    (`model.quantize_decoder_weights()`; the 16-bit parameters stay, the encoder and the cross-attention Wk / Wv use them).  Every
+    projection of a step is then ONE `w8_linear` launch with its RMSNorm in front and its residual add behind.  All modes,
+    kv_cache_dtype and graph=True work with it; the tokens can differ from the default's where two logits are within the
+    quantisation error.  Refused with ValueError before an encoder runs: any other value, a decoder whose weights are fp32 (or
+    of mixed dtypes), and weight shapes outside the kernel's contract (input widths multiples of 64 up to 16384, output widths
+    multiples of 8)."""
     check_kv_cache_dtype(kv_cache_dtype)
+    _check_weight_dtype(model, weight_dtype)
     from .beam import check_args as check_beam_args
     check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample)
     P = _check_prompt(model, input_ids, decoder_input_ids, num_beams, decoder_attention_mask)
@@ -627,18 +710,20 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
         else:
             check_generate_args(model, assistant_model, input_ids, max_length, num_assistant_tokens, P, do_sample, num_beams,
                                 proc is not None)
+            _check_weight_dtype(assistant_model, weight_dtype, "generate: assistant_model")
         return speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph,
                                     prompt_lookup_num_tokens if lookup else num_assistant_tokens, P, decoder_input_ids,
                                     bool(return_stats), kv_cache_dtype, lookup_ngram=max_matching_ngram_size if lookup else None,
-                                    sampling=_sampling(do_sample, temperature, top_k, top_p, seed))
+                                    sampling=_sampling(do_sample, temperature, top_k, top_p, seed), weight_dtype=weight_dtype)
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
-                              early_stopping, return_scores, proc, kv_cache_dtype)
+                              early_stopping, return_scores, proc, kv_cache_dtype, weight_dtype)
     proc = _proc_on_device(proc, input_ids.device, input_ids, attention_mask, dec_pad)
     sampling = _sampling(do_sample, temperature, top_k, top_p, seed)
     B = input_ids.shape[0]
     dev = input_ids.device
-    state = init_decode_state(model, input_ids, max_length, attention_mask, prompt_length=P, kv_cache_dtype=kv_cache_dtype)
+    state = init_decode_state(model, input_ids, max_length, attention_mask, prompt_length=P, kv_cache_dtype=kv_cache_dtype,
+                              weight_dtype=weight_dtype)
     labels = torch.zeros((B, state.capacity), dtype=torch.long, device=dev)
     tok = torch.zeros((B,), dtype=torch.long, device=dev)
     seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)

@@ -385,7 +385,7 @@ def check_lookup_generate_args(model, input_ids, max_length, prompt_lookup_num_t
 
 @torch.no_grad()
 def speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, prompt_length,
-                         decoder_input_ids, return_stats, kv_cache_dtype=None, lookup_ngram=None, sampling=None):
+                         decoder_input_ids, return_stats, kv_cache_dtype=None, lookup_ngram=None, sampling=None, weight_dtype=None):
     """`generate`'s speculative loop (the arguments are checked already): per round the drafter, one chunk step of the target
     and the verification kernel, then ONE host read (`seen_eos.all()`), as the plain loop does once per token.  The drafter is
     the assistant model (gamma + 1 draft steps) or, with `assistant_model=None`, the prompt lookup (ONE launch over
@@ -399,6 +399,8 @@ def speculative_generate(model, assistant_model, input_ids, attention_mask, max_
     B, dev = input_ids.shape[0], input_ids.device
     # capacity P + max_length + gamma + 1: a row at its last free column still appends a whole chunk before the roll-back
     kv = {} if kv_cache_dtype is None else dict(kv_cache_dtype=kv_cache_dtype)   # (both models' caches take the dtype)
+    if weight_dtype is not None:   # (and both decoders the weight dtype)
+        kv["weight_dtype"] = weight_dtype
     state = init_decode_state(model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P, **kv)
     dstate = None if lookup else init_decode_state(assistant_model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P, **kv)
     labels = torch.zeros((B, P + T_max), dtype=torch.long, device=dev)

@@ -1073,6 +1073,57 @@ size_t fat5_sizeof_ul2_params(void);
 int fat5_ul2_collate(const fat5_ul2_params* p, void* hip_stream);
 
 /*
+ * FP8 weights: weight-only e4m3fn linear layers for cached decoding (w8_kernels.h; tests/w8_ref.py restates this).
+ *   - A weight W (N, K), fp32 / fp16 / bf16, is stored as w8 (N, K) OCP e4m3fn bytes (torch.float8_e4m3fn) plus scale (N,) fp32:
+ *     one scale per output row n, taken over its K elements by the rule of "FP8 KV cache" above (s = amax / 448, s = 1 for a zero
+ *     row, software round-to-nearest-even, a non-finite row has s = +inf and reads back as NaN).  Bytes and scales equal that rule
+ *     bit for bit.
+ *   - Legal shapes: K % 64 == 0 with 64 <= K <= 16384, N % 8 == 0, any R >= 0; R == 0 or N == 0 launches nothing.  Anything else,
+ *     a NULL or misaligned pointer or stride: FAT5_EINVAL before any device work.
+ *   - fat5_w8_linear:  y[r, n] = round_T( scale[n] * sum_k fp32(xin[r, k]) * fp32(w8[n, k]) ),  T = fp16 | bf16, fp32 accumulation in
+ *     a fixed order that does not depend on R, N or the grid (bitwise reproducible, also under graph replay).
+ *       norm_weight given:  xin[r, k] = round_T(fp32(x[r, k]) * rstd_r * fp32(norm_weight[k])),  rstd_r = 1 / sqrt(mean_k x^2 + eps),
+ *                           bit for bit what fat5_rmsnorm_fwd writes for (x, norm_weight) of dtype T; otherwise xin = x.
+ *       residual given:     out[r, n] = round_T(fp32(y[r, n]) + fp32(residual[r, n])) with y already rounded to T.
+ *     x, residual and y: 16-byte aligned bases, row strides multiples of 8 elements (y and residual: 2-byte alignment of each
+ *     element is all the kernel needs, the rule is kept uniform); w8: 8-byte aligned base, row stride a multiple of 8; y may alias
+ *     residual (each element is read and written by one lane), not x.
+ */
+typedef struct fat5_w8_quant_params {
+  int64_t N;                  /* weight rows (output features), N % 8 == 0 */
+  int32_t K;                  /* elements per row, K % 64 == 0, 64..16384 */
+  int32_t dtype;              /* FAT5_F32 | FAT5_F16 | FAT5_BF16: w */
+  const void* w;              /* (N, K), row stride w_stride elements (a multiple of 8), 16-byte aligned */
+  int64_t w_stride;
+  void* out;                  /* (N, K) e4m3fn bytes, row stride out_stride (a multiple of 8), 8-byte aligned */
+  int64_t out_stride;
+  float* scale;               /* (N,) contiguous */
+} fat5_w8_quant_params;
+size_t fat5_sizeof_w8_quant_params(void);
+int fat5_w8_quantize(const fat5_w8_quant_params* p, void* hip_stream);
+
+typedef struct fat5_w8_linear_params {
+  int64_t R;                  /* rows of x */
+  int64_t N;
+  int32_t K;
+  int32_t dtype;              /* FAT5_F16 | FAT5_BF16: x, norm_weight, residual, y */
+  const void* x;              /* (R, K), row stride x_stride */
+  int64_t x_stride;
+  const void* w8;             /* (N, K) e4m3fn bytes, row stride w_stride */
+  int64_t w_stride;
+  const float* scale;         /* (N,) */
+  const void* norm_weight;    /* (K,) or NULL */
+  float eps;                  /* with norm_weight: finite, >= 0 */
+  int32_t reserved;           /* 0 */
+  const void* residual;       /* (R, N), row stride residual_stride, or NULL */
+  int64_t residual_stride;
+  void* y;                    /* (R, N), row stride y_stride */
+  int64_t y_stride;
+} fat5_w8_linear_params;
+size_t fat5_sizeof_w8_linear_params(void);
+int fat5_w8_linear(const fat5_w8_linear_params* p, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)
