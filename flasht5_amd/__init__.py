@@ -39,5 +39,8 @@ from .attention_module import FlashT5Attention  # noqa: E402
 from .modules import FlashT5LayerNorm, FlashT5CrossEntropyLoss  # noqa: E402
 from .adamw_scaled import AdamWScale  # noqa: E402
 from .fat5_step import FAT5Config, FAT5ForConditionalGeneration, allreduce_gradients, train_step, GraphedTrainStep  # noqa: E402
+from .pooling import sequence_pool  # noqa: E402
+from .heads import (FAT5EncoderModel, FAT5ForTokenClassification, FAT5ForSequenceClassification,  # noqa: E402
+                    FAT5ForQuestionAnswering)
 
 __version__ = "0.1.0"

@@ -247,6 +247,22 @@ class W8LinearParams(ctypes.Structure):
     ]
 
 
+POOL_EOS, POOL_FIRST, POOL_LAST, POOL_MEAN = 0, 1, 2, 3  # fat5_pool_mode
+
+
+class SeqPoolParams(ctypes.Structure):
+    """Mirror of `fat5_seq_pool_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("mode", ctypes.c_int32), ("dtype", ctypes.c_int32), ("nseq", ctypes.c_int32), ("L", ctypes.c_int32),
+        ("total", ctypes.c_int64), ("d", ctypes.c_int64), ("eos_token_id", ctypes.c_int64),
+        ("hidden", ctypes.c_void_p), ("hidden_row_stride", ctypes.c_int64), ("hidden_batch_stride", ctypes.c_int64),
+        ("cu_seqlens", ctypes.c_void_p), ("seqlens", ctypes.c_void_p), ("input_ids", ctypes.c_void_p),
+        ("ids_batch_stride", ctypes.c_int64), ("pooled", ctypes.c_void_p), ("pooled_stride", ctypes.c_int64),
+        ("position", ctypes.c_void_p), ("found", ctypes.c_void_p), ("dpooled", ctypes.c_void_p), ("dpooled_stride", ctypes.c_int64),
+        ("dhidden", ctypes.c_void_p), ("dhidden_row_stride", ctypes.c_int64), ("dhidden_batch_stride", ctypes.c_int64),
+    ]
+
+
 class DropoutDesc(ctypes.Structure):
     """Mirror of `fat5_dropout_desc` (include/fat5.h) -- field order must match exactly."""
     _fields_ = [
@@ -277,6 +293,7 @@ EXPORTS = (
     "fat5_ul2_collate", "fat5_sizeof_ul2_params",
     "fat5_w8_quantize", "fat5_sizeof_w8_quant_params", "fat5_w8_linear", "fat5_sizeof_w8_linear_params",
     "fat5_dropout", "fat5_dropout_add_rmsnorm_fwd", "fat5_dropout_add_rmsnorm_bwd", "fat5_sizeof_dropout_desc",
+    "fat5_seq_pool_fwd", "fat5_seq_pool_bwd", "fat5_sizeof_seq_pool_params",
 )
 
 _lib = None
@@ -453,6 +470,13 @@ def load():
         size_fn.restype = ctypes.c_size_t
         if size_fn() != ctypes.sizeof(struct):
             raise ImportError(f"{name} layout mismatch: library {size_fn()} B, binding {ctypes.sizeof(struct)} B")
+    for fn in (lib.fat5_seq_pool_fwd, lib.fat5_seq_pool_bwd):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(SeqPoolParams), ctypes.c_void_p]
+    lib.fat5_sizeof_seq_pool_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_seq_pool_params() != ctypes.sizeof(SeqPoolParams):
+        raise ImportError(f"fat5_seq_pool_params layout mismatch: library {lib.fat5_sizeof_seq_pool_params()} B, "
+                          f"binding {ctypes.sizeof(SeqPoolParams)} B")
     dd = ctypes.POINTER(DropoutDesc)
     lib.fat5_dropout.restype = ctypes.c_int
     lib.fat5_dropout.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, dd, i32, vp]

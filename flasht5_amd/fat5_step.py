@@ -18,7 +18,8 @@ Dropout (`dropout_rate`, 0 in every reference pre-training config, 0.1 in fine-t
 kinds of places with Philox masks recomputed inside HIP kernels (flasht5_amd/dropout.py): nothing is stored, and a
 captured `GraphedTrainStep` draws new masks at every replay because the step counter lives in device memory.
 
-This is the step DRIVER of the hot path, not a model zoo: no heads, HF plumbing or checkpoint conversion.  Data parallelism = one process per GPU; `allreduce_gradients` is the step's one
+This is the step DRIVER of the hot path, not a model zoo: no HF plumbing or checkpoint conversion (the encoder-only models and
+their fine-tuning heads are built on `FAT5Stack` in heads.py).  Data parallelism = one process per GPU; `allreduce_gradients` is the step's one
 exchange (RCCL over xGMI): a single flat fp32 all-reduce that carries the two `(32, H)` relative-position tables first.
 """
 import math
@@ -70,6 +71,9 @@ class FAT5Config:
     dropout_rate: float = 0.0              # the reference's six dropout sites (modeling_flash_t5.py :124/:143, :163, :316, :342, :440, :460), training only
     dropout_seed: Optional[int] = None     # the Philox key of the masks; None: drawn from torch's default CPU generator when the model is built
     is_decoder: bool = False
+    num_labels: int = 2                    # the encoder-only heads (heads.py): classes of the classifiers; the QA head needs 2
+    classifier_dropout: float = 0.0        # the heads' own dropout sites (training only)
+    eos_token_id: int = 1                  # FAT5ForSequenceClassification pools the row of the last <eos>
 
     def __post_init__(self):
         if self.position_encoding_type == "FIRE" and self.attention_type == "fat5_rpe":
@@ -77,6 +81,10 @@ class FAT5Config:
                              "Toeplitz once a row passes the threshold T, so fat5_rpe cannot carry it")
         if not 0.0 <= float(self.dropout_rate) < 1.0:
             raise ValueError(f"dropout_rate = {self.dropout_rate} outside [0, 1)")
+        if not 0.0 <= float(self.classifier_dropout) < 1.0:
+            raise ValueError(f"classifier_dropout = {self.classifier_dropout} outside [0, 1)")
+        if int(self.num_labels) < 1:
+            raise ValueError(f"num_labels = {self.num_labels} must be at least 1")
         if self.dropout_rate > 0 and self.fuse_norm_linear:
             raise ValueError("dropout_rate > 0 with fuse_norm_linear: that path's residual add is a GEMM epilogue, which cannot carry "
                              "a dropout mask (use fuse_add_norm, whose pre-norm kernel applies it, or the plain path)")
@@ -324,6 +332,28 @@ class FAT5Stack(nn.Module):  # :394-464
         return self.final_layer_norm(h)
 
 
+@torch.no_grad()
+def init_stack_weights(root, c):
+    """the reference's `_init_weights` (:482-517, Mesh-TF style, factor 1.0) for every norm, feed-forward and attention module under
+    `root`, in module order (the random draws of a model are taken in that order)"""
+    for m in root.modules():
+        if isinstance(m, FlashT5LayerNorm):
+            m.weight.fill_(1.0)
+        elif isinstance(m, FAT5GatedAct):
+            for w in ((m.wi_0, m.wi_1) if m.glu else (m.wi,)):
+                w.weight.normal_(0.0, c.d_model ** -0.5)
+        elif isinstance(m, FAT5LayerFF):
+            m.wo.weight.normal_(0.0, c.d_ff ** -0.5)
+        elif isinstance(m, FlashT5Attention):
+            m.Wq.weight.normal_(0.0, (c.d_model * c.d_kv) ** -0.5)
+            m.Wk.weight.normal_(0.0, c.d_model ** -0.5)
+            m.Wv.weight.normal_(0.0, c.d_model ** -0.5)
+            m.o.weight.normal_(0.0, (c.num_heads * c.d_kv) ** -0.5)
+            # (RoPE has no table; FIRE keeps its own initialisation, which the reference's _init_weights does not touch)
+            if m.pe_encoding is not None and hasattr(m.pe_encoding, "relative_attention_bias"):
+                m.pe_encoding.relative_attention_bias.weight.normal_(0.0, c.d_model ** -0.5)
+
+
 class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; cached greedy / sampled generation in generation.py)
     def __init__(self, config: FAT5Config):
         super().__init__()
@@ -367,22 +397,7 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         c = self.config
         self.shared.weight.normal_(0.0, 1.0)
         self.lm_head.weight.normal_(0.0, c.d_model ** -0.5)
-        for m in self.modules():
-            if isinstance(m, FlashT5LayerNorm):
-                m.weight.fill_(1.0)
-            elif isinstance(m, FAT5GatedAct):
-                for w in ((m.wi_0, m.wi_1) if m.glu else (m.wi,)):
-                    w.weight.normal_(0.0, c.d_model ** -0.5)
-            elif isinstance(m, FAT5LayerFF):
-                m.wo.weight.normal_(0.0, c.d_ff ** -0.5)
-            elif isinstance(m, FlashT5Attention):
-                m.Wq.weight.normal_(0.0, (c.d_model * c.d_kv) ** -0.5)
-                m.Wk.weight.normal_(0.0, c.d_model ** -0.5)
-                m.Wv.weight.normal_(0.0, c.d_model ** -0.5)
-                m.o.weight.normal_(0.0, (c.num_heads * c.d_kv) ** -0.5)
-                # (RoPE has no table; FIRE keeps its own initialisation, which the reference's _init_weights does not touch)
-                if m.pe_encoding is not None and hasattr(m.pe_encoding, "relative_attention_bias"):
-                    m.pe_encoding.relative_attention_bias.weight.normal_(0.0, c.d_model ** -0.5)
+        init_stack_weights(self, c)
 
     def _shift_right(self, labels):  # HF T5 convention used by the reference (:713-714)
         c = self.config

@@ -1124,6 +1124,66 @@ size_t fat5_sizeof_w8_linear_params(void);
 int fat5_w8_linear(const fat5_w8_linear_params* p, void* hip_stream);
 
 /*
+ * Sequence pooling (pool_kernels.h): per-token hidden states to one vector per sequence, and its gradient.
+ * Layouts -- at most one of cu_seqlens / seqlens is given:
+ *   packed  (cu_seqlens != NULL): hidden is (total, d), rows hidden_row_stride elements apart; sequence b owns the rows
+ *           [cu_seqlens[b], cu_seqlens[b + 1]), every entry read as clamped to [0, total] (an end in front of its start: empty);
+ *   padded  (cu_seqlens == NULL): hidden is (nseq, L, d), batches hidden_batch_stride and rows hidden_row_stride elements apart;
+ *           sequence b owns the first len_b rows of batch b, len_b = seqlens[b] read as clamped to [0, L], or L without seqlens.
+ * input_ids (int64, needed by FAT5_POOL_EOS only) holds one id per hidden row: (total,) contiguous, or (nseq, L) with rows
+ * ids_batch_stride elements apart.  Ids outside a sequence's own rows are never read: an EOS under the padding, or one that
+ * belongs to the packed neighbour, is not seen.
+ * Forward, ONE launch, grid nseq x ceil(d / 64):
+ *   FAT5_POOL_EOS    position[b] = the last j < len_b with input_ids[b][j] == eos_token_id, found[b] = 1; without one
+ *                    position[b] = len_b - 1 and found[b] = 0;
+ *   FAT5_POOL_FIRST  position[b] = 0;           FAT5_POOL_LAST  position[b] = len_b - 1;      found[b] = 1 (len_b > 0)
+ *   these three:     pooled[b] = the row at position[b], its bits unchanged;
+ *   FAT5_POOL_MEAN   pooled[b][c] = round_T(S / fp32(len_b)), S the fp32 sum of the column's len_b values in an order that the
+ *                    shape alone fixes (token j goes to partial j mod 16, the partials are added in order 0 .. 15; no atomics),
+ *                    one IEEE division; position[b] = -1, found[b] = 1 (len_b > 0).
+ *   An empty sequence: a zero row, position -1, found 0.  nseq == 0 or d == 0 launches nothing.
+ * Backward, ONE launch that writes every element of dhidden -- (total, d) or (nseq, L, d), strides dhidden_row_stride /
+ * dhidden_batch_stride -- by exactly one thread, with no memset in front and no atomics: row j of sequence b gets dpooled[b]
+ * (bits unchanged) if j == position[b] (the forward's output) for the three gather modes, round_T(fp32(dpooled[b][c]) / fp32(len_b))
+ * for FAT5_POOL_MEAN, and zeros on every row that no sequence owns.  The row's sequence is found from cu_seqlens on the device.
+ * 16-byte accesses when d, every stride and every base allow them, element accesses otherwise.  Nothing is read by the host.
+ * Rejected with FAT5_EINVAL before anything is launched: NULL params, a mode or dtype outside its enum, nseq < 0, d outside
+ * [0, 2^22], cu_seqlens and seqlens together, total or L outside [0, 2^31 - 1], nseq * L >= 2^40, a negative stride,
+ * FAT5_POOL_EOS without input_ids, a NULL or misaligned pointer (the element size for hidden / pooled / dpooled / dhidden, 8 bytes
+ * for input_ids, 4 for the int32 arrays).
+ */
+enum fat5_pool_mode { FAT5_POOL_EOS = 0, FAT5_POOL_FIRST = 1, FAT5_POOL_LAST = 2, FAT5_POOL_MEAN = 3 };
+typedef struct fat5_seq_pool_params {
+  int32_t mode;                 /* enum fat5_pool_mode */
+  int32_t dtype;                /* FAT5_F32 | FAT5_F16 | FAT5_BF16: hidden, pooled, dpooled, dhidden */
+  int32_t nseq;
+  int32_t L;                    /* padded layout: rows per batch */
+  int64_t total;                /* packed layout: rows of hidden */
+  int64_t d;
+  int64_t eos_token_id;
+  const void* hidden;
+  int64_t hidden_row_stride;    /* elements */
+  int64_t hidden_batch_stride;  /* elements (padded layout) */
+  const int32_t* cu_seqlens;    /* (nseq + 1,) or NULL */
+  const int32_t* seqlens;       /* (nseq,) or NULL */
+  const int64_t* input_ids;     /* or NULL */
+  int64_t ids_batch_stride;     /* elements (padded layout) */
+  void* pooled;                 /* (nseq, d), rows pooled_stride elements apart */
+  int64_t pooled_stride;
+  int32_t* position;            /* (nseq,): written by the forward, read by the backward */
+  int32_t* found;               /* (nseq,): forward only */
+  const void* dpooled;          /* backward: (nseq, d), rows dpooled_stride elements apart */
+  int64_t dpooled_stride;
+  void* dhidden;                /* backward */
+  int64_t dhidden_row_stride;
+  int64_t dhidden_batch_stride;
+} fat5_seq_pool_params;
+/* sizeof(fat5_seq_pool_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_seq_pool_params(void);
+int fat5_seq_pool_fwd(const fat5_seq_pool_params* p, void* hip_stream);
+int fat5_seq_pool_bwd(const fat5_seq_pool_params* p, void* hip_stream);
+
+/*
  * Cross-entropy + label smoothing + z-loss.  Replaces flasht5::cross_entropy_triton_fwd / _bwd
  * (src/model/ops/cross_entropy_loss.py:164-274), single-rank path (SPLIT = False).
  *   lse = log sum exp(logits*logit_scale);  loss = lse - logit[label]  (smoothed variant :90-95)
