@@ -18,6 +18,7 @@ from .flash_attention_v2_bias import (flash_attention_v2_bias, FlashAttentionAdd
 from .rms_norm import fast_rms_layernorm, Fast_RMS_Layernorm, fused_add_rms_layernorm, FusedAddRMSLayernorm  # noqa: E402
 from .cross_entropy_loss import cross_entropy_loss, CrossEntropyLoss  # noqa: E402
 from .lm_head_cross_entropy import lm_head_cross_entropy, LMHeadCrossEntropy  # noqa: E402
+from .distillation import distillation_loss, lm_head_distillation  # noqa: E402
 from .fused_linear import rmsnorm_linear, linear_residual, RMSNormLinear, LinearResidual  # noqa: E402
 from .gated_act import gated_act, gated_act_packed  # noqa: E402
 from .dropout import dropout, dropout_add, dropout_add_rms_layernorm  # noqa: E402
@@ -39,6 +40,7 @@ from .attention_module import FlashT5Attention  # noqa: E402
 from .modules import FlashT5LayerNorm, FlashT5CrossEntropyLoss  # noqa: E402
 from .adamw_scaled import AdamWScale  # noqa: E402
 from .fat5_step import FAT5Config, FAT5ForConditionalGeneration, allreduce_gradients, train_step, GraphedTrainStep  # noqa: E402
+from .distill import DistilledFAT5  # noqa: E402
 from .pooling import sequence_pool  # noqa: E402
 from .heads import (FAT5EncoderModel, FAT5ForTokenClassification, FAT5ForSequenceClassification,  # noqa: E402
                     FAT5ForQuestionAnswering)

@@ -263,6 +263,20 @@ class SeqPoolParams(ctypes.Structure):
     ]
 
 
+class KdParams(ctypes.Structure):
+    """Mirror of `fat5_kd_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32), ("rows", ctypes.c_int64), ("n_cols", ctypes.c_int64),
+        ("logits", ctypes.c_void_p), ("row_stride", ctypes.c_int64), ("teacher_logits", ctypes.c_void_p),
+        ("teacher_row_stride", ctypes.c_int64), ("labels", ctypes.c_void_p), ("dlosses", ctypes.c_void_p), ("dloss_stride", ctypes.c_int64),
+        ("losses", ctypes.c_void_p), ("kd_losses", ctypes.c_void_p), ("z_losses", ctypes.c_void_p), ("ce_losses", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p), ("lse_student_t", ctypes.c_void_p), ("lse_teacher_t", ctypes.c_void_p),
+        ("dlogits", ctypes.c_void_p), ("dlogits_row_stride", ctypes.c_int64), ("ignore_index", ctypes.c_int64),
+        ("alpha", ctypes.c_float), ("temperature", ctypes.c_float), ("label_smoothing", ctypes.c_float), ("logit_scale", ctypes.c_float),
+        ("lse_square_scale", ctypes.c_float), ("reserved2", ctypes.c_int32),
+    ]
+
+
 class DropoutDesc(ctypes.Structure):
     """Mirror of `fat5_dropout_desc` (include/fat5.h) -- field order must match exactly."""
     _fields_ = [
@@ -294,6 +308,7 @@ EXPORTS = (
     "fat5_w8_quantize", "fat5_sizeof_w8_quant_params", "fat5_w8_linear", "fat5_sizeof_w8_linear_params",
     "fat5_dropout", "fat5_dropout_add_rmsnorm_fwd", "fat5_dropout_add_rmsnorm_bwd", "fat5_sizeof_dropout_desc",
     "fat5_seq_pool_fwd", "fat5_seq_pool_bwd", "fat5_sizeof_seq_pool_params",
+    "fat5_kd_fwd", "fat5_kd_bwd", "fat5_kd_fwd_bwd", "fat5_sizeof_kd_params",
 )
 
 _lib = None
@@ -477,6 +492,13 @@ def load():
     if lib.fat5_sizeof_seq_pool_params() != ctypes.sizeof(SeqPoolParams):
         raise ImportError(f"fat5_seq_pool_params layout mismatch: library {lib.fat5_sizeof_seq_pool_params()} B, "
                           f"binding {ctypes.sizeof(SeqPoolParams)} B")
+    for fn in (lib.fat5_kd_fwd, lib.fat5_kd_bwd, lib.fat5_kd_fwd_bwd):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(KdParams), ctypes.c_void_p]
+    lib.fat5_sizeof_kd_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_kd_params() != ctypes.sizeof(KdParams):
+        raise ImportError(f"fat5_kd_params layout mismatch: library {lib.fat5_sizeof_kd_params()} B, "
+                          f"binding {ctypes.sizeof(KdParams)} B")
     dd = ctypes.POINTER(DropoutDesc)
     lib.fat5_dropout.restype = ctypes.c_int
     lib.fat5_dropout.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, dd, i32, vp]

@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-mllvm", "-amdg
 
 # (source, object name, extra defines)
 # the C API, one unit per kernel family (helpers they share: api_common.h)
-UNITS = [(f"api_{n}.hip", f"api_{n}.o", []) for n in ("core", "attn", "rowwise", "position", "decode", "generate", "pack", "dropout", "ul2", "w8", "pool")]
+UNITS = [(f"api_{n}.hip", f"api_{n}.o", []) for n in ("core", "attn", "rowwise", "position", "decode", "generate", "pack", "dropout", "ul2", "w8", "pool", "kd")]
 for d in (32, 64, 128):
     UNITS.append(("attn_fwd_inst.hip", f"attn_fwd_d{d}.o", [f"-DFAT5_INST_D={d}"]))
     UNITS.append(("attn_bwd_inst.hip", f"attn_bwd_d{d}.o", [f"-DFAT5_INST_D={d}"]))

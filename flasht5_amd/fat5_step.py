@@ -420,14 +420,25 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         holds as many decoder as encoder segments).  With any of them the model runs over the valid tokens only:
         attention stays inside each example with positions of its own, and the mean runs over the non-ignored labels of valid
         positions.  Without a decoder-side argument, row b's decoder length is max(1, 1 + the last index with labels != -100)."""
-        if attention_mask is not None or decoder_attention_mask is not None or segment_ids is not None or decoder_segment_ids is not None:
-            packed = self._pack(input_ids, labels, attention_mask, decoder_attention_mask, segment_ids, decoder_segment_ids)
-            if packed is not None:   # (None: nothing is padded and no row holds two examples -- the code below, bit for bit)
-                return self._forward_packed(*packed)
+        return self._loss(*self._decoder_states(self._plan(input_ids, labels, attention_mask, decoder_attention_mask, segment_ids,
+                                                           decoder_segment_ids), input_ids, labels))
+
+    def _plan(self, input_ids, labels, attention_mask=None, decoder_attention_mask=None, segment_ids=None, decoder_segment_ids=None):
+        """`_pack`'s plan for a batch with padding masks or segment ids; None without them, or when they describe a batch in which
+        nothing is padded and no row holds two examples (the dense path, bit for bit)"""
+        if attention_mask is None and decoder_attention_mask is None and segment_ids is None and decoder_segment_ids is None:
+            return None
+        return self._pack(input_ids, labels, attention_mask, decoder_attention_mask, segment_ids, decoder_segment_ids)
+
+    def _decoder_states(self, packed, input_ids, labels):
+        """the forward up to the lm_head -> (decoder hidden states, the labels the loss sees): over the valid tokens of `packed`
+        (a `_plan` result; any model with this vocabulary can run over another's plan), or over the whole batch when it is None"""
+        if packed is not None:
+            return self._packed_states(*packed)
         drop = self._drop()
         enc = self.encoder(input_ids, drop=drop)
         dec = self.decoder(self._shift_right(labels), encoder_hidden_states=enc, drop=drop)
-        return self._loss(dec, labels)
+        return dec, labels
 
     def _loss(self, dec, labels):
         if self.config.fuse_lm_head_ce:
@@ -489,8 +500,12 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         return ep, dp, input_ids, labels
 
     def _forward_packed(self, ep, dp, input_ids, labels):
-        """the loss over the valid tokens only: ids and labels gathered through the plans' indices, both stacks over cu_seqlens,
-        the encoder output left packed for the cross-attention, the loss on the packed rows"""
+        """the loss over the valid tokens only: the loss on the packed rows of `_packed_states`"""
+        return self._loss(*self._packed_states(ep, dp, input_ids, labels))
+
+    def _packed_states(self, ep, dp, input_ids, labels):
+        """ids and labels gathered through the plans' indices, both stacks over cu_seqlens, the encoder output left packed for
+        the cross-attention -> (decoder hidden states (1, total_dec, d_model), labels (1, total_dec))"""
         from .packing import Packed
         c = self.config
         ids = input_ids.reshape(-1).index_select(0, ep.index).unsqueeze(0)      # (1, total_enc)
@@ -503,7 +518,7 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         enc = self.encoder(ids, packing=Packed(ep.cu_seqlens, ep.max_seqlen), drop=drop)
         dec = self.decoder(shifted, encoder_hidden_states=enc,
                            packing=Packed(dp.cu_seqlens, dp.max_seqlen, ep.cu_seqlens, ep.max_seqlen), drop=drop)
-        return self._loss(dec, lab.unsqueeze(0))
+        return dec, lab.unsqueeze(0)
 
     def init_decode_state(self, input_ids, max_length=32, attention_mask=None, prompt_length=1, kv_cache_dtype=None, weight_dtype=None):
         """encoder output, cross K / V and empty self-attention caches of capacity max_length + prompt_length (generation.DecodeState);

@@ -1209,6 +1209,63 @@ int fat5_ce_fwd_bwd(const void* logits, const int64_t* labels, const float* dlos
                     int dtype, void* hip_stream);
 
 /*
+ * Knowledge distillation: forward KL(teacher || student) at a temperature mixed with the student's cross-entropy, per row
+ * (csrc/kd_kernels.h).  s = a row of `logits`, t = the same row of `teacher_logits` (same dtype and width), y its label:
+ *   p = softmax(t / T),  q = softmax(s / T),  kd = sum_j p_j (log p_j - log q_j)                       (>= 0)
+ *   ce = the row loss of fat5_ce_fwd(s, y, label_smoothing, logit_scale, lse_square_scale), z-loss inside
+ *   losses = (1 - alpha) ce + alpha T^2 kd;   d losses / d s_j = (1 - alpha) d ce / d s_j + alpha T (q_j - p_j);   no teacher gradient
+ * label_smoothing, logit_scale and lse_square_scale act on ce only.  A row with y == ignore_index has losses = kd_losses = z_losses
+ * = ce_losses = 0 and a zero gradient row; a label outside [0, n_cols) that is not ignore_index keeps fat5_ce_fwd's meaning and its
+ * kd still counts.  A column with t_j = -inf adds exactly 0 to kd and alpha T (q_j - 0) to the gradient, also where s_j = -inf too; a
+ * row whose t is -inf everywhere is outside the contract (its kd is NaN; nothing is checked on the device).  With alpha == 0
+ * losses, z_losses, lse and dlogits have the bits of fat5_ce_fwd / fat5_ce_bwd.
+ * fat5_kd_fwd:     one pass over both rows.  Writes, fp32 per row: losses, kd_losses (the bare kd), z_losses, ce_losses (the bare ce; may
+ *                  be NULL), lse = log sum exp(logit_scale s), lse_student_t = log sum exp(s / T), lse_teacher_t = log sum exp(t / T).
+ * fat5_kd_bwd:     element-wise from lse / lse_student_t / lse_teacher_t and dlosses (fp32, dloss_stride elements apart: 0 for one
+ *                  shared value); writes dlogits, which may be `logits` (in place).
+ * fat5_kd_fwd_bwd: both in one launch per row, for callers that know dlosses beforehand; every output has the bits of the two
+ *                  launches.  dlogits may be `logits`; the teacher row is only read.  Falls back to the two launches where the
+ *                  16-byte layout does not hold (n_cols or a row stride no multiple of 16 bytes, a base not 16-byte aligned).
+ * No atomics: the same bits on every run.  Rejected with FAT5_EINVAL before anything is launched: NULL params, a NULL or misaligned
+ * pointer that the direction needs, a bad dtype, rows or n_cols outside [1, 2^31 - 1], temperature not finite or <= 0, alpha
+ * outside [0, 1].
+ */
+typedef struct fat5_kd_params {
+  int32_t dtype;                /* FAT5_F32 | FAT5_F16 | FAT5_BF16: logits, teacher_logits, dlogits */
+  int32_t reserved;
+  int64_t rows;
+  int64_t n_cols;
+  const void* logits;           /* student, (rows, n_cols), rows row_stride elements apart */
+  int64_t row_stride;
+  const void* teacher_logits;   /* (rows, n_cols), rows teacher_row_stride elements apart */
+  int64_t teacher_row_stride;
+  const int64_t* labels;        /* (rows,) */
+  const float* dlosses;         /* backward */
+  int64_t dloss_stride;
+  float* losses;
+  float* kd_losses;
+  float* z_losses;
+  float* ce_losses;             /* or NULL */
+  float* lse;                   /* written by the forward, read by the backward -- like the next two */
+  float* lse_student_t;
+  float* lse_teacher_t;
+  void* dlogits;                /* backward; may be `logits` */
+  int64_t dlogits_row_stride;
+  int64_t ignore_index;
+  float alpha;
+  float temperature;
+  float label_smoothing;
+  float logit_scale;
+  float lse_square_scale;
+  int32_t reserved2;
+} fat5_kd_params;
+/* sizeof(fat5_kd_params) as compiled into the library (bindings check their mirror against it). */
+size_t fat5_sizeof_kd_params(void);
+int fat5_kd_fwd(const fat5_kd_params* p, void* hip_stream);
+int fat5_kd_bwd(const fat5_kd_params* p, void* hip_stream);
+int fat5_kd_fwd_bwd(const fat5_kd_params* p, void* hip_stream);
+
+/*
  * AdamWScale step over a group of tensors.  Replaces the reference optimizer's per-tensor / foreach op
  * sequences (src/utils/adamw_scaled.py:154-211, :213-281) with two launches for the whole group.
  *   m = beta1 m + (1-beta1) g;  v = beta2 v + (1-beta2) g^2;  denom = sqrt(v) + eps
