@@ -286,7 +286,7 @@ class DropoutDesc(ctypes.Structure):
 
 
 EXPORTS = (
-    "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches",
+    "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches", "fat5_attn_bwd_kvres",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
     "fat5_rmsnorm_fwd", "fat5_rmsnorm_bwd_workspace_bytes", "fat5_rmsnorm_bwd", "fat5_add_rmsnorm_fwd", "fat5_add_rmsnorm_bwd",
     "fat5_ce_fwd", "fat5_ce_bwd", "fat5_ce_fwd_bwd", "fat5_fold_weights", "fat5_fold_weights_bwd", "fat5_fold_weights_bwd_scratch_bytes", "fat5_rmsnorm_unit_bwd", "fat5_gated_act_fwd", "fat5_gated_act_bwd",
@@ -334,6 +334,8 @@ def load():
     lib.fat5_attn_bwd_stages.argtypes = [ctypes.POINTER(AttnParams), ctypes.c_int, ctypes.c_void_p]
     lib.fat5_attn_bwd_launches.restype = ctypes.c_int
     lib.fat5_attn_bwd_launches.argtypes = [ctypes.POINTER(AttnParams)]
+    lib.fat5_attn_bwd_kvres.restype = ctypes.c_int
+    lib.fat5_attn_bwd_kvres.argtypes = [ctypes.POINTER(AttnParams)]
     lib.fat5_attn_describe.restype = ctypes.c_int
     lib.fat5_attn_describe.argtypes = [ctypes.POINTER(AttnParams), ctypes.c_char_p, ctypes.c_size_t]
     lib.fat5_attn_bwd_workspace_bytes.restype = ctypes.c_size_t
@@ -529,6 +531,7 @@ V_FWD64_MIX_ON, V_FWD64_MIX_OFF = 524288, 1048576
 V_FUSED64_ON, V_FUSED64_OFF = 65536, 131072
 V_DBIAS_NOSPLIT = 262144
 V_QDB64_ON, V_QDB64_OFF = 2097152, 4194304
+V_KVRES_ON, V_KVRES_OFF = 134217728, 268435456  # 64-row dQ body, at most 512 keys: the head's K / V resident in LDS (no ring) wherever legal / never
 V_QDIAG_ON, V_QDIAG_OFF = 8388608, 16777216  # T5 bias, one-launch backward: the per-diagonal sums of the table gradient in the dQ workgroups always / never
 V_DTABLE_RUNS_ON, V_DTABLE_RUNS_OFF = 33554432, 67108864  # T5 table gradient: the per-bucket-run reduction wherever legal (the default) / never
 _variant = 0  # what the host mirror writes into every descriptor it builds; 0 = the library's own choice (production)
@@ -662,4 +665,6 @@ def describe(B, H, M, N, D=64, dtype=FAT5_BF16, causal=False, bias_mode=0, radiu
             p.drpe1d = 16
     buf = ctypes.create_string_buffer(256)
     check(load().fat5_attn_describe(ctypes.byref(p), buf, 256), "fat5_attn_describe")
-    return dict(kv.split("=") for kv in buf.value.decode().split())
+    d = dict(kv.split("=") for kv in buf.value.decode().split())
+    d["kvres"] = str(load().fat5_attn_bwd_kvres(ctypes.byref(p)))  # (fat5_attn_bwd_kvres: not a field of the text)
+    return d

@@ -143,6 +143,15 @@ int fat5_attn_bwd_launches(const fat5_attn_params* p) {
   return L.form == kSeparate ? 2 : 1;  // (kDenseFused64: one launch of both bodies behind the small statistics kernel)
 }
 
+// 1: the 64-row dQ body of this problem keeps the head's whole K / V resident in LDS (BwdLayout::kvres); 0: its ring form, another dQ body, or invalid params.
+// Host-only like fat5_attn_describe; a call of its own so that the describe text keeps its fields (the Python describe() dicts carry it as "kvres").
+int fat5_attn_bwd_kvres(const fat5_attn_params* p) {
+  if (check_common(p)) return 0;
+  BwdLayout L;
+  bwd_layout(key_of(p), L);
+  return L.kvres ? 1 : 0;
+}
+
 // Which kernel bodies a problem runs, as text (tests pin the dispatch rules with it; no device needed, no pointer of `p` is followed)
 int fat5_attn_describe(const fat5_attn_params* p, char* out, size_t n) {
   int rc = check_common(p);
@@ -263,6 +272,7 @@ int fat5_attn_bwd_stages(const fat5_attn_params* p, int stages, void* stream_) {
   a.n_nblk = L.n_nblk;
   a.n_kv_blocks = 0;
   a.diag_q = L.diag_q ? 1 : 0;
+  a.kvres = L.kvres ? 1 : 0;
   a.part_stride = L.part_rows;
   const long grid_q = n_units(p) * a.n_mblk, grid_kv = n_units(p) * a.n_nblk;
   // The launch form comes from the FULL problem (L.form: see fat5_attn_fwd), the grids from the call's units; a call for one stage only

@@ -1109,9 +1109,10 @@ FAT5_DEV void attn_bwd_kv64_body(const AttnArgs& a, const int b, const int h, co
 // accumulators in AGPRs), one wave per SIMD; per 32-key step i the matrix pipe runs dQ^T += K^T dS^T of step i-1 and
 // S^T = K Q^T, dP'^T = V dO^T - delta of step i+1 (24 MFMAs, every K / V fragment read from LDS feeds two of them) while the
 // VALU pipe turns step i's scores into dS (FMA, v_exp_f32, multiply per element; bf16 pack per pair).  K / V steps come
-// global -> LDS by DMA three steps ahead into a 4-slot ring, one barrier per step.  Every wave picks the pipelined or the
-// general iteration by ITS 64 rows (wave-uniform): only the steps that cross the wave's own RPE band / causal diagonal / the key
-// tail run the general softmax.
+// global -> LDS by DMA three steps ahead into a 4-slot ring, one barrier per step -- or, up to RES_STEPS steps (512 keys) with staged
+// operands, all of them once into RES_STEPS slots that are never recycled (KVRES below: the ring plus the bytes of the staging images;
+// two barriers in all, the waves run decoupled).  Every wave picks the pipelined or the general iteration by ITS 64 rows
+// (wave-uniform): only the steps that cross the wave's own RPE band / causal diagonal / the key tail run the general softmax.
 template <int D>
 struct BwdQ64Cfg {
   static constexpr int NW = 4, BM = 64 * NW, KT = 32, NT = 64 * NW, NS = 4;
@@ -1123,6 +1124,7 @@ struct BwdQ64Cfg {
   // lines per instruction: 13.5 k cycles of prologue measured (tools/trace64.py), a third of the kernel at 512 keys.
   static constexpr int STG_T = 64 * 2 * D;      // one tensor's 64 rows of one wave
   static constexpr int STG = NW * 3 * STG_T;
+  static constexpr int RES_STEPS = 16;          // KVRES (below): key steps that fit RING + STG, i.e. up to 512 keys
   // qdg: the body also forms the table gradient's per-diagonal sums (QDG below): one private array of 2R+1 sums per (wave, half-wave) + one scratch word per thread
   static size_t smem(int R, int bias_mode, bool stage = false, bool qdg = false) {
     return RING + (stage ? STG : 0) + (bias_mode == FAT5_BIAS_RPE1D ? rpe_table_bytes(R) + 16 : 0) +
@@ -1138,7 +1140,18 @@ struct BwdQ64Cfg {
 // base' = (first row of the query block) - (first key of the step) an element lies on d' = base' + 16 a + p - 16 qh - ql0 - 4 hi -- the formula of diag_sum.h with the
 // roles of rows and keys exchanged.  A step moves 32 keys up: base' - 32, the same hand-over between consecutive steps; query block 1 of a step has the homes
 // query block 0 had one step earlier.  Sums leave at index R - d' of the wave's private arrays (d' >= R: the far-negative bin, d' <= -R: the far-positive one).
-template <int D, bool BF16, int BIAS, bool QDG = false>
+//
+// KVRES (resident K / V; staged operands, at most Cfg::RES_STEPS key steps -- the launcher checks both): key step t lives at t * SLOT from the start of the
+// shared memory and stays there.  Slots 0..3 are the ring, slots 4..15 the bytes of the staging images, dead once the Q / dO / O fragments are in registers:
+// no extra LDS.  Steps 0..3 arrive with the prologue's wait; behind one more barrier (no wave still reads its images) every thread requests ALL remaining
+// steps at once.  They become visible at ONE point -- vmcnt(0) + barrier in step 3's iteration, before its first fragment read of step 4 -- and from there on
+// an iteration has no barrier, no counted wait and no DMA: no slot is ever recycled, so the four waves run decoupled and each pays for its own band steps
+// only (in the ring form a step costs what the slowest of the four waves costs: the union of their T5 bands is 12 of 16 steps at 512 keys, one wave's 10-11).
+// The trips keep their slot immediates: the row-major address registers move up by 4 * SLOT at the end of a trip's last step, the transposed ones behind the
+// last read of the previous trip's slot 3 in its first step (LDS offset immediates do not reach 128 KiB).  dQ leaves through the staging image as before --
+// live K / V slots now -- behind one barrier (every wave done with its last step).  Same arithmetic on the same values in the same order: bit-identical to
+// the ring form.
+template <int D, bool BF16, int BIAS, bool QDG = false, bool KVRES = false>
 FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
   static_assert(D == 64 && BIAS != FAT5_BIAS_DENSE, "gap schedule written for D = 64, bias none / rpe1d");
   static_assert(!QDG || BIAS == FAT5_BIAS_RPE1D, "the diagonal sums belong to the T5 bias");
@@ -1146,8 +1159,9 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
   using Cfg = BwdQ64Cfg<D>;
   constexpr int BM = Cfg::BM, NT = Cfg::NT, IMG = Cfg::IMG, SLOT = Cfg::SLOT;
   constexpr int KK = D / 16, DB = D / 32;
+  static_assert(!KVRES || Cfg::RES_STEPS * SLOT == Cfg::RING + Cfg::STG, "the resident slots are the ring and the staging images, nothing more");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const bool stg = a.lds_stage != 0;
+  const bool stg = KVRES || a.lds_stage != 0;
   float* sT = reinterpret_cast<float*>(smem + Cfg::RING + (stg ? Cfg::STG : 0)) + kRpePad;  // (entry d of copy 0 at sT[d + R]; see attn_common.h)
 
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63, lq = l & 31, hi = l >> 5;  // (w: provably wave-uniform)
@@ -1362,9 +1376,10 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
     if (t + 3 < nt) dma_step(t + 3, slot3_off);
   };
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < (KVRES ? 4 : 3); ++i)  // (KVRES: step 3 comes with the first three -- step 2's iteration reads it ahead of the second visibility point)
     if (i < nt) dma_step(i, (uint32_t)(i * SLOT));
-  for (int i = tid; i < SLOT / 16; i += NT) reinterpret_cast<u32x4*>(smem + 3 * SLOT)[i] = u32x4{0u, 0u, 0u, 0u};  // (see the dK/dV body)
+  if (!KVRES || nt < 4)
+    for (int i = tid; i < SLOT / 16; i += NT) reinterpret_cast<u32x4*>(smem + 3 * SLOT)[i] = u32x4{0u, 0u, 0u, 0u};  // (see the dK/dV body)
   // (round 6, measured and dropped -- profiles/r06_prologue_ab.log: the ring requests right behind the staging requests, the fragment reads + delta behind a counted
   //  wait for the private staging images only, the lse loads youngest: cfg2 backward 27.9 vs 27.0 us on the same box, (2,12,1024) 38.5 vs 37.6 -- the order below stays)
   FAT5_STAMP(7);
@@ -1386,6 +1401,17 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
         off_[qb][kk] = lds_rd128(ad + (uint32_t)(2 * Cfg::STG_T));
       }
     derive_rows();
+    if constexpr (KVRES) {
+      // the staging images become key steps 4 .. nt-1: every wave has its fragments in registers (LDS only: no wait for the statistics stores), then all
+      // requests at once -- 24 per thread at most, inside vmcnt's range; rows past N arrive as zeros through the descriptor like those of the first steps
+      if (nt > 4) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int i = 4; i < Cfg::RES_STEPS; ++i)
+          if (i < nt) dma_step(i, (uint32_t)(i * SLOT));
+      }
+    }
   }
   FAT5_STAMP(1);
 #pragma unroll
@@ -1401,6 +1427,29 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
   for (int j2 = 0; j2 < 2; ++j2)
 #pragma unroll
     for (int db = 0; db < DB; ++db) trA[j2][db] = lds0 + (uint32_t)fa.tr[j2][db];
+  // KVRES: the key step whose slot rmA / trA point at (wave-uniform).  A trip at t starts from rm_base = t and tr_base = t - 4 (0 at t = 0, where the "previous
+  // step" is the empty one: its slot-3 read meets zero operands) and leaves rm_base = t + 4, tr_base = t; the general iteration reads relative to both.
+  [[maybe_unused]] int rm_base = 0, tr_base = 0;
+  [[maybe_unused]] auto res_rebase = [&](const int t) {
+    const int tr_to = t >= 4 ? t - 4 : 0;
+    const uint32_t drm = (uint32_t)((t - rm_base) * SLOT), dtr = (uint32_t)((tr_to - tr_base) * SLOT);
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) rmA[kk] += drm;
+#pragma unroll
+    for (int j2 = 0; j2 < 2; ++j2)
+#pragma unroll
+      for (int db = 0; db < DB; ++db) trA[j2][db] += dtr;
+    rm_base = t;
+    tr_base = tr_to;
+  };
+  // KVRES, the second (and last) visibility point, in step 3's iteration ahead of its first read of step 4: steps 4 .. nt-1 have landed for every wave
+  [[maybe_unused]] auto res_visible = [&](const int t) {
+    if (t == 3 && nt > 4) {
+      wait_dma_all();
+      __syncthreads();
+      FAT5_STAMP(14);
+    }
+  };
 
   const float c2 = a.scale * kLog2e;
   float cst_neg = 0.f, cst_pos = 0.f;
@@ -1514,9 +1563,13 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
     if constexpr (QDG) diag_step_end(gst, nb);
   };
   auto generic_iter = [&](const int t) {
-    const uint32_t o_prev = (uint32_t)(((t + 3) & 3) * SLOT), o_cur = (uint32_t)((t & 3) * SLOT), o_next = (uint32_t)(((t + 1) & 3) * SLOT);
+    // (KVRES: step t at (t - base) * SLOT from the address registers; the empty step before step 0 reads slot 3 as in the ring form)
+    const uint32_t o_prev = KVRES ? (uint32_t)(((t ? t - 1 : 3) - tr_base) * SLOT) : (uint32_t)(((t + 3) & 3) * SLOT);
+    const uint32_t o_cur = KVRES ? (uint32_t)((t - tr_base) * SLOT) : (uint32_t)((t & 3) * SLOT);
+    const uint32_t o_next = KVRES ? (uint32_t)((t + 1 - rm_base) * SLOT) : (uint32_t)(((t + 1) & 3) * SLOT);
     product_step(o_prev);
-    sync_step(t, o_prev);
+    if constexpr (KVRES) res_visible(t);
+    else sync_step(t, o_prev);
     f32x16 Sn[2], DPn[2];
     score_step(o_next, Sn, DPn);
     softmax_generic(t * 32);
@@ -1544,7 +1597,8 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
   // A band step was the general, unpipelined iteration before (the 64-row body lost to the 32-row one below 8192 keys for it).
   constexpr int NG = 24, G_DP = 16;  // (G_DP: first gap of the dP k-steps)
   auto fast_iter = [&]<int SL, bool BAND>(const int t, const float ad0, const float ad1) {
-    constexpr uint32_t o_prev = (uint32_t)(((SL + 3) & 3) * SLOT), o_cur = (uint32_t)(SL * SLOT), o_next = (uint32_t)(((SL + 1) & 3) * SLOT);
+    // (KVRES: the same immediates against address registers that follow the trips -- only the step behind the trip's last one sits at 4 * SLOT instead of 0)
+    constexpr uint32_t o_prev = (uint32_t)(((SL + 3) & 3) * SLOT), o_cur = (uint32_t)(SL * SLOT), o_next = (uint32_t)((KVRES ? SL + 1 : ((SL + 1) & 3)) * SLOT);
     f32x16 Sn[2], DPn[2];
     u32x4 DSn[2][2], kf[KK], vf[KK];
     u32x2 th[2][2], tn[2][2];  // [db][half]: K^T fragments t2 = 1 of step i-1 / t2 = 0 of step i
@@ -1601,11 +1655,21 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
       }
       __builtin_amdgcn_sched_barrier(0);  // (the MFMA opens its gap: without this it may sink below the gap's VALU work and pair up with the next one)
       // ---- barrier + DMA (the K and the V piece of step i+3 in gaps of their own: see the dK/dV body) ----
-      if constexpr (g == 4) {
+      if constexpr (KVRES) {
+        if constexpr (g == 4 && SL == 3) res_visible(t);
+        if constexpr (g == 4 && SL == 0) {  // slot 3 of the previous trip has been read (gaps 0..3): the transposed addresses move on to this trip
+          const uint32_t dtr = (uint32_t)((t - tr_base) * SLOT);
+#pragma unroll
+          for (int j2 = 0; j2 < 2; ++j2)
+#pragma unroll
+            for (int db = 0; db < DB; ++db) trA[j2][db] += dtr;
+          tr_base = t;
+        }
+      } else if constexpr (g == 4) {
         if constexpr (FAT5_DMA_SPREAD) sync_wait(t);
         else sync_step(t, o_prev);
       }
-      if constexpr (FAT5_DMA_SPREAD && (g == 5 || g == 6)) {
+      if constexpr (!KVRES && FAT5_DMA_SPREAD && (g == 5 || g == 6)) {
         if (t + 3 < nt) {
           const uint32_t tt = (uint32_t)__builtin_amdgcn_readfirstlane(t + 3);
           const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave_lds + o_prev));
@@ -1682,6 +1746,11 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
     }
 #pragma unroll
     for (int db = 0; db < DB; ++db) TRK[db] = u32x4{tn[db][0][0], tn[db][0][1], tn[db][1][0], tn[db][1][1]};
+    if constexpr (KVRES && SL == 3) {  // the trip's last row-major read is out: on to the next trip's slots
+#pragma unroll
+      for (int kk = 0; kk < KK; ++kk) rmA[kk] += (uint32_t)(4 * SLOT);
+      rm_base += 4;
+    }
     if constexpr (BAND && QDG) {
       asm volatile("s_nop 1" : "+v"(dst[1].u1), "+v"(dst[1].b1));  // (asm producers: no hazard padding is generated for them)
       diag_step_end(dst, t * 32);
@@ -1716,6 +1785,7 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
     int t = 0;
     while (t < nt) {
       int side, side3;
+      if constexpr (KVRES) res_rebase(t);  // (a no-op between consecutive trips; once per general iteration)
       // steady state: four steps (ring slots 0..3) per trip; the fast steps of one side are contiguous, so the first and the last
       // step of a trip decide for all four.  Steps that do not fill an aligned trip run the general iteration.
       while (t + 4 <= nt && (t & 3) == 0 && classify(t, side) && classify(t + 3, side3) && side3 == side) {
@@ -1752,10 +1822,20 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
       }
     }
     FAT5_STAMP(3);
-    product_step((uint32_t)(((nt - 1) & 3) * SLOT));
+    product_step(KVRES ? (uint32_t)((nt - 1 - tr_base) * SLOT) : (uint32_t)(((nt - 1) & 3) * SLOT));
+    // asm MFMA -> accumulator reads below: see mfma_acc_agpr.  The padding sits HERE, behind the last MFMA and in its block, with the tuples tied to it: to the
+    // compiler a read of theirs is an ordinary register read -- it may place one between the last MFMA and a padding that does not name them, and it did: where
+    // this block meets the "no key step" path it copied one element of dq[1][1] out of its AGPR one wait state behind the MFMA (resident K / V form, T5 bias)
+    asm volatile("s_nop 15\n\ts_nop 15" : "+a"(dq[0][0]), "+a"(dq[0][1]), "+a"(dq[1][0]), "+a"(dq[1][1]) : : "memory");
   }
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // (asm MFMA -> accumulator reads below: see mfma_acc_agpr)
   FAT5_STAMP(4);
+  if constexpr (KVRES) {
+    // the dQ image below overwrites live key steps (the wave's Q image is slot 4 + 3 w): every wave is done with its last step first
+    if (nt > 4) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
+  }
 
   const float scale = a.scale;
   if (stg) {
@@ -1826,10 +1906,10 @@ FAT5_DEV void attn_bwd_q64_body(const AttnArgs& a, const int bid) {
   FAT5_STAMP(6);
 }
 
-template <int D, bool BF16, int BIAS, bool QDG = false>
+template <int D, bool BF16, int BIAS, bool QDG = false, bool KVRES = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void attn_bwd_q64_kernel(const AttnArgs a) {
-  attn_bwd_q64_body<D, BF16, BIAS, QDG>(a, blockIdx.x);
+  attn_bwd_q64_body<D, BF16, BIAS, QDG, KVRES>(a, blockIdx.x);
 }
 
 // Both backward kernels in ONE launch for problems whose grids leave the chip's last round mostly empty (mid sequence lengths) or
@@ -1837,7 +1917,8 @@ void attn_bwd_q64_kernel(const AttnArgs a) {
 // the others the dQ body; one workgroup per CU either way (512 registers per lane), the longer ones first.
 // QDG (round 6, T5 bias): the dQ workgroups form the table gradient's per-diagonal sums, the dK/dV ones none (see attn_bwd_q64_body): taken where every workgroup of
 // the launch is resident at once, i.e. where the launch lasts as long as its longest workgroup -- a dK/dV one
-template <int D, bool BF16, int BIAS, bool QDG = false>
+// KVRES (short key streams): the dQ half keeps the head's whole K / V resident in LDS (see attn_bwd_q64_body); the dK/dV half is the same either way.
+template <int D, bool BF16, int BIAS, bool QDG = false, bool KVRES = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void attn_bwd_fused64_kernel(const AttnArgs a) {
   if ((int)blockIdx.x < a.n_kv_blocks) {
@@ -1845,7 +1926,7 @@ void attn_bwd_fused64_kernel(const AttnArgs a) {
     decode_unit(a, blockIdx.x, a.n_nblk, b, h, nblk, (FAT5_CAUSAL_ORDER && a.causal) ? 2 : 0);
     attn_bwd_kv64_body<D, BF16, BIAS, false, true, false, QDG>(a, b, h, nblk, nblk, false);
   } else {
-    attn_bwd_q64_body<D, BF16, BIAS, QDG>(a, blockIdx.x - a.n_kv_blocks);
+    attn_bwd_q64_body<D, BF16, BIAS, QDG, KVRES>(a, blockIdx.x - a.n_kv_blocks);
   }
 }
 

@@ -31,6 +31,25 @@ static hipError_t launch_kv64(const AttnArgs& a, int grid, hipStream_t s) {
   return hipGetLastError();
 }
 
+// Resident K / V form of the dQ body (attn_bwd_q64_body<..., KVRES>): LDS the launch asks for.  The body's last step prefetches the fragments of "the step behind it"
+// like every other (results dropped): with all sixteen slots in use those reads fall one slot behind the images, so the request covers one slot more than the
+// images wherever the table and the diagonal arrays behind them do not (bias none, small radii).
+template <int D>
+static size_t kvres_smem(size_t smem) { return std::max(smem, (size_t)(BwdQ64Cfg<D>::RES_STEPS + 1) * BwdQ64Cfg<D>::SLOT); }
+// ... and whether a launch can take it: operands staged, every key step of a workgroup resident
+template <int D>
+static bool kvres_ok(const AttnArgs& a, bool staged) { return a.kvres && staged && (a.N + 31) / 32 <= BwdQ64Cfg<D>::RES_STEPS; }
+
+template <int D, bool BF16, int BIAS, bool QDG, bool KVRES>
+static hipError_t launch_q64_form(const AttnArgs& as, size_t smem, int grid, hipStream_t s) {
+  auto kern = attn_bwd_q64_kernel<D, BF16, BIAS, QDG, KVRES>;
+  if (smem > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, as);
+  return hipGetLastError();
+}
 template <int D, bool BF16, int BIAS, bool QDG = false>
 static hipError_t launch_q64(const AttnArgs& a, int grid, hipStream_t s) {
   // (operands / outputs through wave-private LDS images whenever the workgroup's LDS allows: a radius beyond ~500 does not)
@@ -38,13 +57,8 @@ static hipError_t launch_q64(const AttnArgs& a, int grid, hipStream_t s) {
   fill_div_magic(as, grid);
   as.lds_stage = BwdQ64Cfg<D>::smem(a.R, BIAS, true, QDG) <= 160 * 1024;
   const size_t smem = BwdQ64Cfg<D>::smem(a.R, BIAS, as.lds_stage != 0, QDG);
-  auto kern = attn_bwd_q64_kernel<D, BF16, BIAS, QDG>;
-  if (smem > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, as);
-  return hipGetLastError();
+  if (kvres_ok<D>(a, as.lds_stage != 0)) return launch_q64_form<D, BF16, BIAS, QDG, true>(as, kvres_smem<D>(smem), grid, s);
+  return launch_q64_form<D, BF16, BIAS, QDG, false>(as, smem, grid, s);
 }
 hipError_t CAT(launch_bwd_q64_d, FAT5_INST_D)(const AttnArgs& a, int bf16, int bias, int /*nw*/, int grid, hipStream_t s) {
   if (bias == FAT5_BIAS_RPE1D) {
@@ -99,6 +113,16 @@ hipError_t CAT(launch_bwd_kv64_d, FAT5_INST_D)(const AttnArgs& a, int bf16, int 
   return nw == kKv64Half ? launch_kv64_bias<true>(a, bf16, bias, grid, s) : launch_kv64_bias<false>(a, bf16, bias, grid, s);
 }
 // dK/dV (self-sufficient 256-key form) and dQ in one launch: a.n_kv_blocks workgroups of the former, then the dQ workgroups
+template <int D, bool BF16, int BIAS, bool QDG, bool KVRES>
+static hipError_t launch_fused64_form(const AttnArgs& as, size_t smem, int grid, hipStream_t s) {
+  auto kern = attn_bwd_fused64_kernel<D, BF16, BIAS, QDG, KVRES>;
+  if (smem > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, as);
+  return hipGetLastError();
+}
 template <int D, bool BF16, int BIAS, bool QDG = false>
 static hipError_t launch_fused64(const AttnArgs& a, int grid, hipStream_t s) {
   AttnArgs as = a;
@@ -106,13 +130,8 @@ static hipError_t launch_fused64(const AttnArgs& a, int grid, hipStream_t s) {
   as.lds_stage = std::max(Bwd64Cfg<D, false, true>::smem(a.R, BIAS, true), BwdQ64Cfg<D>::smem(a.R, BIAS, true, QDG)) <= 160 * 1024;
   const bool st = as.lds_stage != 0;
   const size_t smem = std::max(Bwd64Cfg<D, false, true>::smem(a.R, BIAS, st), BwdQ64Cfg<D>::smem(a.R, BIAS, st, QDG));
-  auto kern = attn_bwd_fused64_kernel<D, BF16, BIAS, QDG>;
-  if (smem > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, as);
-  return hipGetLastError();
+  if (kvres_ok<D>(a, st)) return launch_fused64_form<D, BF16, BIAS, QDG, true>(as, kvres_smem<D>(smem), grid, s);
+  return launch_fused64_form<D, BF16, BIAS, QDG, false>(as, smem, grid, s);
 }
 hipError_t CAT(launch_bwd_fused64_d, FAT5_INST_D)(const AttnArgs& a, int bf16, int bias, int /*nw*/, int grid, hipStream_t s) {
   if (bias == FAT5_BIAS_RPE1D) {
@@ -125,6 +144,12 @@ hipError_t CAT(launch_bwd_fused64_d, FAT5_INST_D)(const AttnArgs& a, int bf16, i
 size_t CAT(smem_bwd_fused64_d, FAT5_INST_D)(int R, int bias) {
   return std::max(Bwd64Cfg<FAT5_INST_D, false, true>::smem(R, bias), BwdQ64Cfg<FAT5_INST_D>::smem(R, bias, false, true));
 }
+// do the launchers above stage the operands of the dQ body (the resident K / V form needs it)?  one_launch: inside attn_bwd_fused64_kernel
+bool CAT(stage_bwd_q64_d, FAT5_INST_D)(int R, int bias, bool qdg, bool one_launch) {
+  const size_t q = BwdQ64Cfg<FAT5_INST_D>::smem(R, bias, true, qdg);
+  return (one_launch ? std::max(Bwd64Cfg<FAT5_INST_D, false, true>::smem(R, bias, true), q) : q) <= 160 * 1024;
+}
+int CAT(res_steps_bwd_q64_d, FAT5_INST_D)() { return BwdQ64Cfg<FAT5_INST_D>::RES_STEPS; }
 size_t CAT(smem_bwd_kv64_d, FAT5_INST_D)(int R, int bias) {
   return bias == FAT5_BIAS_DENSE ? Bwd64Cfg<FAT5_INST_D, false, false, true>::smem(R, bias) : Bwd64Cfg<FAT5_INST_D>::smem(R, bias);
 }

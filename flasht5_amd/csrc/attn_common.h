@@ -413,6 +413,7 @@ struct AttnArgs {
   int32_t dvalid;           // valid head-dim columns: = D except head_dim 16, which runs the D = 32 instantiations with columns 16..31 read as zeros and never written
   int32_t ref_first;        // forward sweep, bf16 without the T5 table: reference point of every row = its maximum over the first tile instead of 0 (large logits: see attn_fwd64.h)
   int32_t lds_stage;        // 64-wide backward bodies: the register-resident operands arrive / the outputs leave through wave-private LDS images (set by the launcher when the LDS fits)
+  int32_t kvres;            // 64-row dQ body: the layout asks for the resident K / V form (BwdLayout::kvres); read by the launchers, which pick the instantiation
   float scale;
 };
 

@@ -48,7 +48,7 @@ inline int vsel(int variant, int on_bit, int off_bit) { return (variant & on_bit
 // ... all of them, decoded once per policy call
 struct Overrides {
   int fwd64, fwd64_ksplit, fwd64_mix;                  // forward
-  int kv64, kv64_half, kv64_mix, q64, fused64, qdb64, qdiag;  // backward
+  int kv64, kv64_half, kv64_mix, q64, fused64, qdb64, qdiag, kvres;  // backward
   bool dbias_staged, dbias_inkernel;                   // a call that asks for one of the older dense dbias paths keeps it
   bool no_split, no_fuse;
   explicit Overrides(int v)
@@ -56,7 +56,7 @@ struct Overrides {
         fwd64_mix(vsel(v, FAT5_V_FWD64_MIX_ON, FAT5_V_FWD64_MIX_OFF)), kv64(vsel(v, FAT5_V_KV64_ON, FAT5_V_KV64_OFF)),
         kv64_half(vsel(v, FAT5_V_KV64_HALF_ON, FAT5_V_KV64_HALF_OFF)), kv64_mix(vsel(v, FAT5_V_KV64_MIX_ON, FAT5_V_KV64_MIX_OFF)),
         q64(vsel(v, FAT5_V_Q64_ON, FAT5_V_Q64_OFF)), fused64(vsel(v, FAT5_V_FUSED64_ON, FAT5_V_FUSED64_OFF)),
-        qdb64(vsel(v, FAT5_V_QDB64_ON, FAT5_V_QDB64_OFF)), qdiag(vsel(v, FAT5_V_QDIAG_ON, FAT5_V_QDIAG_OFF)),
+        qdb64(vsel(v, FAT5_V_QDB64_ON, FAT5_V_QDB64_OFF)), qdiag(vsel(v, FAT5_V_QDIAG_ON, FAT5_V_QDIAG_OFF)), kvres(vsel(v, FAT5_V_KVRES_ON, FAT5_V_KVRES_OFF)),
         dbias_staged(v & FAT5_V_DBIAS_STAGED), dbias_inkernel(v & FAT5_V_DBIAS_INKERNEL), no_split(v & FAT5_V_NO_SPLIT),
         no_fuse(v & FAT5_V_NO_FUSE) {}
 };
@@ -119,6 +119,7 @@ struct BwdLayout {
   int nw_q, nw_kv;  // launcher codes (attn_launch.h): waves per workgroup of the 32-wide bodies; nw_kv of the 64-key body: a Kv64Launch
   bool diag_q;     // T5 bias, one-launch 64-wide backward: the dQ workgroups form the partial diagonal sums (one partial row per 256-row block), the dK/dV ones none
   int part_rows;   // partial diagonal-sum rows per (b, h) in the workspace
+  bool kvres;      // 64-row dQ body: the head's whole K / V resident in LDS, no ring (attn_bwd_q64_body<..., KVRES>); the same in the one-launch and the stage-by-stage form
   // the launch plan of the FULL problem (a unit-range call keeps the form and takes its grids from its own units)
   long grid_q, grid_kv;
   BwdForm form;
@@ -568,6 +569,12 @@ inline int bwd_layout_compute(const DispatchKey& k, BwdLayout& L) {
   L.grid_q = bh * L.n_mblk;
   L.grid_kv = bh * L.n_nblk;
   L.form = bwd_fusable(L, ov, k) ? kFused32 : (L.fused64 ? kFused64 : (L.dfused64 ? kDenseFused64 : kSeparate));
+  // The 64-row dQ body keeps a short head's K and V resident in LDS instead of cycling them through its four-slot ring: at most 16 key steps (512 keys) fit the
+  // ring plus the staging images, so the operands have to be staged (not at radius 512, where the table and the diagonal arrays crowd the LDS).  Legal means taken:
+  // the ring's per-step barrier makes every step cost what the slowest of the four waves pays, the resident form has two barriers in all.  Bit-identical results
+  // either way; FAT5_V_KVRES_ON / _OFF force / forbid it wherever it is legal.
+  L.kvres = L.q64 && k.D == 64 && k.bias_mode != FAT5_BIAS_DENSE && ov.kvres != 0 && (k.N + 31) / 32 <= res_steps_bwd_q64_d64() &&
+            stage_bwd_q64_d64(k.rpe_radius, k.bias_mode, L.diag_q, L.form == kFused64);
   return FAT5_OK;
 }
 

@@ -726,7 +726,9 @@ class AttentionPlan:
         """the kernel bodies this plan's calls run, e.g. {"fwd": "64row-ksplit", "dq": "64row", "dkdv": "64key", "fused": "1", ...} (fat5_attn_describe)"""
         buf = ctypes.create_string_buffer(256)
         _lib.check(self.lib.fat5_attn_describe(ctypes.byref(self.p), buf, 256), "fat5_attn_describe")
-        return dict(kv.split("=") for kv in buf.value.decode().split())
+        d = dict(kv.split("=") for kv in buf.value.decode().split())
+        d["kvres"] = str(int(self.lib.fat5_attn_bwd_kvres(ctypes.byref(self.p))))  # (the dQ body's resident K / V form: a host call of its own)
+        return d
 
     def bwd_launches(self):
         """1: dQ and dK/dV halves share one launch (short sequences); 2: two kernels (fat5_attn_bwd_launches)."""

@@ -57,6 +57,7 @@ enum fat5_variant {
   FAT5_V_QDB64_ON = 2097152, FAT5_V_QDB64_OFF = 4194304,        /* dense (1,H,M,N) bias, bf16, D = 64: dQ and the batch-reduced dbias in one kernel, four batch elements per workgroup (attn_bwd_qdb64.h) wherever legal / never */
   FAT5_V_QDIAG_ON = 8388608, FAT5_V_QDIAG_OFF = 16777216,       /* (continued below) */
   FAT5_V_DTABLE_RUNS_ON = 33554432, FAT5_V_DTABLE_RUNS_OFF = 67108864, /* T5 table gradient: the per-bucket reduction over the runs of rpe_bucket_host wherever legal (the default) / never (the per-diagonal reduction + bucket scan) */       /* T5 bias, one-launch 64-wide backward: the table gradient's per-diagonal sums formed by the dQ workgroups (attn_bwd_q64_body<QDG>) wherever that launch runs / never */
+  FAT5_V_KVRES_ON = 134217728, FAT5_V_KVRES_OFF = 268435456,     /* 64-row dQ body (alone or in the one-launch backward), at most 512 keys, operands staged: the head's whole K / V resident in LDS instead of the four-slot ring wherever legal (the default) / never; bit-identical results */
   FAT5_V_FUSED64_ON = 65536, FAT5_V_FUSED64_OFF = 131072         /* backward: the 64-wide dK/dV and dQ bodies in ONE launch (the dK/dV half forms its row statistics itself) wherever legal / never; dense (1,H,M,N) bias: the dense dK/dV body beside the dQ + dBias body in one launch behind a small row-statistics kernel */
 };
 
@@ -167,6 +168,9 @@ int fat5_attn_bwd_launches(const fat5_attn_params* p);
 /* Which kernel bodies this problem runs -- "fwd=64row-ksplit dq=32row dkdv=64key-mixed:4 fused=0 dbias=direct" -- written to `out`
  * (n bytes).  Host-only (no device, no pointer of `p` is followed): tests pin the dispatch rules with it. */
 int fat5_attn_describe(const fat5_attn_params* p, char* out, size_t n);
+/* 1 when the backward of this problem runs the 64-row dQ body with the head's whole K / V resident in LDS (at most 512 keys, operands staged;
+ * FAT5_V_KVRES_ON / _OFF), else 0 (also on invalid params).  Host-only; the text of fat5_attn_describe does not carry it. */
+int fat5_attn_bwd_kvres(const fat5_attn_params* p);
 /* the same backward, one stage at a time (profiling / stream overlap).  Order matters:
  * FAT5_BWD_DQ (writes delta + dq) must precede FAT5_BWD_DKDV (reads delta; writes dk, dv, dS / partial
  * diagonal sums), which must precede FAT5_BWD_REDUCE (dbias / drpe1d).  fat5_attn_bwd == FAT5_BWD_ALL.

@@ -2,7 +2,8 @@
   cd flasht5_amd/lib && cp -r obj obj_trace && rm obj_trace/attn_bwd64_d64.o; FAT5_VARIANT=trace FAT5_EXTRA_FLAGS=-DFAT5_TRACE=1 python flasht5_amd/build.py
 usage (GPU box): FAT5_LIB_VARIANT=trace python tools/trace64.py [--S 512] [--mode rpe] [--variant BITS] [--stage 1|2]
 Thread 0 of every workgroup stamps s_memtime at: 0 entry, 1 prologue done (operands loaded, first steps in LDS), 2 first scores, 3 main loop done,
-4 drain done, 5 partial sums out (dK/dV), 6 outputs stored.  Printed: medians relative to the first workgroup's entry, in shader-clock ticks."""
+4 drain done, 5 partial sums out (dK/dV), 6 outputs stored; dQ workgroups in the resident K / V form also 14: all key steps landed (the barrier in step 3's iteration --
+"loop" then splits into "first scores -> K/V resident" and the barrier-free rest).  Printed: medians relative to the first workgroup's entry, in shader-clock ticks."""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -45,6 +46,8 @@ def show(rows, title):
             if rows[:, k_].min() <= 0:
                 continue
             print(f"   prologue detail: entry -> {n_:18s} {np.median(rows[:, k_] - rows[:, 0]):8.0f}")
+    if rows[:, 14].min() > 0:   # (resident K / V form of the dQ body: its second and last visibility point)
+        print(f"   loop detail: first scores -> K/V resident (vmcnt(0) + barrier) {np.median(rows[:, 14] - rows[:, 2]):8.0f}   -> loop end {np.median(rows[:, 3] - rows[:, 14]):8.0f}")
     for n_, k_ in (("dQ rows on their way", 12), ("diagonal arrays complete (barrier)", 13)):
         if rows[:, k_].min() > 0:
             print(f"   epilogue detail: drain -> {n_:34s} {np.median(rows[:, k_] - rows[:, 4]):8.0f}")
