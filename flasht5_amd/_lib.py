@@ -305,7 +305,7 @@ EXPORTS = (
     "fat5_lookup_draft", "fat5_sizeof_lookup_params",
     "fat5_pack_plan", "fat5_sizeof_pack_params",
     "fat5_ul2_collate", "fat5_sizeof_ul2_params",
-    "fat5_w8_quantize", "fat5_sizeof_w8_quant_params", "fat5_w8_linear", "fat5_sizeof_w8_linear_params",
+    "fat5_w8_quantize", "fat5_sizeof_w8_quant_params", "fat5_w8_linear", "fat5_sizeof_w8_linear_params", "fat5_w8_linear_mma",
     "fat5_dropout", "fat5_dropout_add_rmsnorm_fwd", "fat5_dropout_add_rmsnorm_bwd", "fat5_sizeof_dropout_desc",
     "fat5_seq_pool_fwd", "fat5_seq_pool_bwd", "fat5_sizeof_seq_pool_params",
     "fat5_kd_fwd", "fat5_kd_bwd", "fat5_kd_fwd_bwd", "fat5_sizeof_kd_params",
@@ -487,6 +487,8 @@ def load():
         size_fn.restype = ctypes.c_size_t
         if size_fn() != ctypes.sizeof(struct):
             raise ImportError(f"{name} layout mismatch: library {size_fn()} B, binding {ctypes.sizeof(struct)} B")
+    lib.fat5_w8_linear_mma.restype = ctypes.c_int
+    lib.fat5_w8_linear_mma.argtypes = [ctypes.POINTER(W8LinearParams), ctypes.c_void_p]
     for fn in (lib.fat5_seq_pool_fwd, lib.fat5_seq_pool_bwd):
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.POINTER(SeqPoolParams), ctypes.c_void_p]

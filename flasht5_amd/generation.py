@@ -86,6 +86,7 @@ class DecodeState:
     cross_k_scale: Optional[List[torch.Tensor]] = None
     cross_v_scale: Optional[List[torch.Tensor]] = None
     w8: Optional[object] = None   # FP8 weights (weight_dtype="fp8"): the model's w8.DecoderW8; the step then runs `_decoder_blocks_w8`
+    w8_kernel: str = "rows"       # weight_kernel: "matrix" sends the step's w8_linear calls of more than one row tile to the MFMA kernel
 
     def scales(self, i):
         """forward_decode's keywords for layer i -> (self-attention's, cross-attention's); empty without FP8 caches"""
@@ -244,7 +245,7 @@ def encode(model, input_ids, pad=None):
 
 @torch.no_grad()
 def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1, prompt_length=1, kv_cache_dtype=None,
-                      weight_dtype=None):
+                      weight_dtype=None, weight_kernel=None):
     """Run the encoder, project every decoder layer's cross-attention K / V once and allocate self-attention caches of capacity
     `max_length + prompt_length` (a decoder prompt of `prompt_length` tokens, the start token included, then max_length new ones).
     `attention_mask` (B, L), right-padded, is applied: it is validated with one host read before the encoder runs
@@ -256,9 +257,10 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     the cross-attention K / V are quantised once (`quantize_kv`); anything but these and None raises before the encoder runs.
     weight_dtype="fp8" (alias "fp8_e4m3"): the state's steps read the model's FP8 decoder weights
     (`quantize_decoder_weights`, built once per model) through `w8_linear`; checked, like the decoder's dtype and shapes, before
-    the encoder runs."""
+    the encoder runs.  weight_kernel (None, "rows" or "matrix"; with weight_dtype="fp8" only): see `generate`."""
     fp8 = check_kv_cache_dtype(kv_cache_dtype, "init_decode_state")
     w8 = _check_weight_dtype(model, weight_dtype, "init_decode_state")
+    w8_kernel = _check_weight_kernel(weight_kernel, weight_dtype, "init_decode_state")
     _check_supported(model)
     first = model.decoder.block[0].self_attention_layer.self_attention
     cap = int(max_length) + int(prompt_length)
@@ -303,6 +305,7 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     if w8:
         from .w8 import quantize_decoder_weights
         state.w8 = quantize_decoder_weights(model)
+        state.w8_kernel = w8_kernel
     if num_beams > 1:
         state.cross_batch_idx = torch.arange(Bk, dtype=torch.int32, device=dev) // int(num_beams)
         state.row_batch = torch.zeros((Bk, cap), dtype=torch.int32, device=dev)
@@ -339,33 +342,41 @@ def _check_weight_dtype(model, weight_dtype, what="generate"):
     return True
 
 
+def _check_weight_kernel(weight_kernel, weight_dtype, what="generate"):
+    from .w8 import check_weight_kernel
+    return check_weight_kernel(weight_kernel, weight_dtype, what)
+
+
 def _decoder_blocks_w8(model, state, h, chunk_seqlens=None):
     """`_decoder_blocks` over the FP8 weights of `state.w8`: per block norm + qkv, self-attention, o + residual,
     norm + q, cross-attention, o + residual, norm + wi, the gated activation, wo + residual -- every projection ONE `w8_linear`
-    launch with its RMSNorm in front and its residual add behind"""
+    launch with its RMSNorm in front and its residual add behind, on the kernel the call's B * M rows select
+    (`w8.kernel_for_rows`: a shape, so static under a graph)"""
     from . import w8 as w8m   # (looked up per call: the entry point can be wrapped)
     from .gated_act import gated_act_packed
     pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
     B, M = h.shape[:2]
+    kern = w8m.kernel_for_rows(state.w8_kernel, B * M)
     for i, (blk, lw) in enumerate(zip(model.decoder.block, state.w8.layers)):
         sa, ca, ff = blk.self_attention_layer, blk.cross_attention_layer, blk.ff_layer
         ssc, csc = state.scales(i)
         att = sa.self_attention
         H, D, inner = att.n_heads, att.key_value_proj_dim, att.inner_dim
-        qkv = w8m.w8_linear(h, *lw.qkv, norm_weight=sa.layer_norm.weight, eps=sa.layer_norm.variance_epsilon)
+        qkv = w8m.w8_linear(h, *lw.qkv, norm_weight=sa.layer_norm.weight, eps=sa.layer_norm.variance_epsilon, kernel=kern)
         q, k, v = (qkv[..., j * inner:(j + 1) * inner].view(B, M, H, D) for j in range(3))
         o = att.attend_decode(q, k, v, state.self_k[i], state.self_v[i], state.cache_seqlens, position_bias=state.position_bias,
                               position=pos, cache_row_batch=state.row_batch, chunk_seqlens=chunk_seqlens, **ssc)
-        h = w8m.w8_linear(o, *lw.self_o, residual=h)
+        h = w8m.w8_linear(o, *lw.self_o, residual=h, kernel=kern)
         att = ca.cross_attention
-        q = w8m.w8_linear(h, *lw.cross_q, norm_weight=ca.layer_norm.weight, eps=ca.layer_norm.variance_epsilon).view(B, M, H, D)
+        q = w8m.w8_linear(h, *lw.cross_q, norm_weight=ca.layer_norm.weight, eps=ca.layer_norm.variance_epsilon, kernel=kern)
+        q = q.view(B, M, H, D)
         o = att.attend_decode(q, None, None, state.cross_k[i], state.cross_v[i], None, position=pos,
                               cache_batch_idx=state.cross_batch_idx, cross_seqlens=state.cross_seqlens, chunk_seqlens=chunk_seqlens,
                               **csc)
-        h = w8m.w8_linear(o, *lw.cross_o, residual=h)
-        g = w8m.w8_linear(h, *lw.wi, norm_weight=ff.layer_norm.weight, eps=ff.layer_norm.variance_epsilon)
+        h = w8m.w8_linear(o, *lw.cross_o, residual=h, kernel=kern)
+        g = w8m.w8_linear(h, *lw.wi, norm_weight=ff.layer_norm.weight, eps=ff.layer_norm.variance_epsilon, kernel=kern)
         t = gated_act_packed(g, ff.act.act_name) if ff.act.glu else ff.act.act(g)
-        h = w8m.w8_linear(t, *lw.wo, residual=h)
+        h = w8m.w8_linear(t, *lw.wo, residual=h, kernel=kern)
     return h
 
 
@@ -380,7 +391,8 @@ def _head(model, state, h):
         return model.lm_head(model.decoder.final_layer_norm(h))
     from . import w8 as w8m
     ln = model.decoder.final_layer_norm
-    return w8m.w8_linear(h, *state.w8.lm_head, norm_weight=ln.weight, eps=ln.variance_epsilon)
+    return w8m.w8_linear(h, *state.w8.lm_head, norm_weight=ln.weight, eps=ln.variance_epsilon,
+                         kernel=w8m.kernel_for_rows(state.w8_kernel, h.numel() // h.shape[-1]))
 
 
 @torch.no_grad()
@@ -542,12 +554,12 @@ def _beam_step(model, state, tok, bs, opts, proc=None):
 
 
 def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, length_penalty, early_stopping, return_scores,
-                   proc=None, kv_cache_dtype=None, weight_dtype=None):
+                   proc=None, kv_cache_dtype=None, weight_dtype=None, weight_kernel=None):
     from .beam import new_state, keep_going
     B = input_ids.shape[0]
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask, num_beams=k, kv_cache_dtype=kv_cache_dtype,
-                              weight_dtype=weight_dtype)
+                              weight_dtype=weight_dtype, weight_kernel=weight_kernel)
     bs = new_state(B, k, int(max_length) + 1, state.capacity, dev)
     proc = _proc_on_device(proc, dev, input_ids, attention_mask, None, k)
     bs.cache_row_batch = state.row_batch  # (one table: the decode kernel reads it, the beam step reorders it)
@@ -570,7 +582,7 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
              decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
              decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
              encoder_repetition_penalty=1.0, encoder_no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
-             forced_bos_token_id=None, forced_eos_token_id=None, weight_dtype=None):
+             forced_bos_token_id=None, forced_eos_token_id=None, weight_dtype=None, weight_kernel=None):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -680,9 +692,18 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     kv_cache_dtype and graph=True work with it; the tokens can differ from the default's where two logits are within the
     quantisation error.  Refused with ValueError before an encoder runs: any other value, a decoder whose weights are fp32 (or
     of mixed dtypes), and weight shapes outside the kernel's contract (input widths multiples of 64 up to 16384, output widths
-    multiples of 8)."""
+    multiples of 8).
+
+    `weight_kernel` (with weight_dtype="fp8" only): None or "rows" (everything above, unchanged) or "matrix": every
+    `w8_linear` call of a step with more than 8 rows (`w8.MATRIX_MIN_ROWS`: batches above 8, B * num_beams beam rows, B * P rows of
+    a prompt chunk, B * (gamma + 1) rows of a verification step) runs on the MFMA kernel (csrc/w8_mma_kernels.h), whose time is
+    nearly flat in the row count up to 64; calls of at most 8 rows keep the row kernel and its bits.  The choice is made from the
+    call's shape, so nothing is added to a step: no launch, no host read; graph=True and every mode work as above, the assistant
+    gets the same setting.  The tokens can differ from "rows" where two logits are within the fp32 summation error.  Any other
+    value, or a weight_kernel without weight_dtype="fp8", raises ValueError before an encoder runs."""
     check_kv_cache_dtype(kv_cache_dtype)
     _check_weight_dtype(model, weight_dtype)
+    _check_weight_kernel(weight_kernel, weight_dtype)
     from .beam import check_args as check_beam_args
     check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping, do_sample)
     P = _check_prompt(model, input_ids, decoder_input_ids, num_beams, decoder_attention_mask)
@@ -714,16 +735,17 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
         return speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph,
                                     prompt_lookup_num_tokens if lookup else num_assistant_tokens, P, decoder_input_ids,
                                     bool(return_stats), kv_cache_dtype, lookup_ngram=max_matching_ngram_size if lookup else None,
-                                    sampling=_sampling(do_sample, temperature, top_k, top_p, seed), weight_dtype=weight_dtype)
+                                    sampling=_sampling(do_sample, temperature, top_k, top_p, seed), weight_dtype=weight_dtype,
+                                    weight_kernel=weight_kernel)
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
-                              early_stopping, return_scores, proc, kv_cache_dtype, weight_dtype)
+                              early_stopping, return_scores, proc, kv_cache_dtype, weight_dtype, weight_kernel)
     proc = _proc_on_device(proc, input_ids.device, input_ids, attention_mask, dec_pad)
     sampling = _sampling(do_sample, temperature, top_k, top_p, seed)
     B = input_ids.shape[0]
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask, prompt_length=P, kv_cache_dtype=kv_cache_dtype,
-                              weight_dtype=weight_dtype)
+                              weight_dtype=weight_dtype, weight_kernel=weight_kernel)
     labels = torch.zeros((B, state.capacity), dtype=torch.long, device=dev)
     tok = torch.zeros((B,), dtype=torch.long, device=dev)
     seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)

@@ -9,6 +9,7 @@ RNE(clamp(W / scale, -448, 448)); a row with an inf or a NaN gets scale +inf and
 launch: y = round(scale[n] * sum_k xin * w8) with fp32 accumulation in a fixed order (bitwise reproducible, graph replay included);
 `norm_weight` puts the T5 RMSNorm of x in front (bit for bit `w8_linear(fast_rms_layernorm(x, g, eps), ...)`), `residual` adds it
 behind (bit for bit `residual + w8_linear(...)`).  Shapes: K a multiple of 64 in [64, 16384], N a multiple of 8.
+`kernel="matrix"` runs the same contract on the matrix pipe (csrc/w8_mma_kernels.h), for calls with more than one tile of 8 rows.
 
 `quantize_decoder_weights(model)` builds, once per model, what a cached decoding step with `weight_dtype="fp8"` reads
 (generation.py).  Forward only; there is no CPU path and no fallback."""
@@ -25,6 +26,15 @@ COLS_PER_BLOCK = 16     # (W8_COLS)
 ROW_TILE = 8            # (W8_RT)
 K_TILE = 2048           # (W8_KT)
 LANE_K = 512            # (W8_LANE_K): K elements a wave covers per step
+# the matrix-pipe kernel (csrc/w8_mma_kernels.h)
+MMA_ROW_TILE = 64       # (W8M_ROWS): rows of one workgroup pass, four MFMA fragments of 16
+MMA_COLS = 32           # (W8M_COLS): output columns of one workgroup
+MMA_K_CHUNK = 64        # (W8M_KC): K elements one wave stages and multiplies at a time
+MMA_K_PIECE = 256       # (W8M_K_PIECE): one round of the four waves
+KERNELS = ("rows", "matrix")
+# generation's weight_kernel="matrix": a w8_linear call with at least this many rows takes the matrix kernel.  One row tile (R <= 8)
+# sits on the launch floor in either kernel and keeps the row kernel's bits; 9 <= R <= 15 is in DESIGN 4.23's kernel table.
+MATRIX_MIN_ROWS = ROW_TILE + 1
 
 
 def check_shape(N, K, what):
@@ -42,6 +52,22 @@ def check_weight_dtype(weight_dtype, what="generate"):
     if isinstance(weight_dtype, str) and weight_dtype in ("fp8", "fp8_e4m3"):
         return True
     raise ValueError(f"{what}: weight_dtype {weight_dtype!r} (None, 'fp8' or its alias 'fp8_e4m3')")
+
+
+def check_weight_kernel(weight_kernel, weight_dtype, what="generate"):
+    """None / "rows" / "matrix" -> the kernel name a state carries ("rows" for None); needs weight_dtype="fp8"; host only"""
+    if weight_kernel is None:
+        return "rows"
+    if not (isinstance(weight_kernel, str) and weight_kernel in KERNELS):
+        raise ValueError(f"{what}: weight_kernel {weight_kernel!r} (None, 'rows' or 'matrix')")
+    if not check_weight_dtype(weight_dtype, what):
+        raise ValueError(f"{what}: weight_kernel {weight_kernel!r} needs weight_dtype='fp8'")
+    return weight_kernel
+
+
+def kernel_for_rows(weight_kernel, rows):
+    """the `kernel=` of one w8_linear call of a step: the matrix kernel from MATRIX_MIN_ROWS rows on, where the state asks for it"""
+    return "matrix" if weight_kernel == "matrix" and rows >= MATRIX_MIN_ROWS else "rows"
 
 
 # ------------------------------------------------------------------------------------------------------------------ operators
@@ -99,10 +125,8 @@ def quantize_weight(W, out=None, scale=None):
     return out, scale
 
 
-@torch.library.custom_op("fat5::w8_linear", mutates_args=(), device_types="cuda")
-def w8_linear_op(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, norm_weight: Optional[torch.Tensor], eps: float,
-                 residual: Optional[torch.Tensor]) -> torch.Tensor:
-    """x (R, K), w8 (N, K) float8_e4m3fn, scale (N,) -> (R, N) contiguous, in one launch (fat5_w8_linear)"""
+def _launch_linear(entry, x, w8, scale, norm_weight, eps, residual):
+    """the checks, the output and the one launch of `entry` (fat5_w8_linear or fat5_w8_linear_mma: one parameter struct)"""
     _check_linear(x, w8, scale, norm_weight, eps, residual)
     for t in (x, w8, scale, norm_weight, residual):
         if t is not None and (not t.is_cuda or t.device != x.device):
@@ -123,11 +147,26 @@ def w8_linear_op(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, norm_we
         p.residual, p.residual_stride = residual.data_ptr(), (residual.stride(0) if R > 1 else N)
     p.y, p.y_stride = y.data_ptr(), y.stride(0)
     with _lib.on_device(x.device):
-        _lib.check(_lib.load().fat5_w8_linear(p, _lib.stream_ptr(x.device)), "fat5_w8_linear")
+        _lib.check(getattr(_lib.load(), entry)(p, _lib.stream_ptr(x.device)), entry)
     return y
 
 
+@torch.library.custom_op("fat5::w8_linear", mutates_args=(), device_types="cuda")
+def w8_linear_op(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, norm_weight: Optional[torch.Tensor], eps: float,
+                 residual: Optional[torch.Tensor]) -> torch.Tensor:
+    """x (R, K), w8 (N, K) float8_e4m3fn, scale (N,) -> (R, N) contiguous, in one launch (fat5_w8_linear)"""
+    return _launch_linear("fat5_w8_linear", x, w8, scale, norm_weight, eps, residual)
+
+
+@torch.library.custom_op("fat5::w8_linear_mma", mutates_args=(), device_types="cuda")
+def w8_linear_mma_op(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, norm_weight: Optional[torch.Tensor], eps: float,
+                     residual: Optional[torch.Tensor]) -> torch.Tensor:
+    """`w8_linear_op` on the matrix pipe (fat5_w8_linear_mma): the same contract, the MFMA kernel's summation order"""
+    return _launch_linear("fat5_w8_linear_mma", x, w8, scale, norm_weight, eps, residual)
+
+
 @w8_linear_op.register_fake
+@w8_linear_mma_op.register_fake
 def _w8_linear_fake(x, w8, scale, norm_weight, eps, residual):
     return x.new_empty((x.shape[0], w8.shape[0]))
 
@@ -174,10 +213,14 @@ def _rows(t, width):
     return t2 if (t2.numel() == 0 or _row_ready(t2)) else t2.contiguous()
 
 
-def w8_linear(x, w8, scale, *, norm_weight=None, eps=1e-6, residual=None):
+def w8_linear(x, w8, scale, *, norm_weight=None, eps=1e-6, residual=None, kernel="rows"):
     """y (..., N) = x (..., K) @ (w8 * scale[:, None]).T in ONE launch, x fp16 / bf16 on the GPU, w8 / scale from `quantize_weight`.
     `norm_weight` (K,) of x's dtype: the T5 RMSNorm of x (with `eps`) is applied first, inside the launch; `residual` (..., N) of
-    x's dtype is added to the rounded result, inside the launch.  Both are invisible in the bits (see the module's text)."""
+    x's dtype is added to the rounded result, inside the launch.  Both are invisible in the bits (see the module's text).
+    `kernel`: "rows" (the VALU kernel over row tiles of 8: the choice for R <= 8) or "matrix" (the MFMA kernel over row tiles of 64,
+    csrc/w8_mma_kernels.h: the choice for more rows).  Each has its own fixed summation order, so the two differ in the last bits."""
+    if kernel not in KERNELS:
+        raise ValueError(f"w8_linear: kernel {kernel!r} ('rows' or 'matrix')")
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, norm_weight, residual)):
         raise RuntimeError("w8_linear is forward only: call it under torch.no_grad() / inference_mode(), or detach")
     if x.dim() < 1 or w8.dim() != 2:
@@ -193,7 +236,8 @@ def w8_linear(x, w8, scale, *, norm_weight=None, eps=1e-6, residual=None):
     _check_linear(x2, w8, scale, norm_weight, float(eps), r2)
     if not x.is_cuda:
         raise ValueError("w8_linear: tensors must be on the GPU (there is no CPU path)")
-    return w8_linear_op(x2, w8, scale, norm_weight, float(eps), r2).view(lead + (N,))
+    op = w8_linear_mma_op if kernel == "matrix" else w8_linear_op
+    return op(x2, w8, scale, norm_weight, float(eps), r2).view(lead + (N,))
 
 
 # ------------------------------------------------------------------------------------------- what a cached decoding step reads

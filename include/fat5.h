@@ -1092,6 +1092,10 @@ int fat5_ul2_collate(const fat5_ul2_params* p, void* hip_stream);
  *     x, residual and y: 16-byte aligned bases, row strides multiples of 8 elements (y and residual: 2-byte alignment of each
  *     element is all the kernel needs, the rule is kept uniform); w8: 8-byte aligned base, row stride a multiple of 8; y may alias
  *     residual (each element is read and written by one lane), not x.
+ *   - fat5_w8_linear_mma: the same struct, checks and result, formed on the matrix pipe (w8_mma_kernels.h: bf16 / fp16 MFMA on weights
+ *     converted in registers, exactly) for calls with more than one tile of 8 rows; the summation order is the MFMA kernel's, fixed,
+ *     independent of R, N and the grid (so bitwise reproducible too, but not fat5_w8_linear's bits: both lie inside the bound of
+ *     tests/w8_ref.py with c = 2 K).  The norm_weight and residual identities above hold for it bit for bit.
  */
 typedef struct fat5_w8_quant_params {
   int64_t N;                  /* weight rows (output features), N % 8 == 0 */
@@ -1126,6 +1130,7 @@ typedef struct fat5_w8_linear_params {
 } fat5_w8_linear_params;
 size_t fat5_sizeof_w8_linear_params(void);
 int fat5_w8_linear(const fat5_w8_linear_params* p, void* hip_stream);
+int fat5_w8_linear_mma(const fat5_w8_linear_params* p, void* hip_stream);
 
 /*
  * Sequence pooling (pool_kernels.h): per-token hidden states to one vector per sequence, and its gradient.

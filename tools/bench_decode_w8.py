@@ -6,8 +6,10 @@ layers, 2 encoder layers -- the encoder is not part of a step) at B = 1.  Both g
 default, fp8, ...: REPEATS blocks of ITERS replays each, device events around a block, the cache lengths reset before every block), so
 a drift of the clocks hits both alike; reported are the median and the spread (min .. max) of the block means, in ms per token.
 
-Per kernel: `w8_linear` (plain instance) against `F.linear` in bf16 at (R, K, N) in {1, 16, 64} x {(768, 2304), (768, 4096),
-(2048, 768), (768, 32768)}, timed the same way; GB/s counts the weight bytes (N K, or 2 N K), the scales, x and y.
+Per kernel: `w8_linear` (plain instance), kernel="rows" and kernel="matrix", against `F.linear` in bf16 at (R, K, N) in
+{1, 9, 16, 64, 128} x {(768, 2304), (768, 4096), (2048, 768), (768, 32768)}, the three graphs taking turns the same way; the end-to-end
+table has a `weight_kernel="matrix"` column at B > 8.  The matrix kernel is accepted against the row kernel of the same run: its
+min..max over the blocks must lie wholly below the row kernel's ("below rows" / "below fp8"); GB/s counts the weight bytes (N K, or 2 N K), the scales, x and y.
 Writes profiles/decode_w8_bench.log and prints one JSON line at the end.  `--kernel-only` / `--e2e-only` run one half,
 `--quick` only FAT5-base at B = 1 of the second."""
 import json
@@ -51,23 +53,25 @@ def block(g, before=None):
     return s.elapsed_time(e) / ITERS * 1e-3
 
 
-def alternate(ga, gb, before_a=None, before_b=None):
-    ta, tb = [], []
+def alternate(graphs, befores=None):
+    """the block means of every graph, the graphs taking turns block by block -> one list of REPEATS times per graph"""
+    befores = befores or [None] * len(graphs)
+    times = [[] for _ in graphs]
     for _ in range(REPEATS):
-        ta.append(block(ga, before_a))
-        tb.append(block(gb, before_b))
-    return ta, tb
+        for t, g, before in zip(times, graphs, befores):
+            t.append(block(g, before))
+    return times
 
 
 def fmt(t, unit):
     return f"{statistics.median(t) * unit:9.3f} ({min(t) * unit:9.3f}..{max(t) * unit:9.3f})"
 
 
-def step_graph(model, ids, weight_dtype):
+def step_graph(model, ids, weight_dtype, weight_kernel=None):
     """one captured decoding step of a fresh state -> (graph, reset, the tensors the graph uses): `reset` puts the cache lengths
     back to one token"""
     B = ids.shape[0]
-    state = model.init_decode_state(ids, max_length=ITERS + 16, weight_dtype=weight_dtype)
+    state = model.init_decode_state(ids, max_length=ITERS + 16, weight_dtype=weight_dtype, weight_kernel=weight_kernel)
     labels = torch.zeros((B, state.capacity), dtype=torch.long, device="cuda")
     tok = torch.zeros((B,), dtype=torch.long, device="cuda")
     eos = torch.zeros((B,), dtype=torch.bool, device="cuda")
@@ -83,7 +87,10 @@ def step_graph(model, ids, weight_dtype):
 def e2e(say):
     rows = {}
     say("# ms per token of one graph-replayed greedy step; default = 16-bit weights (library GEMMs), fp8 = weight_dtype='fp8'")
-    say("# model        B | default ms median (min..max)     | fp8 ms median (min..max)         | fp8/default")
+    say("# matrix = weight_dtype='fp8', weight_kernel='matrix' (B > 8: the MFMA kernel in every projection); accepted where its")
+    say("# min..max lies wholly below fp8's")
+    say("# model        B | default ms median (min..max)     | fp8 ms median (min..max)         | fp8/default | matrix ms median "
+        "(min..max)      | matrix/fp8 | below fp8")
     wide = dict(d_model=2048, d_ff=5120, num_heads=32, d_kv=64, num_layers=2, num_decoder_layers=24)
     quick = "--quick" in sys.argv   # (FAT5-base at B = 1 alone)
     for name, cfg, batches in (("FAT5-base", {}, (1,) if quick else (1, 16, 64)),) + (() if quick else (("wide-2048", wide, (1,)),)):
@@ -95,13 +102,25 @@ def e2e(say):
             with torch.no_grad():
                 g16, r16, s16 = step_graph(model, ids, None)
                 g8, r8, s8 = step_graph(model, ids, "fp8")
-                t16, t8 = alternate(g16, g8, r16, r8)
+                if B > 8:
+                    gm, rm, sm = step_graph(model, ids, "fp8", "matrix")
+                    t16, t8, tm = alternate([g16, g8, gm], [r16, r8, rm])
+                else:
+                    (t16, t8), tm = alternate([g16, g8], [r16, r8]), None
             m16, m8 = statistics.median(t16), statistics.median(t8)
             rows[f"{name}_B{B}"] = {"default_ms": round(m16 * 1e3, 4), "default_min_ms": round(min(t16) * 1e3, 4),
                                     "default_max_ms": round(max(t16) * 1e3, 4), "fp8_ms": round(m8 * 1e3, 4),
                                     "fp8_min_ms": round(min(t8) * 1e3, 4), "fp8_max_ms": round(max(t8) * 1e3, 4),
                                     "fp8_over_default": round(m8 / m16, 3)}
-            say(f"  {name:10s} {B:3d} | {fmt(t16, 1e3)} | {fmt(t8, 1e3)} | {m8 / m16:.3f}")
+            line = f"  {name:10s} {B:3d} | {fmt(t16, 1e3)} | {fmt(t8, 1e3)} | {m8 / m16:.3f}"
+            if tm is not None:
+                mm = statistics.median(tm)
+                rows[f"{name}_B{B}"].update(matrix_ms=round(mm * 1e3, 4), matrix_min_ms=round(min(tm) * 1e3, 4),
+                                            matrix_max_ms=round(max(tm) * 1e3, 4), matrix_over_fp8=round(mm / m8, 3),
+                                            matrix_below_fp8=max(tm) < min(t8))
+                line += f"       | {fmt(tm, 1e3)} | {mm / m8:.3f}      | {'yes' if max(tm) < min(t8) else 'NO'}"
+                del gm, sm
+            say(line)
             del g16, g8, s16, s8
         del model
         torch.cuda.empty_cache()
@@ -110,24 +129,31 @@ def e2e(say):
 
 def kernels(say):
     rows = {}
-    say("# w8_linear (plain) against F.linear in bf16; us per call, graph-replayed")
-    say("#   R     K      N | F.linear us median (min..max)    GB/s | w8_linear us median (min..max)   GB/s | w8/bf16")
+    say("# w8_linear (plain), kernel='rows' and kernel='matrix', against F.linear in bf16; us per call, graph-replayed")
+    say("#   R     K      N | F.linear us median (min..max)    GB/s | rows us median (min..max)        GB/s | rows/bf16 | matrix us "
+        "median (min..max)      GB/s | matrix/bf16 | matrix/rows | below rows")
     for K, N in ((768, 2304), (768, 4096), (2048, 768), (768, 32768)):
         W = (torch.randn(N, K, device="cuda") * 0.05).bfloat16()
         w8, sc = quantize_weight(W)
-        for R in (1, 16, 64):
+        for R in (1, 9, 16, 64, 128):
             x = torch.randn(R, K, device="cuda", dtype=torch.bfloat16)
             g16 = capture(lambda: F.linear(x, W))
             g8 = capture(lambda: w8_linear(x, w8, sc))
-            t16, t8 = alternate(g16, g8)
+            gm = capture(lambda: w8_linear(x, w8, sc, kernel="matrix"))
+            t16, t8, tm = alternate([g16, g8, gm])
             io = 2 * R * K + 2 * R * N
             n16, n8 = 2 * N * K + io, N * K + 4 * N + io
-            m16, m8 = statistics.median(t16), statistics.median(t8)
+            m16, m8, mm = statistics.median(t16), statistics.median(t8), statistics.median(tm)
             rows[f"R{R}_K{K}_N{N}"] = {"bf16_us": round(m16 * 1e6, 2), "bf16_GBs": round(n16 / m16 / 1e9, 1), "w8_us": round(m8 * 1e6, 2),
                                        "w8_min_us": round(min(t8) * 1e6, 2), "w8_max_us": round(max(t8) * 1e6, 2),
-                                       "w8_GBs": round(n8 / m8 / 1e9, 1), "w8_over_bf16": round(m8 / m16, 3)}
-            say(f"  {R:3d} {K:5d} {N:6d} | {fmt(t16, 1e6)} {n16 / m16 / 1e9:7.1f} | {fmt(t8, 1e6)} {n8 / m8 / 1e9:7.1f} | {m8 / m16:.3f}")
-            del g16, g8
+                                       "w8_GBs": round(n8 / m8 / 1e9, 1), "w8_over_bf16": round(m8 / m16, 3),
+                                       "matrix_us": round(mm * 1e6, 2), "matrix_min_us": round(min(tm) * 1e6, 2),
+                                       "matrix_max_us": round(max(tm) * 1e6, 2), "matrix_over_bf16": round(mm / m16, 3),
+                                       "matrix_over_rows": round(mm / m8, 3), "matrix_below_rows": max(tm) < min(t8)}
+            say(f"  {R:3d} {K:5d} {N:6d} | {fmt(t16, 1e6)} {n16 / m16 / 1e9:7.1f} | {fmt(t8, 1e6)} {n8 / m8 / 1e9:7.1f} | {m8 / m16:.3f}"
+                f"     | {fmt(tm, 1e6)} {n8 / mm / 1e9:7.1f} | {mm / m16:.3f}       | {mm / m8:.3f}       | "
+                f"{'yes' if max(tm) < min(t8) else 'NO'}")
+            del g16, g8, gm
     return rows
 
 
