@@ -39,6 +39,7 @@ from .ul2 import ul2_lengths, ul2_tables, ul2_collate, UL2Collator, UL2Tables  #
 from .attention_module import FlashT5Attention  # noqa: E402
 from .modules import FlashT5LayerNorm, FlashT5CrossEntropyLoss  # noqa: E402
 from .adamw_scaled import AdamWScale  # noqa: E402
+from .adafactor import Adafactor  # noqa: E402
 from .fat5_step import FAT5Config, FAT5ForConditionalGeneration, allreduce_gradients, train_step, GraphedTrainStep  # noqa: E402
 from .distill import DistilledFAT5  # noqa: E402
 from .pooling import sequence_pool  # noqa: E402

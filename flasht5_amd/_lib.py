@@ -291,6 +291,7 @@ EXPORTS = (
     "fat5_rmsnorm_fwd", "fat5_rmsnorm_bwd_workspace_bytes", "fat5_rmsnorm_bwd", "fat5_add_rmsnorm_fwd", "fat5_add_rmsnorm_bwd",
     "fat5_ce_fwd", "fat5_ce_bwd", "fat5_ce_fwd_bwd", "fat5_fold_weights", "fat5_fold_weights_bwd", "fat5_fold_weights_bwd_scratch_bytes", "fat5_rmsnorm_unit_bwd", "fat5_gated_act_fwd", "fat5_gated_act_bwd",
     "fat5_adamw_scale_step", "fat5_adamw_scale_step_clipped", "fat5_adamw_scale_step_dev", "fat5_adamw_grad_sumsq", "fat5_sizeof_adamw_tensor",
+    "fat5_adafactor_step", "fat5_adafactor_workspace_bytes", "fat5_sizeof_adafactor_tensor",
     "fat5_rope_apply", "fat5_sizeof_rope_params",
     "fat5_fire_fwd", "fat5_fire_bwd", "fat5_fire_bwd_workspace_bytes", "fat5_sizeof_fire_params",
     "fat5_attn_decode", "fat5_attn_decode_workspace_bytes", "fat5_sizeof_decode_params",
@@ -382,6 +383,11 @@ def load():
     lib.fat5_adamw_grad_sumsq.restype = ctypes.c_int
     lib.fat5_adamw_grad_sumsq.argtypes = [vp, i32, i32, vp, i32, vp]
     lib.fat5_sizeof_adamw_tensor.restype = ctypes.c_size_t
+    lib.fat5_sizeof_adafactor_tensor.restype = ctypes.c_size_t
+    lib.fat5_adafactor_workspace_bytes.restype = ctypes.c_size_t
+    lib.fat5_adafactor_workspace_bytes.argtypes = [vp, i32]
+    lib.fat5_adafactor_step.restype = ctypes.c_int
+    lib.fat5_adafactor_step.argtypes = [vp, vp, i32, vp, ctypes.c_size_t, f64, f64, f64, f64, f64, i32, i32, i32, vp, vp]
     lib.fat5_rope_apply.restype = ctypes.c_int
     lib.fat5_rope_apply.argtypes = [ctypes.POINTER(RopeParams), ctypes.c_void_p]
     lib.fat5_sizeof_rope_params.restype = ctypes.c_size_t

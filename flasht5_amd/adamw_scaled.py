@@ -13,6 +13,7 @@ from torch import nn
 from torch.optim import Optimizer
 
 from . import _lib
+from ._captured_step import CapturedStepHost
 
 __all__ = ["AdamWScale"]
 
@@ -25,7 +26,7 @@ class _Desc(ctypes.Structure):
                 ("numel", ctypes.c_int64), ("chunk_begin", ctypes.c_int32), ("step_prefactor", ctypes.c_float)]
 
 
-class AdamWScale(Optimizer):
+class AdamWScale(Optimizer, CapturedStepHost):
     """Same arguments as the reference class (:40-66).  `foreach` is accepted and ignored (the fused step replaces both of the
     reference's paths); `use_state_dtype` = torch.float16 / torch.bfloat16 keeps exp_avg / exp_avg_sq in that dtype beside
     parameters of another one (reference :101-103; any other value = the parameter dtype, like the reference).
@@ -76,14 +77,7 @@ class AdamWScale(Optimizer):
         lib = _lib.load()
         capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
         if capturing:  # (a step recorded into a HIP graph: see graph_advance)
-            # ONE captured step per optimizer: the graph bakes raw pointers to the arena's descriptor table and step scalars into its
-            # launches, and graph_advance() writes the scalars of exactly one capture -- a second capture would hand the same arena
-            # bytes out again (the first graph would then replay over another table) and leave the first graph's scalars stale
-            if getattr(self, "_graph_jobs", None):
-                raise RuntimeError("AdamWScale: this optimizer already holds a captured step; destroy that graph and call "
-                                   "release_captured_step() before capturing another one")
-            self._graph_jobs, self._graph_keep = [], []
-            self._capture_generation = getattr(self, "_capture_generation", 0) + 1  # (ownership token of THIS capture: capture_token())
+            self._begin_capture()
         jobs = []  # one per (group, device, dtype, kahan) bucket: descriptor table on the device, launched below
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
@@ -214,76 +208,13 @@ class AdamWScale(Optimizer):
                 state["exp_avg_sq"] = torch.zeros_like(p, dtype=sd, memory_format=torch.preserve_format)
                 kah = group["kahan_sum"] and p.dtype in (torch.float16, torch.bfloat16)
                 state["kahan_comp"] = torch.zeros_like(p, memory_format=torch.preserve_format) if kah else None
-        # descriptor tables + step scalars of a captured step (see step()): one arena per device, [tensor, bytes handed out].  An arena
-        # a captured graph may be reading is never replaced or resized: it is allocated once and only while no step is captured.
-        if not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
-            count = {}
-            for group in self.param_groups:
-                for p in group["params"]:
-                    if p.is_cuda:
-                        count[p.device] = count.get(p.device, 0) + 1
-            need = {dev: (2 * n + 8 * len(self.param_groups) + 8) * 128 for dev, n in count.items()}
-            have = getattr(self, "_graph_arena", None)
-            if have is None or any(dev not in have or have[dev][0].numel() < nb for dev, nb in need.items()):
-                if getattr(self, "_graph_jobs", None):
-                    raise RuntimeError("AdamWScale.init_state: parameters were added while a captured step exists; destroy that graph "
-                                       "and call release_captured_step() first")
-                self._graph_arena = {dev: [torch.empty(nb, dtype=torch.uint8, device=dev), 0] for dev, nb in need.items()}
-
-    def capture_token(self):
-        """Ownership token of the captured step this optimizer currently holds (0: none).  Whoever captured keeps the token and hands it to
-        `release_captured_step(token)`: a holder whose capture was already released -- and replaced by a newer one -- then releases nothing
-        (an old GraphedTrainStep collected late must not clear the arena a live graph reads)."""
-        return getattr(self, "_capture_generation", 0) if getattr(self, "_graph_jobs", None) else 0
-
-    def release_captured_step(self, token=None):
-        """Forget the captured step (the caller has destroyed every graph that holds it): its arena bytes may be handed out again.
-        token (from `capture_token()` right after the capture): release only if the optimizer still holds THAT capture; None: unconditionally."""
-        if token is not None and token != self.capture_token():
-            return False
-        self._graph_jobs, self._graph_keep = [], []
-        for a in getattr(self, "_graph_arena", {}).values():
-            a[1] = 0
-        return True
-
-    def _upload(self, device, table):
-        """descriptor table -> device, ASYNCHRONOUSLY: through one of eight rotating pinned staging buffers (a copy from pageable memory
-        makes the host wait for the stream, i.e. for the whole backward pass in front of it -- the host could never run ahead of the
-        device).  A staging buffer is rewritten only after the copy issued from it eight uploads ago has completed."""
-        n = ctypes.sizeof(table)
-        ring = self.__dict__.setdefault("_staging", {}).setdefault(device, {"i": 0, "slot": 0, "pin": None, "ev": [None] * 8})
-        if ring["pin"] is None or ring["slot"] < n:  # (ONE pinned allocation for the whole ring: hipHostMalloc costs milliseconds)
-            for ev in ring["ev"]:
-                if ev is not None:
-                    ev.synchronize()
-            ring["slot"] = max(2 * n, 1 << 16)
-            ring["pin"] = torch.empty(8 * ring["slot"], dtype=torch.uint8).pin_memory()
-            ring["ev"] = [None] * 8
-        i = ring["i"]
-        ring["i"] = (i + 1) % 8
-        if ring["ev"][i] is not None:
-            ring["ev"][i].synchronize()
-        buf = ring["pin"][i * ring["slot"]:(i + 1) * ring["slot"]]
-        ctypes.memmove(buf.data_ptr(), ctypes.addressof(table), n)
-        raw = torch.empty(n, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            raw.copy_(buf[:n], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        ring["ev"][i] = ev
-        return raw
-
-    def _arena_take(self, device, nbytes):
-        """`nbytes` of the pre-capture arena of `device` (64-byte aligned pieces, handed out in order)"""
-        a = getattr(self, "_graph_arena", {}).get(device)
-        if a is None:
-            raise RuntimeError("AdamWScale: call init_state() before capturing a step (it allocates the buffers a captured step "
-                               "keeps outside the graph's memory pool)")
-        off = a[1]
-        a[1] = off + (nbytes + 63) // 64 * 64
-        if a[1] > a[0].numel():
-            raise RuntimeError("AdamWScale: capture arena too small (parameters added after init_state()?)")
-        return a[0][off:off + nbytes]
+        # descriptor tables + step scalars of a captured step (see step()): one arena per device
+        count = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.is_cuda:
+                    count[p.device] = count.get(p.device, 0) + 1
+        self._reserve_arena({dev: (2 * n + 8 * len(self.param_groups) + 8) * 128 for dev, n in count.items()})
 
     @torch.no_grad()
     def graph_advance(self):

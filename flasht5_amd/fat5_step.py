@@ -648,9 +648,11 @@ class GraphedTrainStep:
     (`close()` -- also run when this object is destroyed -- releases it: `AdamWScale.release_captured_step()`)."""
 
     def __init__(self, model, optimizer, group=None, warmup=2, split=None):
+        from .adafactor import Adafactor
         from .adamw_scaled import AdamWScale
-        if not isinstance(optimizer, AdamWScale):
-            raise TypeError("GraphedTrainStep needs flasht5_amd.AdamWScale (its captured step reads lr / bias correction from device memory)")
+        if not isinstance(optimizer, (AdamWScale, Adafactor)):
+            raise TypeError("GraphedTrainStep needs flasht5_amd.AdamWScale or flasht5_amd.Adafactor (their captured steps read the "
+                            "step-dependent scalars from device memory)")
         self.model, self.optimizer, self.group = model, optimizer, group
         self.warmup = int(warmup)
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
@@ -690,7 +692,7 @@ class GraphedTrainStep:
         self.graphs = graphs
         self._token = self.optimizer.capture_token()  # (close() releases THIS capture only: ADVICE r5)
         # what the capture baked in (see the class docstring)
-        self._baked = [(tuple(g["betas"]), float(g["eps"])) for g in self.optimizer.param_groups]
+        self._baked = [self._fixed(g) for g in self.optimizer.param_groups]
         self._grads = [(p, p.grad) for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
 
     def close(self):
@@ -705,11 +707,19 @@ class GraphedTrainStep:
         except Exception:
             pass
 
+    @staticmethod
+    def _fixed(g):
+        """the options of a parameter group that are launch arguments of its captured step"""
+        if "betas" in g:  # AdamWScale
+            return tuple(g["betas"]), float(g["eps"])
+        return tuple(g["eps"]), float(g["clip_threshold"]), g["beta1"], bool(g["scale_parameter"])  # Adafactor
+
     def _check_baked(self):
-        for g, (betas, eps) in zip(self.optimizer.param_groups, self._baked):
-            if tuple(g["betas"]) != betas or float(g["eps"]) != eps:
-                raise RuntimeError("GraphedTrainStep: betas / eps are launch arguments of the captured optimizer step and cannot change "
-                                   "after capture (lr and weight_decay can: they travel through device memory)")
+        for g, fixed in zip(self.optimizer.param_groups, self._baked):
+            if self._fixed(g) != fixed:
+                raise RuntimeError("GraphedTrainStep: betas / eps (Adafactor: eps, clip_threshold, beta1, scale_parameter) are launch "
+                                   "arguments of the captured optimizer step and cannot change after capture (lr and weight_decay can: "
+                                   "they travel through device memory)")
         for p, gr in self._grads:
             if p.grad is not gr:
                 raise RuntimeError("GraphedTrainStep: p.grad was reset or replaced between replays; the captured graph owns the gradient "

@@ -1324,6 +1324,46 @@ int fat5_adamw_scale_step_dev(const fat5_adamw_tensor* table, int32_t n_tensors,
                               void* hip_stream);
 size_t fat5_sizeof_adamw_tensor(void);
 
+/*
+ * Adafactor step over a bucket of tensors, with the semantics of transformers.optimization.Adafactor (csrc/adafactor_kernels.h).
+ * Per tensor, all in fp32 whatever the parameter / gradient dtypes:
+ *   RMS = |p| / sqrt(numel);  lr = (scale_parameter ? max(eps1, RMS) : 1) * rho;  t = g^2 + eps0
+ *   2-D (rows x cols): row = beta2t row + (1-beta2t) mean_j t;  col = beta2t col + (1-beta2t) mean_i t
+ *                      u = g * rsqrt(row_i / mean(row)) * rsqrt(col_j)
+ *   1-D (rows == 0):   v = beta2t v + (1-beta2t) t;  u = g * rsqrt(v)
+ *   u = u / max(1, RMS(u) / clip_threshold) * lr;   with a first moment: m = beta1 m + (1-beta1) u, u = m
+ *   p = p + p * (-weight_decay * lr) - u            (one rounding to the parameter dtype)
+ * Four launches for the whole bucket, no atomics; every sum's order depends on the tensor's shape alone.
+ * The caller fills p, g, the state pointers, rows, cols, beta2t (1 - step^decay_rate) and rho (the relative step or the external
+ * lr) of n_tensors descriptors plus one terminator; the workspace call below fills ws_begin, tile_begin and fblock_begin of all
+ * n_tensors + 1 entries and returns the bytes of device scratch the step needs (0: illegal descriptor, see the error text).
+ * The step takes that table twice: the host copy (checked before any device work) and its copy in device memory.
+ */
+typedef struct fat5_adafactor_tensor {
+  void* p;           /* parameters, updated in place (contiguous) */
+  const void* g;     /* gradients (contiguous, their own dtype) */
+  float* vr;         /* 2-D: exp_avg_sq_row (rows);  1-D: exp_avg_sq (cols) */
+  float* vc;         /* 2-D: exp_avg_sq_col (cols);  1-D: NULL */
+  float* m;          /* exp_avg (fp32, the parameter's shape) with a first moment, else NULL */
+  float* rms;        /* one float: RMS(p) as HF's state["RMS"] */
+  int64_t rows;      /* 0: a 1-D parameter of `cols` elements */
+  int64_t cols;
+  int64_t ws_begin;     /* floats */
+  int32_t tile_begin;   /* 64 x 512 tiles (1-D: 8192-element chunks) of the tensors in front */
+  int32_t fblock_begin; /* workgroups of the factor kernel of the tensors in front */
+  float beta2t;
+  float rho;
+} fat5_adafactor_tensor;
+size_t fat5_sizeof_adafactor_tensor(void);
+size_t fat5_adafactor_workspace_bytes(fat5_adafactor_tensor* host_table, int32_t n_tensors);
+/* dev_scalars: NULL, or three floats in DEVICE memory {beta2t, rho, weight_decay} that replace the descriptors' beta2t / rho
+ * and the weight_decay argument -- a launch captured in a HIP graph then follows the schedule.  beta1 < 0: no first moment
+ * (every m NULL); otherwise every m non-NULL. */
+int fat5_adafactor_step(const fat5_adafactor_tensor* host_table, const fat5_adafactor_tensor* dev_table, int32_t n_tensors,
+                        float* workspace, size_t workspace_bytes, double eps0, double eps1, double clip_threshold, double beta1,
+                        double weight_decay, int scale_parameter, int dtype, int grad_dtype, const float* dev_scalars,
+                        void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
