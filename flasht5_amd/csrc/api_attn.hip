@@ -186,6 +186,18 @@ int fat5_attn_bwd_stages(const fat5_attn_params* p, int stages, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if ((p->cu_seqlens_q == nullptr) != (p->cu_seqlens_k == nullptr)) return fail(FAT5_EINVAL, "cu_seqlens_q/k must both be set");
   if (p->cu_seqlens_q && p->bias_mode == FAT5_BIAS_DENSE) return fail(FAT5_EINVAL, "varlen: dense bias unsupported (none or rpe1d)");
+  const DispatchKey key = key_of(p);
+  BwdLayout L;
+  bwd_layout(key, L);
+  // (ahead of the pointer checks: host-only like the layout, so a call without tensors answers whether a radius is accepted -- tests/test_radius_seams_cpu.py)
+  if (p->bias_mode == FAT5_BIAS_RPE1D) {
+    // the dK/dV body keeps the table and one private diagonal accumulator per wave in LDS
+    const size_t lds = L.kv64 ? (L.kv64_half ? smem_bwd_kv64h_d64(p->rpe_radius, p->bias_mode) : smem_bwd_kv64_d64(p->rpe_radius, p->bias_mode))
+                     : effD(p) == 32 ? smem_bwd_kv_d32(L.nw_kv, p->rpe_radius, p->bias_mode)
+                                  : (p->D == 64 ? smem_bwd_kv_d64(L.nw_kv, p->rpe_radius, p->bias_mode) : smem_bwd_kv_d128(L.nw_kv, p->rpe_radius, p->bias_mode));
+    if (lds > 160 * 1024)
+      return fail(FAT5_EINVAL, "bwd: rpe_radius %d needs %zu bytes of LDS (160 KiB per workgroup; radius <= 1024 fits every head_dim)", p->rpe_radius, lds);
+  }
   if (!p->q || !p->k || !p->v || !p->o || !p->lse || !p->dout || !p->dq || !p->dk || !p->dv)
     return fail(FAT5_EINVAL, "bwd: null tensor pointer");
   if (!strides_ok(p->q, p->q_stride) || !strides_ok(p->k, p->k_stride) || !strides_ok(p->v, p->v_stride) ||
@@ -204,17 +216,6 @@ int fat5_attn_bwd_stages(const fat5_attn_params* p, int stages, void* stream_) {
       !slice_fits(p->M, p->o_stride[2], p->D) || !slice_fits(p->M, p->do_stride[2], p->D) || !slice_fits(p->M, p->dq_stride[2], p->D) ||
       !slice_fits(p->N, p->dk_stride[2], p->D) || !slice_fits(p->N, p->dv_stride[2], p->D))
     return fail(FAT5_EINVAL, "bwd: one (batch, head) slice must span less than 2 GiB");
-  const DispatchKey key = key_of(p);
-  BwdLayout L;
-  bwd_layout(key, L);
-  if (p->bias_mode == FAT5_BIAS_RPE1D) {
-    // the dK/dV body keeps the table and one private diagonal accumulator per wave in LDS
-    const size_t lds = L.kv64 ? (L.kv64_half ? smem_bwd_kv64h_d64(p->rpe_radius, p->bias_mode) : smem_bwd_kv64_d64(p->rpe_radius, p->bias_mode))
-                     : effD(p) == 32 ? smem_bwd_kv_d32(L.nw_kv, p->rpe_radius, p->bias_mode)
-                                  : (p->D == 64 ? smem_bwd_kv_d64(L.nw_kv, p->rpe_radius, p->bias_mode) : smem_bwd_kv_d128(L.nw_kv, p->rpe_radius, p->bias_mode));
-    if (lds > 160 * 1024)
-      return fail(FAT5_EINVAL, "bwd: rpe_radius %d needs %zu bytes of LDS (160 KiB per workgroup; radius <= 1024 fits every head_dim)", p->rpe_radius, lds);
-  }
   if (L.total > 0 && (!p->workspace || p->workspace_bytes < L.total))
     return fail(FAT5_EWORKSPACE, "bwd: workspace of %zu bytes required, got %zu", L.total, p->workspace_bytes);
   if ((reinterpret_cast<uintptr_t>(p->workspace) & 255) != 0) return fail(FAT5_EINVAL, "bwd: workspace must be 256-byte aligned");

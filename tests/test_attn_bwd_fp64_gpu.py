@@ -330,11 +330,17 @@ def seams_dense64(case):
     return list(range(0, case["M"], 32)), list(range(0, case["N"], 32))
 
 
+def num_buckets(case):
+    return case.get("num_buckets", NUM_BUCKETS)
+
+
 def bucket_map(case):
+    """the case's (2R + 1) bucket ids: the T5 map at `num_buckets` (32) buckets and `max_distance` (128); `bucket_edit` (tests/test_attn_radius_fp64_gpu.py) rewrites entries of it"""
     if case["bias"][:2] != "t5":
         return None
     R = case["R"]
-    return torch.from_numpy(relative_position_bucket(torch.arange(-R, R + 1).numpy(), case["bias"] == "t5b", NUM_BUCKETS, 128)).to(torch.int32)
+    ids = torch.from_numpy(relative_position_bucket(torch.arange(-R, R + 1).numpy(), case["bias"] == "t5b", num_buckets(case), case.get("max_distance", 128))).to(torch.int32)
+    return case["bucket_edit"](ids) if "bucket_edit" in case else ids
 
 
 def inputs(case):
@@ -366,7 +372,7 @@ def inputs(case):
     if kind == "rpe":      # an i.i.d. generator: every entry distinct, so a wrong index shows
         rpe = torch.randn(H, 2 * case["R"] + 1, generator=g)
     elif bucket is not None:   # a T5 table through its bucket map (bidirectional / unidirectional), clamped at R
-        rpe = torch.randn(NUM_BUCKETS, H, generator=g)[bucket.long()].T.contiguous()
+        rpe = torch.randn(num_buckets(case), H, generator=g)[bucket.long().clamp(0, num_buckets(case) - 1)].T.contiguous()   # (the host builds the generator here; ids outside the table are clamped, which mirrors the clamp of rpe1d_gather_kernel)
     elif kind != "none":
         sb, sh = DENSE_SHAPE[kind[:2]]
         bias = torch.randn(1 if sb else B, 1 if sh else H, M, N, generator=g).to(dtype)
@@ -395,7 +401,7 @@ def inputs(case):
 
 def reference(case, t, mutant=None):
     return G.attn_bwd_ref(t["q"], t["k"], t["v"], t["o"], t["lse"], t["do"], case["scale"], case["causal"], t["bias"], t["rpe"], case["R"],
-                          t["bucket"], NUM_BUCKETS if t["bucket"] is not None else 0, mutant=mutant)
+                          t["bucket"], num_buckets(case) if t["bucket"] is not None else 0, mutant=mutant)
 
 
 def compared(case, ref):
@@ -412,8 +418,8 @@ def variant_bits(case):
     return bits
 
 
-def describe(case):
-    """the backward bodies the library would run this case with (fat5_attn_describe: host-only, no pointer but the host bucket map is followed)"""
+def describe_params(case):
+    """(AttnParams of the case with placeholder pointers, the host bucket map they point to -- keep it alive); a case with grad=False asks for no bias gradient"""
     from flasht5_amd import _lib
     B, H, M, N = case["B"], case["H"], case["M"], case["N"]
     p = _lib.AttnParams()
@@ -433,9 +439,18 @@ def describe(case):
         bucket = bucket_map(case)
         if bucket is not None:
             host = (ctypes.c_int32 * len(bucket))(*[int(x) for x in bucket])
-            p.rpe_bucket, p.drpe_table, p.rpe_num_buckets, p.rpe_bucket_host = 16, 16, NUM_BUCKETS, ctypes.addressof(host)
+            p.rpe_bucket, p.drpe_table, p.rpe_num_buckets, p.rpe_bucket_host = 16, 16, num_buckets(case), ctypes.addressof(host)
         else:
             p.drpe1d = 16
+        if not case.get("grad", True):
+            p.drpe1d = p.drpe_table = 0
+    return p, host
+
+
+def describe(case):
+    """the backward bodies the library would run this case with (fat5_attn_describe: host-only, no pointer but the host bucket map is followed)"""
+    from flasht5_amd import _lib
+    p, host = describe_params(case)
     buf = ctypes.create_string_buffer(256)
     _lib.check(_lib.load().fat5_attn_describe(ctypes.byref(p), buf, 256), "fat5_attn_describe")
     return dict(kv.split("=") for kv in buf.value.decode().split())
