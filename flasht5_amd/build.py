@@ -26,6 +26,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-mllvm", "-amdg
 UNITS = [(f"api_{n}.hip", f"api_{n}.o", []) for n in ("core", "attn", "rowwise", "position", "decode", "generate", "pack", "dropout", "ul2", "w8", "pool", "kd")]
 # the matrix-pipe FP8-weight linear: scalar fp32 ops only in its VALU code (no v_pk_{add,mul,fma}_f32)
 UNITS.append(("api_w8_mma.hip", "api_w8_mma.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
+# the MXFP4-weight linear: its staging expression and statistics are that unit's, kept under the same code generation
+UNITS.append(("api_w4.hip", "api_w4.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
 # the Adafactor step: its sums and updates are scalar fp32 ops too
 UNITS.append(("api_adafactor.hip", "api_adafactor.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
 for d in (32, 64, 128):

@@ -47,9 +47,9 @@ inline W8LinearArgs w8_linear_args(const fat5_w8_linear_params* p) {
   return a;
 }
 
-// launch(dtype, NORM, RES) of the instance the parameters ask for
-template <typename L>
-void w8_with_instance(const fat5_w8_linear_params* p, L&& launch) {
+// launch(dtype, NORM, RES) of the instance the parameters ask for (fat5_w8_linear_params, or fat5_w4_linear_params: api_w4.hip)
+template <typename P, typename L>
+void w8_with_instance(const P* p, L&& launch) {
   auto with_dt = [&](auto dt) {
     if (p->norm_weight) p->residual ? launch(dt, IC<1>{}, IC<1>{}) : launch(dt, IC<1>{}, IC<0>{});
     else p->residual ? launch(dt, IC<0>{}, IC<1>{}) : launch(dt, IC<0>{}, IC<0>{});

@@ -536,6 +536,12 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         from .w8 import quantize_decoder_weights
         return quantize_decoder_weights(self)
 
+    def quantize_decoder_weights_mxfp4(self):
+        """the MXFP4 (e2m1 nibbles + one e8m0 scale byte per 32 weights) copies of the same weights, for weight_dtype="mxfp4"
+        (w4.quantize_decoder_weights_mxfp4)"""
+        from .w4 import quantize_decoder_weights_mxfp4
+        return quantize_decoder_weights_mxfp4(self)
+
     def decode_chunk(self, state, token_ids, logits="all", chunk_seqlens=None):
         """M tokens per row (B, M) through the cached decoder in one step -> logits (B, M, vocab) ("all"), (B, vocab) ("last") or
         None ("none"); the caches and cache_seqlens advance by M, or per row by chunk_seqlens (generation.decode_chunk)"""

@@ -57,6 +57,8 @@ scales and quantises the rows it appends: (D + 4) / (2 D) of the cache bytes, in
 FP8 weights (`weight_dtype="fp8"`): the decoder weights a step reads are quantised once per model (flasht5_amd/w8.py)
 and the state's steps run `_decoder_blocks_w8` beside `_decoder_blocks`: each projection one `w8_linear` launch with its RMSNorm
 in front and its residual add behind, 9 launches per block where the default path makes about 19.  None: nothing here runs.
+MXFP4 weights (`weight_dtype="mxfp4"`): the same pass over e2m1 nibbles and block scales (flasht5_amd/w4.py), each
+projection one `w4_linear` launch.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -85,7 +87,8 @@ class DecodeState:
     self_v_scale: Optional[List[torch.Tensor]] = None
     cross_k_scale: Optional[List[torch.Tensor]] = None
     cross_v_scale: Optional[List[torch.Tensor]] = None
-    w8: Optional[object] = None   # FP8 weights (weight_dtype="fp8"): the model's w8.DecoderW8; the step then runs `_decoder_blocks_w8`
+    w8: Optional[object] = None   # quantised weights (weight_dtype="fp8" / "mxfp4"): the model's w8.DecoderW8; the step then runs `_decoder_blocks_w8`
+    weight_format: Optional[str] = None   # "fp8" (pairs of bytes and row scales, `w8_linear`) or "mxfp4" (nibbles and block scales, `w4_linear`)
     w8_kernel: str = "rows"       # weight_kernel: "matrix" sends the step's w8_linear calls of more than one row tile to the MFMA kernel
 
     def scales(self, i):
@@ -257,7 +260,9 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     the cross-attention K / V are quantised once (`quantize_kv`); anything but these and None raises before the encoder runs.
     weight_dtype="fp8" (alias "fp8_e4m3"): the state's steps read the model's FP8 decoder weights
     (`quantize_decoder_weights`, built once per model) through `w8_linear`; checked, like the decoder's dtype and shapes, before
-    the encoder runs.  weight_kernel (None, "rows" or "matrix"; with weight_dtype="fp8" only): see `generate`."""
+    the encoder runs.  weight_kernel (None, "rows" or "matrix"; with weight_dtype="fp8" only): see `generate`.
+    weight_dtype="mxfp4" (DESIGN 4.27): the same steps over the model's MXFP4 decoder weights (`quantize_decoder_weights_mxfp4`)
+    through `w4_linear`; weight_kernel must be None."""
     fp8 = check_kv_cache_dtype(kv_cache_dtype, "init_decode_state")
     w8 = _check_weight_dtype(model, weight_dtype, "init_decode_state")
     w8_kernel = _check_weight_kernel(weight_kernel, weight_dtype, "init_decode_state")
@@ -302,10 +307,14 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     state = DecodeState(enc, self_k, self_v, cross_k, cross_v, torch.zeros((Bk,), dtype=torch.int32, device=dev), pb, cap)
     if fp8:
         state.self_k_scale, state.self_v_scale, state.cross_k_scale, state.cross_v_scale = sks, svs, cks, cvs
-    if w8:
+    if w8 == "fp8":
         from .w8 import quantize_decoder_weights
         state.w8 = quantize_decoder_weights(model)
         state.w8_kernel = w8_kernel
+    elif w8 == "mxfp4":
+        from .w4 import quantize_decoder_weights_mxfp4
+        state.w8 = quantize_decoder_weights_mxfp4(model)
+    state.weight_format = w8
     if num_beams > 1:
         state.cross_batch_idx = torch.arange(Bk, dtype=torch.int32, device=dev) // int(num_beams)
         state.row_batch = torch.zeros((Bk, cap), dtype=torch.int32, device=dev)
@@ -333,13 +342,16 @@ def _decoder_blocks(model, state, h, chunk_seqlens=None):
 
 
 def _check_weight_dtype(model, weight_dtype, what="generate"):
-    """None, or "fp8" / "fp8_e4m3" -> whether the step reads FP8 decoder weights; with them the decoder's dtype and shapes are
-    checked too (host only: nothing has run yet)"""
+    """None, "fp8" / "fp8_e4m3" or "mxfp4" -> the format of the decoder weights the step reads (None: the 16-bit parameters); with
+    a format the decoder's dtype and shapes are checked too (host only: nothing has run yet)"""
     from .w8 import check_decoder_weights, check_weight_dtype
-    if not check_weight_dtype(weight_dtype, what):
-        return False
-    check_decoder_weights(model, what)
-    return True
+    fmt = check_weight_dtype(weight_dtype, what)
+    if fmt == "fp8":
+        check_decoder_weights(model, what)
+    elif fmt == "mxfp4":
+        from .w4 import check_decoder_weights_mxfp4
+        check_decoder_weights_mxfp4(model, what)
+    return fmt
 
 
 def _check_weight_kernel(weight_kernel, weight_dtype, what="generate"):
@@ -347,36 +359,46 @@ def _check_weight_kernel(weight_kernel, weight_dtype, what="generate"):
     return check_weight_kernel(weight_kernel, weight_dtype, what)
 
 
+def _weight_linear(state, rows):
+    """the linear layer of this state's weight format for a call of `rows` rows -> lin(x, pair, **norm / residual): `w8_linear` on
+    the kernel the row count selects (`w8.kernel_for_rows`: a shape, so static under a graph), or `w4_linear`, whose one kernel
+    serves every row count.  (The entry points are looked up per call: they can be wrapped.)"""
+    if state.weight_format == "mxfp4":
+        from . import w4 as w4m
+        return lambda x, pair, **kw: w4m.w4_linear(x, *pair, **kw)
+    from . import w8 as w8m
+    kern = w8m.kernel_for_rows(state.w8_kernel, rows)
+    return lambda x, pair, **kw: w8m.w8_linear(x, *pair, kernel=kern, **kw)
+
+
 def _decoder_blocks_w8(model, state, h, chunk_seqlens=None):
-    """`_decoder_blocks` over the FP8 weights of `state.w8`: per block norm + qkv, self-attention, o + residual,
-    norm + q, cross-attention, o + residual, norm + wi, the gated activation, wo + residual -- every projection ONE `w8_linear`
-    launch with its RMSNorm in front and its residual add behind, on the kernel the call's B * M rows select
-    (`w8.kernel_for_rows`: a shape, so static under a graph)"""
-    from . import w8 as w8m   # (looked up per call: the entry point can be wrapped)
+    """`_decoder_blocks` over the quantised weights of `state.w8` (FP8: DESIGN 4.23; MXFP4: 4.27): per block norm + qkv,
+    self-attention, o + residual, norm + q, cross-attention, o + residual, norm + wi, the gated activation, wo + residual -- every
+    projection ONE launch of the format's linear layer (`_weight_linear`) with its RMSNorm in front and its residual add behind"""
     from .gated_act import gated_act_packed
     pos = state.position if model.decoder.block[0].self_attention_layer.self_attention.rotary else None
     B, M = h.shape[:2]
-    kern = w8m.kernel_for_rows(state.w8_kernel, B * M)
+    lin = _weight_linear(state, B * M)
     for i, (blk, lw) in enumerate(zip(model.decoder.block, state.w8.layers)):
         sa, ca, ff = blk.self_attention_layer, blk.cross_attention_layer, blk.ff_layer
         ssc, csc = state.scales(i)
         att = sa.self_attention
         H, D, inner = att.n_heads, att.key_value_proj_dim, att.inner_dim
-        qkv = w8m.w8_linear(h, *lw.qkv, norm_weight=sa.layer_norm.weight, eps=sa.layer_norm.variance_epsilon, kernel=kern)
+        qkv = lin(h, lw.qkv, norm_weight=sa.layer_norm.weight, eps=sa.layer_norm.variance_epsilon)
         q, k, v = (qkv[..., j * inner:(j + 1) * inner].view(B, M, H, D) for j in range(3))
         o = att.attend_decode(q, k, v, state.self_k[i], state.self_v[i], state.cache_seqlens, position_bias=state.position_bias,
                               position=pos, cache_row_batch=state.row_batch, chunk_seqlens=chunk_seqlens, **ssc)
-        h = w8m.w8_linear(o, *lw.self_o, residual=h, kernel=kern)
+        h = lin(o, lw.self_o, residual=h)
         att = ca.cross_attention
-        q = w8m.w8_linear(h, *lw.cross_q, norm_weight=ca.layer_norm.weight, eps=ca.layer_norm.variance_epsilon, kernel=kern)
+        q = lin(h, lw.cross_q, norm_weight=ca.layer_norm.weight, eps=ca.layer_norm.variance_epsilon)
         q = q.view(B, M, H, D)
         o = att.attend_decode(q, None, None, state.cross_k[i], state.cross_v[i], None, position=pos,
                               cache_batch_idx=state.cross_batch_idx, cross_seqlens=state.cross_seqlens, chunk_seqlens=chunk_seqlens,
                               **csc)
-        h = w8m.w8_linear(o, *lw.cross_o, residual=h, kernel=kern)
-        g = w8m.w8_linear(h, *lw.wi, norm_weight=ff.layer_norm.weight, eps=ff.layer_norm.variance_epsilon, kernel=kern)
+        h = lin(o, lw.cross_o, residual=h)
+        g = lin(h, lw.wi, norm_weight=ff.layer_norm.weight, eps=ff.layer_norm.variance_epsilon)
         t = gated_act_packed(g, ff.act.act_name) if ff.act.glu else ff.act.act(g)
-        h = w8m.w8_linear(t, *lw.wo, residual=h, kernel=kern)
+        h = lin(t, lw.wo, residual=h)
     return h
 
 
@@ -389,10 +411,8 @@ def _head(model, state, h):
     """final norm + lm_head of the rows of h"""
     if state.w8 is None:
         return model.lm_head(model.decoder.final_layer_norm(h))
-    from . import w8 as w8m
     ln = model.decoder.final_layer_norm
-    return w8m.w8_linear(h, *state.w8.lm_head, norm_weight=ln.weight, eps=ln.variance_epsilon,
-                         kernel=w8m.kernel_for_rows(state.w8_kernel, h.numel() // h.shape[-1]))
+    return _weight_linear(state, h.numel() // h.shape[-1])(h, state.w8.lm_head, norm_weight=ln.weight, eps=ln.variance_epsilon)
 
 
 @torch.no_grad()
@@ -700,7 +720,10 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     nearly flat in the row count up to 64; calls of at most 8 rows keep the row kernel and its bits.  The choice is made from the
     call's shape, so nothing is added to a step: no launch, no host read; graph=True and every mode work as above, the assistant
     gets the same setting.  The tokens can differ from "rows" where two logits are within the fp32 summation error.  Any other
-    value, or a weight_kernel without weight_dtype="fp8", raises ValueError before an encoder runs."""
+    value, or a weight_kernel without weight_dtype="fp8", raises ValueError before an encoder runs.
+    `weight_dtype="mxfp4"`: the same 9 launches per block and the same modes over MXFP4 copies of the decoder weights
+    (`quantize_decoder_weights_mxfp4`: e2m1 nibbles and one e8m0 scale byte per 32 weights, N * K * 17 / 32 bytes per stack, built
+    once per model; an assistant's the same way), each launch `w4_linear`'s one MFMA kernel; `weight_kernel` must be None."""
     check_kv_cache_dtype(kv_cache_dtype)
     _check_weight_dtype(model, weight_dtype)
     _check_weight_kernel(weight_kernel, weight_dtype)

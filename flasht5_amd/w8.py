@@ -46,21 +46,24 @@ def check_shape(N, K, what):
 
 
 def check_weight_dtype(weight_dtype, what="generate"):
-    """None, or "fp8" / "fp8_e4m3" -> whether the decoder weights are FP8"""
+    """None, "fp8" / "fp8_e4m3" or "mxfp4" -> the format of the decoder weights: None (16-bit), "fp8" or "mxfp4" (w4.py)"""
     if weight_dtype is None:
-        return False
+        return None
     if isinstance(weight_dtype, str) and weight_dtype in ("fp8", "fp8_e4m3"):
-        return True
-    raise ValueError(f"{what}: weight_dtype {weight_dtype!r} (None, 'fp8' or its alias 'fp8_e4m3')")
+        return "fp8"
+    if isinstance(weight_dtype, str) and weight_dtype == "mxfp4":
+        return "mxfp4"
+    raise ValueError(f"{what}: weight_dtype {weight_dtype!r} (None, 'fp8', its alias 'fp8_e4m3', or 'mxfp4')")
 
 
 def check_weight_kernel(weight_kernel, weight_dtype, what="generate"):
-    """None / "rows" / "matrix" -> the kernel name a state carries ("rows" for None); needs weight_dtype="fp8"; host only"""
+    """None / "rows" / "matrix" -> the kernel name a state carries ("rows" for None); needs weight_dtype="fp8" (MXFP4 weights have
+    one kernel); host only"""
     if weight_kernel is None:
         return "rows"
     if not (isinstance(weight_kernel, str) and weight_kernel in KERNELS):
         raise ValueError(f"{what}: weight_kernel {weight_kernel!r} (None, 'rows' or 'matrix')")
-    if not check_weight_dtype(weight_dtype, what):
+    if check_weight_dtype(weight_dtype, what) != "fp8":
         raise ValueError(f"{what}: weight_kernel {weight_kernel!r} needs weight_dtype='fp8'")
     return weight_kernel
 
@@ -276,23 +279,30 @@ def _sources(model):
     return blocks, model.lm_head.weight
 
 
-def check_decoder_weights(model, what="generate"):
-    """host-only: a decoder the FP8-weight step can run -- 16-bit weights of one dtype and shapes inside the contract"""
+def check_decoder_weights(model, what="generate", fmt="fp8", shape_check=check_shape):
+    """host-only: a decoder the quantised-weight step can run -- 16-bit weights of one dtype and shapes inside the contract of the
+    format (`shape_check`: this module's `check_shape`, or w4's)"""
     blocks, head = _sources(model)
     every = [w for b in blocks for ws in b for w in ws] + [head]
     norms = [ln.weight for blk in model.decoder.block for ln in (blk.self_attention_layer.layer_norm, blk.cross_attention_layer.layer_norm,
                                                                    blk.ff_layer.layer_norm)] + [model.decoder.final_layer_norm.weight]
     dt = head.dtype
     if dt not in (torch.float16, torch.bfloat16) or any(w.dtype != dt for w in every + norms + [model.shared.weight]):
-        raise ValueError(f"{what}: weight_dtype='fp8' needs a decoder whose weights are fp16 or bf16 (one dtype; the activations keep "
+        raise ValueError(f"{what}: weight_dtype='{fmt}' needs a decoder whose weights are fp16 or bf16 (one dtype; the activations keep "
                          f"it), got {sorted({str(w.dtype) for w in every + norms})}: convert the model (model.bfloat16()), an "
                          "fp32 model under autocast is not supported")
     for b in blocks:
         for ws in b:
-            check_shape(sum(w.shape[0] for w in ws), ws[0].shape[1], f"{what}: weight_dtype='fp8'")
+            shape_check(sum(w.shape[0] for w in ws), ws[0].shape[1], f"{what}: weight_dtype='{fmt}'")
             if any(w.shape[0] % 8 != 0 for w in ws):
-                raise ValueError(f"{what}: weight_dtype='fp8': every stacked weight needs a multiple of 8 rows")
-    check_shape(head.shape[0], head.shape[1], f"{what}: weight_dtype='fp8' (lm_head)")
+                raise ValueError(f"{what}: weight_dtype='{fmt}': every stacked weight needs a multiple of 8 rows")
+    shape_check(head.shape[0], head.shape[1], f"{what}: weight_dtype='{fmt}' (lm_head)")
+
+
+def source_key(model):
+    """(data_ptr, _version) of every source weight, in order: what a cached set of quantised decoder weights is keyed on"""
+    blocks, head = _sources(model)
+    return tuple((w.data_ptr(), w._version) for b in blocks for ws in b for w in ws) + ((head.data_ptr(), head._version),)
 
 
 def _stack(ws):
@@ -314,7 +324,7 @@ def quantize_decoder_weights(model):
     version changed.  The 16-bit parameters stay as they are.  -> DecoderW8"""
     check_decoder_weights(model, "quantize_decoder_weights")
     blocks, head = _sources(model)
-    key = tuple((w.data_ptr(), w._version) for b in blocks for ws in b for w in ws) + ((head.data_ptr(), head._version),)
+    key = source_key(model)
     cached = getattr(model, "_w8_decoder", None)
     if cached is not None and cached.key == key:
         return cached

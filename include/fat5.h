@@ -1133,6 +1133,66 @@ int fat5_w8_linear(const fat5_w8_linear_params* p, void* hip_stream);
 int fat5_w8_linear_mma(const fat5_w8_linear_params* p, void* hip_stream);
 
 /*
+ * MXFP4 weights: weight-only OCP microscaling FP4 linear layers for cached decoding (w4_kernels.h; tests/w4_ref.py
+ * restates this).
+ *   - A weight W (N, K), fp32 / fp16 / bf16, is stored as two byte tensors:
+ *       w4 (N, K / 2):  byte j of row n holds element k = 2 j in its low nibble and k = 2 j + 1 in its high nibble; a nibble is
+ *                       sign | 2 exponent bits | 1 mantissa bit (e2m1), magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6};
+ *       e8 (N, K / 32): byte b of row n is the e8m0 exponent of the block k = 32 b .. 32 b + 31 and means 2^(byte - 127); 255 is NaN.
+ *   - The quantisation rule (the bytes are the contract), per block of 32 values taken as fp32:
+ *       any value non-finite: scale byte 255, all nibbles 0;  amax = 0: X = 0;
+ *       otherwise X = clamp(floor(log2(amax)) - 2, -13, 13)   (the OCP rule with emax(e2m1) = 2);  scale byte = X + 127;
+ *       element = round-to-nearest-even of v * 2^-X onto the e2m1 grid, saturating at +-6; the sign bit is v's sign bit, also for
+ *       zeros and for values that round to zero.
+ *     Inside the clamp q * 2^X is a normal number of fp16 and of bf16 (0.5 * 2^-13 = 2^-14; 6 * 2^13 < 65504): the dequantised
+ *     weight is exact in either activation type, and its product with a 16-bit activation is exact in fp32.
+ *   - fat5_w4_linear:  y[r, n] = round_T( sum_k fp32(xin[r, k]) * q[n, k] * 2^X[n, k / 32] ),  T = fp16 | bf16, fp32 accumulation in a
+ *     fixed order that depends on K alone (the same bits for any R, N and grid, on every run and under graph replay).  There is no
+ *     per-row scale.  norm_weight, eps and residual mean what they mean for fat5_w8_linear: xin is bit for bit what
+ *     fat5_rmsnorm_fwd writes, and the residual is added to the already rounded y.  A block with scale byte 255 makes its output
+ *     column NaN; a NaN in a row of x stays in that row.  The result is defined for scale bytes in [114, 140] and 255 (all the
+ *     quantiser writes); for others it is unspecified, but nothing is read or written out of bounds.
+ *   - Legal shapes: K % 32 == 0 with 32 <= K <= 16384, N % 8 == 0, any R >= 0; R == 0 or N == 0 launches nothing.  x, residual, y
+ *     and the quantiser's w follow "FP8 weights"; w4: 16-byte aligned base, row stride in BYTES, a multiple of 16; e8: row stride
+ *     in bytes, at least K / 32.  Anything else, a NULL or misaligned pointer or stride: FAT5_EINVAL before any device work.
+ */
+typedef struct fat5_w4_quant_params {
+  int64_t N;                  /* weight rows (output features), N % 8 == 0 */
+  int32_t K;                  /* elements per row, K % 32 == 0, 32..16384 */
+  int32_t dtype;              /* FAT5_F32 | FAT5_F16 | FAT5_BF16: w */
+  const void* w;              /* (N, K), row stride w_stride elements (a multiple of 8), 16-byte aligned */
+  int64_t w_stride;
+  void* out;                  /* w4: (N, K / 2) bytes, row stride out_stride bytes (a multiple of 16), 16-byte aligned */
+  int64_t out_stride;
+  void* e8;                   /* (N, K / 32) bytes, row stride e_stride bytes */
+  int64_t e_stride;
+} fat5_w4_quant_params;
+size_t fat5_sizeof_w4_quant_params(void);
+int fat5_w4_quantize(const fat5_w4_quant_params* p, void* hip_stream);
+
+typedef struct fat5_w4_linear_params {
+  int64_t R;                  /* rows of x */
+  int64_t N;
+  int32_t K;
+  int32_t dtype;              /* FAT5_F16 | FAT5_BF16: x, norm_weight, residual, y */
+  const void* x;              /* (R, K), row stride x_stride */
+  int64_t x_stride;
+  const void* w4;             /* (N, K / 2) bytes, row stride w_stride bytes */
+  int64_t w_stride;
+  const void* e8;             /* (N, K / 32) bytes, row stride e_stride bytes */
+  int64_t e_stride;
+  const void* norm_weight;    /* (K,) or NULL */
+  float eps;                  /* with norm_weight: finite, >= 0 */
+  int32_t reserved;           /* 0 */
+  const void* residual;       /* (R, N), row stride residual_stride, or NULL */
+  int64_t residual_stride;
+  void* y;                    /* (R, N), row stride y_stride */
+  int64_t y_stride;
+} fat5_w4_linear_params;
+size_t fat5_sizeof_w4_linear_params(void);
+int fat5_w4_linear(const fat5_w4_linear_params* p, void* hip_stream);
+
+/*
  * Sequence pooling (pool_kernels.h): per-token hidden states to one vector per sequence, and its gradient.
  * Layouts -- at most one of cu_seqlens / seqlens is given:
  *   packed  (cu_seqlens != NULL): hidden is (total, d), rows hidden_row_stride elements apart; sequence b owns the rows

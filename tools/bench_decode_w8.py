@@ -11,7 +11,12 @@ Per kernel: `w8_linear` (plain instance), kernel="rows" and kernel="matrix", aga
 table has a `weight_kernel="matrix"` column at B > 8.  The matrix kernel is accepted against the row kernel of the same run: its
 min..max over the blocks must lie wholly below the row kernel's ("below rows" / "below fp8"); GB/s counts the weight bytes (N K, or 2 N K), the scales, x and y.
 Writes profiles/decode_w8_bench.log and prints one JSON line at the end.  `--kernel-only` / `--e2e-only` run one half,
-`--quick` only FAT5-base at B = 1 of the second."""
+`--quick` only FAT5-base at B = 1 of the second.
+
+`--mxfp4` runs the MXFP4 tables instead and writes profiles/decode_w4_bench.log: per launch, the FAT5-base projections
+and lm_head at R in {1, 8, 16, 64} with four alternating graphs (F.linear in bf16, w8_linear rows, w8_linear matrix, w4_linear; GB/s
+of the MXFP4 column counts N K 17 / 32 weight bytes, x and y), and end to end a FAT5-base step at B in {1, 8, 64} with the columns
+default, fp8, fp8 + weight_kernel="matrix" and mxfp4.  No ratio is asserted: the table says what was measured."""
 import json
 import os
 import statistics
@@ -23,6 +28,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 from flasht5_amd import FAT5Config, FAT5ForConditionalGeneration, generation, quantize_weight, w8_linear  # noqa: E402
+from flasht5_amd import quantize_weight_mxfp4, w4_linear  # noqa: E402
 
 REPEATS, ITERS = 7, 40
 L_ENC = 512
@@ -157,6 +163,71 @@ def kernels(say):
     return rows
 
 
+def kernels_w4(say):
+    rows = {}
+    say("# per launch, us median (min..max) of graph replays: F.linear bf16 | w8_linear rows | w8_linear matrix | w4_linear (MXFP4) GB/s")
+    say("#   R     K      N | bf16                              | fp8 rows                          | fp8 matrix                        "
+        "| mxfp4                                GB/s | mxfp4/rows | mxfp4/matrix | mxfp4/bf16")
+    for K, N in ((768, 768), (768, 2304), (768, 4096), (2048, 768), (768, 32128)):   # o / cross q, qkv, [wi_0; wi_1], wo, lm_head
+        W = (torch.randn(N, K, device="cuda") * 0.05).bfloat16()
+        w8, sc = quantize_weight(W)
+        q4, e8 = quantize_weight_mxfp4(W)
+        for R in (1, 8, 16, 64):
+            x = torch.randn(R, K, device="cuda", dtype=torch.bfloat16)
+            graphs = [capture(lambda: F.linear(x, W)), capture(lambda: w8_linear(x, w8, sc)),
+                      capture(lambda: w8_linear(x, w8, sc, kernel="matrix")), capture(lambda: w4_linear(x, q4, e8))]
+            t16, t8, tm, t4 = alternate(graphs)
+            m16, m8, mm, m4 = (statistics.median(t) for t in (t16, t8, tm, t4))
+            n4 = N * K * 17 // 32 + 2 * R * K + 2 * R * N
+            rows[f"R{R}_K{K}_N{N}"] = {"bf16_us": round(m16 * 1e6, 2), "rows_us": round(m8 * 1e6, 2), "matrix_us": round(mm * 1e6, 2),
+                                       "mxfp4_us": round(m4 * 1e6, 2), "mxfp4_min_us": round(min(t4) * 1e6, 2),
+                                       "mxfp4_max_us": round(max(t4) * 1e6, 2), "mxfp4_GBs": round(n4 / m4 / 1e9, 1)}
+            say(f"  {R:3d} {K:5d} {N:6d} | {fmt(t16, 1e6)} | {fmt(t8, 1e6)} | {fmt(tm, 1e6)} | {fmt(t4, 1e6)} {n4 / m4 / 1e9:7.1f} | "
+                f"{m4 / m8:.3f}      | {m4 / mm:.3f}        | {m4 / m16:.3f}")
+            del graphs
+    return rows
+
+
+def e2e_w4(say):
+    rows = {}
+    say("# ms per token of one graph-replayed greedy FAT5-base step, median (min..max): default (16-bit) | fp8 | fp8 matrix (B > 8) | mxfp4")
+    torch.manual_seed(0)
+    model = FAT5ForConditionalGeneration(FAT5Config()).bfloat16().cuda().eval()
+    V = model.lm_head.weight.shape[0]
+    for B in (1, 8, 64):
+        ids = torch.randint(2, V, (B, L_ENC), device="cuda")
+        variants = [(None, None), ("fp8", None)] + ([("fp8", "matrix")] if B > 8 else []) + [("mxfp4", None)]
+        with torch.no_grad():
+            built = [step_graph(model, ids, wd, wk) for wd, wk in variants]
+        times = alternate([b[0] for b in built], [b[1] for b in built])
+        med = [statistics.median(t) for t in times]
+        names = ["default", "fp8"] + (["matrix"] if B > 8 else []) + ["mxfp4"]
+        rows[f"B{B}"] = {f"{n}_ms": round(m * 1e3, 4) for n, m in zip(names, med)}
+        rows[f"B{B}"].update(mxfp4_min_ms=round(min(times[-1]) * 1e3, 4), mxfp4_max_ms=round(max(times[-1]) * 1e3, 4))
+        say(f"  B {B:3d} | " + " | ".join(f"{n} {fmt(t, 1e3)}" for n, t in zip(names, times)) +
+            f" | mxfp4/fp8 {med[-1] / med[1]:.3f} | mxfp4/default {med[-1] / med[0]:.3f}")
+        del built
+    return rows
+
+
+def main_w4():
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+    say(f"# MXFP4 decoder weights; {REPEATS} alternating blocks of {ITERS} graph replays; {torch.cuda.get_device_name(0)}")
+    res = {}
+    if "--e2e-only" not in sys.argv:
+        res["kernel"] = kernels_w4(say)
+    if "--kernel-only" not in sys.argv:
+        res["end_to_end"] = e2e_w4(say)
+    out = os.environ.get("FAT5_BENCH_LOG", os.path.join(ROOT, "profiles", "decode_w4_bench.log"))
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(json.dumps({"decode_w4": res}))
+
+
 def main():
     lines = []
 
@@ -176,4 +247,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main_w4() if "--mxfp4" in sys.argv else main()
