@@ -31,6 +31,7 @@ from .positional_encoding import (relative_position_bucket, compute_bias, rpe1d_
 from .decode import flash_attn_with_kvcache, flash_attn_with_kvcache_chunk, quantize_kv  # noqa: E402
 from .w8 import quantize_weight, w8_linear  # noqa: E402
 from .w4 import quantize_weight_mxfp4, w4_linear, quantize_decoder_weights_mxfp4  # noqa: E402
+from .w4a8 import quantize_activation_mxfp8, w4a8_linear, w4a8_matmul, quantize_encoder_weights_mxfp4  # noqa: E402
 from .sampling import sample_logits  # noqa: E402
 from .logits_process import process_logits, pack_bad_words  # noqa: E402
 from .speculative import speculative_accept, speculative_round, draft_tokens  # noqa: E402

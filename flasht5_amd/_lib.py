@@ -266,6 +266,25 @@ class W4LinearParams(ctypes.Structure):
     ]
 
 
+class Mx8QuantParams(ctypes.Structure):
+    """Mirror of `fat5_mx8_quant_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("R", ctypes.c_int64), ("K", ctypes.c_int32), ("dtype", ctypes.c_int32), ("x", ctypes.c_void_p), ("x_stride", ctypes.c_int64),
+        ("norm_weight", ctypes.c_void_p), ("eps", ctypes.c_float), ("reserved", ctypes.c_int32), ("a8", ctypes.c_void_p),
+        ("a_stride", ctypes.c_int64), ("ax", ctypes.c_void_p), ("ax_stride", ctypes.c_int64),
+    ]
+
+
+class W4A8LinearParams(ctypes.Structure):
+    """Mirror of `fat5_w4a8_linear_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("R", ctypes.c_int64), ("N", ctypes.c_int64), ("K", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("a8", ctypes.c_void_p), ("a_stride", ctypes.c_int64), ("ax", ctypes.c_void_p), ("ax_stride", ctypes.c_int64),
+        ("w4", ctypes.c_void_p), ("w_stride", ctypes.c_int64), ("e8", ctypes.c_void_p), ("e_stride", ctypes.c_int64),
+        ("residual", ctypes.c_void_p), ("residual_stride", ctypes.c_int64), ("y", ctypes.c_void_p), ("y_stride", ctypes.c_int64),
+    ]
+
+
 POOL_EOS, POOL_FIRST, POOL_LAST, POOL_MEAN = 0, 1, 2, 3  # fat5_pool_mode
 
 
@@ -327,6 +346,7 @@ EXPORTS = (
     "fat5_ul2_collate", "fat5_sizeof_ul2_params",
     "fat5_w8_quantize", "fat5_sizeof_w8_quant_params", "fat5_w8_linear", "fat5_sizeof_w8_linear_params", "fat5_w8_linear_mma",
     "fat5_w4_quantize", "fat5_sizeof_w4_quant_params", "fat5_w4_linear", "fat5_sizeof_w4_linear_params",
+    "fat5_mx8_quantize", "fat5_sizeof_mx8_quant_params", "fat5_w4a8_linear", "fat5_sizeof_w4a8_linear_params",
     "fat5_dropout", "fat5_dropout_add_rmsnorm_fwd", "fat5_dropout_add_rmsnorm_bwd", "fat5_sizeof_dropout_desc",
     "fat5_seq_pool_fwd", "fat5_seq_pool_bwd", "fat5_sizeof_seq_pool_params",
     "fat5_kd_fwd", "fat5_kd_bwd", "fat5_kd_fwd_bwd", "fat5_sizeof_kd_params",
@@ -509,7 +529,10 @@ def load():
     for fn, size_fn, struct, name in ((lib.fat5_w8_quantize, lib.fat5_sizeof_w8_quant_params, W8QuantParams, "fat5_w8_quant_params"),
                                       (lib.fat5_w8_linear, lib.fat5_sizeof_w8_linear_params, W8LinearParams, "fat5_w8_linear_params"),
                                       (lib.fat5_w4_quantize, lib.fat5_sizeof_w4_quant_params, W4QuantParams, "fat5_w4_quant_params"),
-                                      (lib.fat5_w4_linear, lib.fat5_sizeof_w4_linear_params, W4LinearParams, "fat5_w4_linear_params")):
+                                      (lib.fat5_w4_linear, lib.fat5_sizeof_w4_linear_params, W4LinearParams, "fat5_w4_linear_params"),
+                                      (lib.fat5_mx8_quantize, lib.fat5_sizeof_mx8_quant_params, Mx8QuantParams, "fat5_mx8_quant_params"),
+                                      (lib.fat5_w4a8_linear, lib.fat5_sizeof_w4a8_linear_params, W4A8LinearParams,
+                                       "fat5_w4a8_linear_params")):
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
         size_fn.restype = ctypes.c_size_t

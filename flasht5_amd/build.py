@@ -28,6 +28,8 @@ UNITS = [(f"api_{n}.hip", f"api_{n}.o", []) for n in ("core", "attn", "rowwise",
 UNITS.append(("api_w8_mma.hip", "api_w8_mma.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
 # the MXFP4-weight linear: its staging expression and statistics are that unit's, kept under the same code generation
 UNITS.append(("api_w4.hip", "api_w4.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
+# the MXFP8 activation quantiser and the W4A8 GEMM: the quantiser's NORM expression and statistics are that unit's too
+UNITS.append(("api_w4a8.hip", "api_w4a8.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
 # the Adafactor step: its sums and updates are scalar fp32 ops too
 UNITS.append(("api_adafactor.hip", "api_adafactor.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
 for d in (32, 64, 128):

@@ -521,14 +521,19 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         return dec, lab.unsqueeze(0)
 
     def init_decode_state(self, input_ids, max_length=32, attention_mask=None, prompt_length=1, kv_cache_dtype=None, weight_dtype=None,
-                          weight_kernel=None):
+                          weight_kernel=None, encoder_weight_dtype=None):
         """encoder output, cross K / V and empty self-attention caches of capacity max_length + prompt_length (generation.DecodeState);
         kv_cache_dtype="fp8": the caches as e4m3fn bytes plus one fp32 scale per row and head; weight_dtype="fp8": the state's steps
         read the FP8 decoder weights of `quantize_decoder_weights`, with weight_kernel="matrix" on the MFMA kernel wherever a
         projection has more than 8 rows"""
         from .generation import init_decode_state
         return init_decode_state(self, input_ids, max_length, attention_mask, prompt_length=prompt_length, kv_cache_dtype=kv_cache_dtype,
-                                 weight_dtype=weight_dtype, weight_kernel=weight_kernel)
+                                 weight_dtype=weight_dtype, weight_kernel=weight_kernel, encoder_weight_dtype=encoder_weight_dtype)
+
+    def quantize_encoder_weights_mxfp4(self):
+        """the MXFP4 copies of the encoder's projections, for encoder_weight_dtype="mxfp4" (w4a8.quantize_encoder_weights_mxfp4)"""
+        from .w4a8 import quantize_encoder_weights_mxfp4
+        return quantize_encoder_weights_mxfp4(self)
 
     def quantize_decoder_weights(self):
         """the FP8 (e4m3fn bytes + one fp32 scale per output row) copies of the decoder weights a cached step reads, built once and
@@ -559,7 +564,8 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
                  decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
                  decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
                  encoder_repetition_penalty=1.0, encoder_no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
-                 forced_bos_token_id=None, forced_eos_token_id=None, weight_dtype=None, weight_kernel=None):
+                 forced_bos_token_id=None, forced_eos_token_id=None, weight_dtype=None, weight_kernel=None,
+                 encoder_weight_dtype=None):
         """greedy (or, with do_sample=True, temperature / top-k / top-p sampled) decoding with a KV cache; returns what the
         reference's generate returns; num_beams > 1: HF's beam search; repetition_penalty / no_repeat_ngram_size / min_length /
         suppress_tokens / encoder_repetition_penalty / encoder_no_repeat_ngram_size / bad_words_ids / min_new_tokens /
@@ -569,7 +575,8 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         caches as e4m3fn bytes plus per-row scales, in every mode; prompt_lookup_num_tokens / max_matching_ngram_size: speculative greedy
         decoding drafted by an n-gram search of the input and the output so far, one launch per round; weight_dtype="fp8": the decoder
         weights of a step as e4m3fn bytes plus per-row scales, every projection one fused HIP launch, with weight_kernel="matrix" the MFMA kernel for the
-        projections of more than 8 rows (generation.generate)"""
+        projections of more than 8 rows; encoder_weight_dtype="mxfp4": the encoder over its MXFP4 weights on the block-scaled MFMA
+        (generation.generate)"""
         from .generation import generate
         return generate(self, input_ids, attention_mask, max_length, graph, do_sample=do_sample, temperature=temperature,
                         top_k=top_k, top_p=top_p, seed=seed, num_beams=num_beams, num_return_sequences=num_return_sequences,
@@ -582,7 +589,8 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
                         encoder_repetition_penalty=encoder_repetition_penalty,
                         encoder_no_repeat_ngram_size=encoder_no_repeat_ngram_size, bad_words_ids=bad_words_ids,
                         min_new_tokens=min_new_tokens, forced_bos_token_id=forced_bos_token_id,
-                        forced_eos_token_id=forced_eos_token_id, weight_dtype=weight_dtype, weight_kernel=weight_kernel)
+                        forced_eos_token_id=forced_eos_token_id, weight_dtype=weight_dtype, weight_kernel=weight_kernel,
+                        encoder_weight_dtype=encoder_weight_dtype)
 
 
 def allreduce_gradients(model: nn.Module, group=None, average=True):

@@ -233,9 +233,12 @@ def _masked_bias_encoder(stack, input_ids, pad):
     return stack.final_layer_norm(h).masked_fill(~pad.mask.unsqueeze(-1), 0)
 
 
-def encode(model, input_ids, pad=None):
+def encode(model, input_ids, pad=None, encoder_weight_dtype=None):
     """the encoder's output (B, L, d_model); with a `Padding`, every row's self-attention sees its own valid keys only and the
-    padded rows come back as zeros"""
+    padded rows come back as zeros.  encoder_weight_dtype="mxfp4" (DESIGN 4.28): the stack over the model's MXFP4 encoder weights
+    (`quantize_encoder_weights_mxfp4`) through `w4a8_linear`; None: the code below as it always ran"""
+    if encoder_weight_dtype is not None:
+        return _encode_mxfp4(model, input_ids, pad, encoder_weight_dtype)
     if pad is None:
         return model.encoder(input_ids)
     att = model.encoder.block[0].self_attention_layer.self_attention
@@ -246,9 +249,37 @@ def encode(model, input_ids, pad=None):
     return _masked_bias_encoder(model.encoder, input_ids, pad)
 
 
+def _encode_mxfp4(model, input_ids, pad, encoder_weight_dtype, what="generate"):
+    """`encode` over the MXFP4 encoder weights: the three paths above (unpadded, packed rows, masked dense bias) with every
+    projection a `w4a8_linear` (w4a8.encoder_forward_mxfp4); the host checks come before anything runs"""
+    from .packing import Packed
+    from .w4a8 import check_encoder_weight_dtype, encoder_forward_mxfp4, encoder_weights_mxfp4
+    check_encoder_weight_dtype(encoder_weight_dtype, what)
+    weights = encoder_weights_mxfp4(model, what)
+    stack = model.encoder
+    if pad is None:
+        return encoder_forward_mxfp4(stack, weights, input_ids)
+    B, L = input_ids.shape
+    att = stack.block[0].self_attention_layer.self_attention
+    if att.rotary or att.attention_type == "fat5_rpe":   # (_packed_encoder's indices)
+        lens, dev = pad.lengths, input_ids.device
+        idx = torch.cat([torch.arange(n) + b * L for b, n in enumerate(lens)]).to(dev)
+        cu = torch.tensor([0] + [sum(lens[:b + 1]) for b in range(B)], dtype=torch.int32).to(dev)
+        h = encoder_forward_mxfp4(stack, weights, input_ids.reshape(-1).index_select(0, idx).unsqueeze(0), packing=Packed(cu, max(lens)))
+        enc = h.new_zeros((B * L, h.shape[-1]))
+        enc.index_copy_(0, idx, h[0])
+        return enc.view(B, L, -1)
+    if att.position_encoding_type != "t5":
+        raise NotImplementedError(f"attention_mask with position_encoding_type {att.position_encoding_type!r}")
+    dtype = stack.embed_tokens.weight.dtype
+    bias = att.pe_encoding.compute_bias(L, L, device=input_ids.device).to(dtype)   # (_masked_bias_encoder's bias)
+    bias = torch.where(pad.mask.view(B, 1, 1, L), bias, torch.finfo(dtype).min).contiguous()
+    return encoder_forward_mxfp4(stack, weights, input_ids, position_bias=bias).masked_fill(~pad.mask.unsqueeze(-1), 0)
+
+
 @torch.no_grad()
 def init_decode_state(model, input_ids, max_length, attention_mask=None, num_beams=1, prompt_length=1, kv_cache_dtype=None,
-                      weight_dtype=None, weight_kernel=None):
+                      weight_dtype=None, weight_kernel=None, encoder_weight_dtype=None):
     """Run the encoder, project every decoder layer's cross-attention K / V once and allocate self-attention caches of capacity
     `max_length + prompt_length` (a decoder prompt of `prompt_length` tokens, the start token included, then max_length new ones).
     `attention_mask` (B, L), right-padded, is applied: it is validated with one host read before the encoder runs
@@ -262,7 +293,9 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     (`quantize_decoder_weights`, built once per model) through `w8_linear`; checked, like the decoder's dtype and shapes, before
     the encoder runs.  weight_kernel (None, "rows" or "matrix"; with weight_dtype="fp8" only): see `generate`.
     weight_dtype="mxfp4" (DESIGN 4.27): the same steps over the model's MXFP4 decoder weights (`quantize_decoder_weights_mxfp4`)
-    through `w4_linear`; weight_kernel must be None."""
+    through `w4_linear`; weight_kernel must be None.
+    encoder_weight_dtype="mxfp4" (DESIGN 4.28): the encoder runs over the model's MXFP4 encoder weights
+    (`quantize_encoder_weights_mxfp4`); checked before it runs.  The steps are untouched."""
     fp8 = check_kv_cache_dtype(kv_cache_dtype, "init_decode_state")
     w8 = _check_weight_dtype(model, weight_dtype, "init_decode_state")
     w8_kernel = _check_weight_kernel(weight_kernel, weight_dtype, "init_decode_state")
@@ -277,7 +310,8 @@ def init_decode_state(model, input_ids, max_length, attention_mask=None, num_bea
     B = input_ids.shape[0]
     Bk = B * int(num_beams)
     pad, _ = check_padding(input_ids, attention_mask, what="init_decode_state")
-    enc = encode(model, input_ids, pad)
+    # (None: the three-argument call as it always was, which is what stands in for `encode` in the padding tests)
+    enc = encode(model, input_ids, pad) if encoder_weight_dtype is None else encode(model, input_ids, pad, encoder_weight_dtype)
     dev = enc.device
     # (the projections' dtype: autocast's when it is on, the weights' otherwise -- the dtype of k and v in the training forward)
     dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else model.shared.weight.dtype
@@ -352,6 +386,14 @@ def _check_weight_dtype(model, weight_dtype, what="generate"):
         from .w4 import check_decoder_weights_mxfp4
         check_decoder_weights_mxfp4(model, what)
     return fmt
+
+
+def _check_encoder_weight_dtype(model, encoder_weight_dtype, what="generate"):
+    """None or "mxfp4"; with the format, the encoder's dtype and shapes and the presence of its quantised copies (host only)"""
+    if encoder_weight_dtype is not None:
+        from .w4a8 import check_encoder_weight_dtype, encoder_weights_mxfp4
+        check_encoder_weight_dtype(encoder_weight_dtype, what)
+        encoder_weights_mxfp4(model, what)
 
 
 def _check_weight_kernel(weight_kernel, weight_dtype, what="generate"):
@@ -574,12 +616,12 @@ def _beam_step(model, state, tok, bs, opts, proc=None):
 
 
 def _beam_generate(model, input_ids, attention_mask, max_length, graph, k, R, length_penalty, early_stopping, return_scores,
-                   proc=None, kv_cache_dtype=None, weight_dtype=None, weight_kernel=None):
+                   proc=None, kv_cache_dtype=None, weight_dtype=None, weight_kernel=None, encoder_weight_dtype=None):
     from .beam import new_state, keep_going
     B = input_ids.shape[0]
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask, num_beams=k, kv_cache_dtype=kv_cache_dtype,
-                              weight_dtype=weight_dtype, weight_kernel=weight_kernel)
+                              weight_dtype=weight_dtype, weight_kernel=weight_kernel, encoder_weight_dtype=encoder_weight_dtype)
     bs = new_state(B, k, int(max_length) + 1, state.capacity, dev)
     proc = _proc_on_device(proc, dev, input_ids, attention_mask, None, k)
     bs.cache_row_batch = state.row_batch  # (one table: the decode kernel reads it, the beam step reorders it)
@@ -602,7 +644,7 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
              decoder_input_ids=None, assistant_model=None, num_assistant_tokens=4, return_stats=False,
              decoder_attention_mask=None, kv_cache_dtype=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=2,
              encoder_repetition_penalty=1.0, encoder_no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0,
-             forced_bos_token_id=None, forced_eos_token_id=None, weight_dtype=None, weight_kernel=None):
+             forced_bos_token_id=None, forced_eos_token_id=None, weight_dtype=None, weight_kernel=None, encoder_weight_dtype=None):
     """Greedy decoding with the reference's algorithm and return value: start token 0, argmax, stop once every row holds a 1
     (one host read per token, as in the reference), then `finish_labels`.  Returns (B, steps + 1) int64.
 
@@ -723,8 +765,13 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
     value, or a weight_kernel without weight_dtype="fp8", raises ValueError before an encoder runs.
     `weight_dtype="mxfp4"`: the same 9 launches per block and the same modes over MXFP4 copies of the decoder weights
     (`quantize_decoder_weights_mxfp4`: e2m1 nibbles and one e8m0 scale byte per 32 weights, N * K * 17 / 32 bytes per stack, built
-    once per model; an assistant's the same way), each launch `w4_linear`'s one MFMA kernel; `weight_kernel` must be None."""
+    once per model; an assistant's the same way), each launch `w4_linear`'s one MFMA kernel; `weight_kernel` must be None.
+    `encoder_weight_dtype="mxfp4"`: the encoder, which runs once and outside the step graph, reads MXFP4 copies of its
+    projections (`quantize_encoder_weights_mxfp4`) through `w4a8_linear` (activations quantised per row and block of 32 to MXFP8, the
+    block-scaled MFMA kernel); every mode, padding, `weight_dtype`, `kv_cache_dtype` and `graph=True` combine with it, the steps are
+    untouched, and an assistant's encoder keeps its 16-bit weights.  None: today's encoder, bit for bit."""
     check_kv_cache_dtype(kv_cache_dtype)
+    _check_encoder_weight_dtype(model, encoder_weight_dtype)
     _check_weight_dtype(model, weight_dtype)
     _check_weight_kernel(weight_kernel, weight_dtype)
     from .beam import check_args as check_beam_args
@@ -759,16 +806,16 @@ def generate(model, input_ids, attention_mask=None, max_length=32, graph=False, 
                                     prompt_lookup_num_tokens if lookup else num_assistant_tokens, P, decoder_input_ids,
                                     bool(return_stats), kv_cache_dtype, lookup_ngram=max_matching_ngram_size if lookup else None,
                                     sampling=_sampling(do_sample, temperature, top_k, top_p, seed), weight_dtype=weight_dtype,
-                                    weight_kernel=weight_kernel)
+                                    weight_kernel=weight_kernel, encoder_weight_dtype=encoder_weight_dtype)
     if num_beams > 1:
         return _beam_generate(model, input_ids, attention_mask, max_length, graph, num_beams, num_return_sequences, length_penalty,
-                              early_stopping, return_scores, proc, kv_cache_dtype, weight_dtype, weight_kernel)
+                              early_stopping, return_scores, proc, kv_cache_dtype, weight_dtype, weight_kernel, encoder_weight_dtype)
     proc = _proc_on_device(proc, input_ids.device, input_ids, attention_mask, dec_pad)
     sampling = _sampling(do_sample, temperature, top_k, top_p, seed)
     B = input_ids.shape[0]
     dev = input_ids.device
     state = init_decode_state(model, input_ids, max_length, attention_mask, prompt_length=P, kv_cache_dtype=kv_cache_dtype,
-                              weight_dtype=weight_dtype, weight_kernel=weight_kernel)
+                              weight_dtype=weight_dtype, weight_kernel=weight_kernel, encoder_weight_dtype=encoder_weight_dtype)
     labels = torch.zeros((B, state.capacity), dtype=torch.long, device=dev)
     tok = torch.zeros((B,), dtype=torch.long, device=dev)
     seen_eos = torch.zeros((B,), dtype=torch.bool, device=dev)

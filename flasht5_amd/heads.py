@@ -121,8 +121,33 @@ class _EncoderOnly(nn.Module):
         self.encoder.block[0].self_attention_layer.self_attention.packed_supported()   # (NotImplementedError: dense bias, FIRE, ...)
         return plan
 
-    def _encode(self, input_ids, attention_mask):
-        """-> (_Rows, the head's dropout context)"""
+    def quantize_encoder_weights_mxfp4(self):
+        """the MXFP4 (e2m1 nibbles + one e8m0 scale byte per 32 weights) copies of the encoder's projections, for
+        forward(..., weight_dtype="mxfp4") (w4a8.quantize_encoder_weights_mxfp4)"""
+        from .w4a8 import quantize_encoder_weights_mxfp4
+        return quantize_encoder_weights_mxfp4(self)
+
+    def _encode_mxfp4(self, input_ids, attention_mask):
+        """`_encode` over the MXFP4 encoder weights: inference only, checked on the host before anything runs"""
+        from .packing import Packed
+        from .w4a8 import encoder_forward_mxfp4, encoder_weights_mxfp4
+        weights = encoder_weights_mxfp4(self, "forward")
+        plan = self._plan(input_ids, attention_mask)
+        B, L = input_ids.shape
+        if plan is None:
+            ids = input_ids.reshape(-1)
+            h = encoder_forward_mxfp4(self.encoder, weights, input_ids)
+        else:
+            ids = input_ids.reshape(-1).index_select(0, plan.index)
+            h = encoder_forward_mxfp4(self.encoder, weights, ids.unsqueeze(0), packing=Packed(plan.cu_seqlens, plan.max_seqlen))
+        return _Rows(h.reshape(-1, h.shape[-1]), ids, plan, B, L), None
+
+    def _encode(self, input_ids, attention_mask, weight_dtype=None):
+        """-> (_Rows, the head's dropout context); weight_dtype="mxfp4": the encoder over its MXFP4 weights"""
+        if weight_dtype is not None:
+            from .w4a8 import check_encoder_weight_dtype
+            check_encoder_weight_dtype(weight_dtype, "forward")
+            return self._encode_mxfp4(input_ids, attention_mask)
         from .packing import Packed
         plan = self._plan(input_ids, attention_mask)
         drop, head_drop = self._drops()
@@ -147,12 +172,12 @@ class FAT5EncoderModel(_EncoderOnly):
         super().__init__(config)
         self.reset_parameters()
 
-    def forward(self, input_ids, attention_mask=None, pool=None):
+    def forward(self, input_ids, attention_mask=None, pool=None, weight_dtype=None):
         """pool None: last_hidden_state (B, L, d_model), zero at the padded positions; "eos", "mean", "first" or "last": (B, d_model)
         through `sequence_pool` over each row's valid tokens"""
         if pool is not None and pool not in MODES:
             raise ValueError(f"forward: pool {pool!r} (None or one of {', '.join(repr(m) for m in MODES)})")
-        rows, _ = self._encode(input_ids, attention_mask)
+        rows, _ = self._encode(input_ids, attention_mask, weight_dtype)
         if pool is None:
             return rows.scatter(rows.h)
         return rows.pool(pool, self.config.eos_token_id)[0]
@@ -176,10 +201,10 @@ class FAT5ForTokenClassification(_EncoderOnly):
             self.classifier.weight.normal_(0.0, 1.0)
             self.classifier.bias.zero_()
 
-    def forward(self, input_ids, labels=None, attention_mask=None, return_logits=False):
+    def forward(self, input_ids, labels=None, attention_mask=None, return_logits=False, weight_dtype=None):
         """labels (B, L) int64, -100 = ignored: the loss, a mean over the labels that are not -100 at valid positions.  Without
         labels: logits (B, L, num_labels), 0 at the padded positions.  return_logits with labels: (loss, logits)."""
-        rows, drop = self._encode(input_ids, attention_mask)
+        rows, drop = self._encode(input_ids, attention_mask, weight_dtype)
         logits = self.classifier(self._head_drop(rows.h, drop, 0))
         if labels is None:
             return rows.scatter(logits)
@@ -230,11 +255,11 @@ class FAT5ForSequenceClassification(_EncoderOnly):
                 self.problem_type = "multi_label_classification"
         return self.problem_type
 
-    def forward(self, input_ids, labels=None, attention_mask=None, return_logits=False):
+    def forward(self, input_ids, labels=None, attention_mask=None, return_logits=False, weight_dtype=None):
         """labels: (B,) integer classes, (B,) / (B, 1) regression targets (num_labels == 1) or (B, num_labels) floating-point
         multi-label targets -> the loss; without labels: logits (B, num_labels), fp32.  return_logits with labels: (loss, logits).
         Nothing is read on the host: `last_found` keeps the (B,) int32 flags of this forward for `check`."""
-        rows, drop = self._encode(input_ids, attention_mask)
+        rows, drop = self._encode(input_ids, attention_mask, weight_dtype)
         pooled, _, found = rows.pool("eos", self.config.eos_token_id)
         self.last_found = found
         # the head works on B rows: its two small GEMMs, the tanh, the logits and the loss stay in fp32 whatever the model's dtype
@@ -284,7 +309,8 @@ class FAT5ForQuestionAnswering(_EncoderOnly):
             self.qa_outputs.weight.normal_(0.0, 1.0)
             self.qa_outputs.bias.zero_()
 
-    def forward(self, input_ids, labels=None, attention_mask=None, start_positions=None, end_positions=None, return_logits=False):
+    def forward(self, input_ids, labels=None, attention_mask=None, start_positions=None, end_positions=None, return_logits=False,
+                weight_dtype=None):
         """labels (B, 2) = [start, end], or start_positions= / end_positions= (B,): the reference's loss -- positions clamped to
         [0, L], L ignored, the mean of the two cross-entropies over the (B, L) start / end logits -- with a target in a row's
         padding ignored as well.  Without targets: (start_logits, end_logits), both (B, L), the dtype's minimum at the padded
@@ -297,7 +323,7 @@ class FAT5ForQuestionAnswering(_EncoderOnly):
             start_positions, end_positions = labels[:, 0], labels[:, 1]
         elif (start_positions is None) != (end_positions is None):
             raise ValueError("forward: start_positions and end_positions come together")
-        rows, _ = self._encode(input_ids, attention_mask)
+        rows, _ = self._encode(input_ids, attention_mask, weight_dtype)
         logits = self.qa_outputs(rows.h)
         full = rows.scatter(logits, torch.finfo(logits.dtype).min)
         # (copies, never views of `full`: the loss op's backward is declared to write its logits, and at L = 1 a slice is contiguous)

@@ -386,7 +386,7 @@ def check_lookup_generate_args(model, input_ids, max_length, prompt_lookup_num_t
 @torch.no_grad()
 def speculative_generate(model, assistant_model, input_ids, attention_mask, max_length, graph, num_assistant_tokens, prompt_length,
                          decoder_input_ids, return_stats, kv_cache_dtype=None, lookup_ngram=None, sampling=None, weight_dtype=None,
-                         weight_kernel=None):
+                         weight_kernel=None, encoder_weight_dtype=None):
     """`generate`'s speculative loop (the arguments are checked already): per round the drafter, one chunk step of the target
     and the verification kernel, then ONE host read (`seen_eos.all()`), as the plain loop does once per token.  The drafter is
     the assistant model (gamma + 1 draft steps) or, with `assistant_model=None`, the prompt lookup (ONE launch over
@@ -403,7 +403,9 @@ def speculative_generate(model, assistant_model, input_ids, attention_mask, max_
     if weight_dtype is not None:   # (and both decoders the weight dtype)
         kv["weight_dtype"] = weight_dtype
         kv["weight_kernel"] = weight_kernel   # (the chunk step of gamma + 1 rows per batch row is where the matrix kernel pays)
-    state = init_decode_state(model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P, **kv)
+    # (encoder_weight_dtype is the target's: an assistant's encoder keeps its 16-bit weights)
+    state = init_decode_state(model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P,
+                              encoder_weight_dtype=encoder_weight_dtype, **kv)
     dstate = None if lookup else init_decode_state(assistant_model, input_ids, T_max + gamma + 1, attention_mask, prompt_length=P, **kv)
     labels = torch.zeros((B, P + T_max), dtype=torch.long, device=dev)
     limit = P - 1 + T_max

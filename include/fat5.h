@@ -1193,6 +1193,71 @@ size_t fat5_sizeof_w4_linear_params(void);
 int fat5_w4_linear(const fat5_w4_linear_params* p, void* hip_stream);
 
 /*
+ * MXFP8 activations: many-row MXFP4-weight linear layers on the block-scaled MFMA, W4A8 (w4a8_kernels.h;
+ * tests/w4a8_ref.py restates this).  The weights are the w4 / e8 tensors of "MXFP4 weights"; the activations are quantised too:
+ *   - x (R, K), fp16 / bf16, K % 32 == 0, becomes two byte tensors:
+ *       a8 (R, K):      OCP e4m3fn bytes (sign | 4 exponent bits, bias 7 | 3 mantissa bits; largest value 448, no inf);
+ *       ax (R, K / 32): byte b of row r is the e8m0 exponent of the block k = 32 b .. 32 b + 31 and means 2^(byte - 127); 255 is NaN.
+ *   - The quantisation rule (the bytes are the contract), per block of 32 values taken as fp32:
+ *       any value non-finite: scale byte 255, all bytes 0;  amax = 0: X = 0;
+ *       otherwise X = floor(log2(amax)) - 8   (the OCP rule with emax(e4m3) = 8), clamped so that the scale byte X + 127 stays in
+ *       [1, 254];  element = round-to-nearest-even of v * 2^-X onto the e4m3fn grid (its subnormals, multiples of 2^-9, included),
+ *       saturating at +-448; the sign bit is v's sign bit, also for zeros and for values that round to zero.
+ *   - norm_weight (with eps): v is round_T(x * rstd * norm_weight), bit for bit what fat5_rmsnorm_fwd writes, so the bytes are those
+ *     of that kernel followed by the plain quantiser.
+ *   - fat5_w4a8_linear:  y[r, n] = round_T( sum_b 2^(ax[r, b] + e8[n, b] - 254) * sum_{k in block b} a8[r, k] * q[n, k] ),  T = fp16 |
+ *     bf16, summed in a fixed order that depends on K alone (the same bits for any R, N and grid, on every run and under graph
+ *     replay; a row's result does not depend on the other rows of the call): 128 k at a time inside gfx950's block-scaled MFMA,
+ *     the steps added in fp32 in ascending k.  The sum is NOT an fp32 sum of the products: as measured, the instruction aligns
+ *     the 32 products of a block to the block's largest and drops what lies about 2^-12 below it (a block holding 256, -256 and
+ *     2^-6 contributes 0; the same 2^-6 in another block is kept; a term 2^-11 below the largest was seen kept, one 2^-14 below lost).
+ *     Where exactly the cut lies is the hardware's; callers whose blocks hold products that far apart lose the small ones.
+ *     residual is added to the already rounded y.  A
+ *     weight block with scale byte 255 makes its output column NaN, an activation block with scale byte 255 its output row.
+ *   - Legal shapes: K % 32 == 0 with 32 <= K <= 16384, N % 8 == 0, any R >= 0; R == 0 or N == 0 launches nothing.  x, residual and y
+ *     follow "FP8 weights"; a8: 16-byte aligned base, row stride in BYTES, a multiple of 16; ax: row stride in bytes, at least
+ *     K / 32; w4 and e8 as for the MXFP4-weight linear.  Anything else, a NULL or misaligned pointer or stride: FAT5_EINVAL before
+ *     any device work.
+ */
+typedef struct fat5_mx8_quant_params {
+  int64_t R;                  /* rows of x */
+  int32_t K;                  /* elements per row, K % 32 == 0, 32..16384 */
+  int32_t dtype;              /* FAT5_F16 | FAT5_BF16: x, norm_weight */
+  const void* x;              /* (R, K), row stride x_stride elements (a multiple of 8), 16-byte aligned */
+  int64_t x_stride;
+  const void* norm_weight;    /* (K,) or NULL */
+  float eps;                  /* with norm_weight: finite, >= 0 */
+  int32_t reserved;           /* 0 */
+  void* a8;                   /* (R, K) bytes, row stride a_stride bytes (a multiple of 16), 16-byte aligned */
+  int64_t a_stride;
+  void* ax;                   /* (R, K / 32) bytes, row stride ax_stride bytes */
+  int64_t ax_stride;
+} fat5_mx8_quant_params;
+size_t fat5_sizeof_mx8_quant_params(void);
+int fat5_mx8_quantize(const fat5_mx8_quant_params* p, void* hip_stream);
+
+typedef struct fat5_w4a8_linear_params {
+  int64_t R;                  /* rows of a8 */
+  int64_t N;
+  int32_t K;
+  int32_t dtype;              /* FAT5_F16 | FAT5_BF16: residual, y */
+  const void* a8;             /* (R, K) bytes, row stride a_stride bytes */
+  int64_t a_stride;
+  const void* ax;             /* (R, K / 32) bytes, row stride ax_stride bytes */
+  int64_t ax_stride;
+  const void* w4;             /* (N, K / 2) bytes, row stride w_stride bytes */
+  int64_t w_stride;
+  const void* e8;             /* (N, K / 32) bytes, row stride e_stride bytes */
+  int64_t e_stride;
+  const void* residual;       /* (R, N), row stride residual_stride, or NULL */
+  int64_t residual_stride;
+  void* y;                    /* (R, N), row stride y_stride */
+  int64_t y_stride;
+} fat5_w4a8_linear_params;
+size_t fat5_sizeof_w4a8_linear_params(void);
+int fat5_w4a8_linear(const fat5_w4a8_linear_params* p, void* hip_stream);
+
+/*
  * Sequence pooling (pool_kernels.h): per-token hidden states to one vector per sequence, and its gradient.
  * Layouts -- at most one of cu_seqlens / seqlens is given:
  *   packed  (cu_seqlens != NULL): hidden is (total, d), rows hidden_row_stride elements apart; sequence b owns the rows
