@@ -105,6 +105,18 @@ class FlashT5Attention(nn.Module):
                              "threshold T, so fat5_rpe cannot carry it")
         if self.attention_type == "fat5_rpe" and (self.position_encoding_type not in ("t5", "RoPE") or self.use_masking):
             raise ValueError("fat5_rpe needs the T5 relative-position encoding or RoPE, and no key masking (use var-len batches)")
+        # LongT5's local encoder self-attention: |n - m| <= local_radius (decoder self- and cross-attention stay full)
+        self.window = None
+        if _cfg(config, "encoder_attention_type", "full") == "local":
+            if self.attention_type != "fat5_rpe" or self.position_encoding_type not in ("t5", "RoPE") or self.key_value_proj_dim != 64:
+                raise ValueError("encoder_attention_type='local' needs attention_type='fat5_rpe', position_encoding_type 't5' or 'RoPE' "
+                                 "and d_kv = 64")
+            if not self.is_decoder:
+                self.window = int(_cfg(config, "local_radius", 127))
+                if self.window < 1:
+                    raise ValueError(f"local_radius = {self.window} must be at least 1")
+        elif _cfg(config, "encoder_attention_type", "full") != "full":
+            raise ValueError(f"encoder_attention_type {_cfg(config, 'encoder_attention_type', None)!r}: 'full' or 'local'")
         self.pe_encoding = None
         self._randomized = bool(_cfg(config, "use_randomized_position_encoding", False))  # (decode time: forward_decode refuses it)
         self.rotary = self.position_encoding_type == "RoPE"
@@ -248,7 +260,8 @@ class FlashT5Attention(nn.Module):
                 raise ValueError("fat5_rpe self-attention without a bias producer needs position_bias=(rpe1d, radius) from the "
                                  "block that owns the RelativePositionalEncoding")
             rpe1d, radius = position_bias
-        out = flash_attn_varlen_func(q, k, v, cu, kv_cu, mx, kv_mx, self.is_causal and is_self, self.softmax_scale, rpe1d, radius)
+        out = flash_attn_varlen_func(q, k, v, cu, kv_cu, mx, kv_mx, self.is_causal and is_self, self.softmax_scale, rpe1d, radius,
+                                     window=self.window if is_self else None)
         return out.reshape(1, q.shape[0], self.inner_dim), position_bias
 
     def decode_supported(self):
@@ -358,8 +371,12 @@ class FlashT5Attention(nn.Module):
         """attention of projected (B, H, S, D) views -> (B, M, inner_dim), plus the position bias to hand on"""
         B, _, M, _ = q.shape
         N = k.shape[2]
+        window = self.window if is_self else None
         if self.rotary and position_bias is None:  # (q, k, v already rotated: no bias, and none handed on)
-            out = flash_attention_v2_bias(q, k, v, None, self.is_causal, self.softmax_scale)
+            if window is not None:
+                out = flash_attention_v2_rpe1d(q, k, v, None, 0, self.is_causal, self.softmax_scale, window=window)
+            else:
+                out = flash_attention_v2_bias(q, k, v, None, self.is_causal, self.softmax_scale)
             return out.permute(0, 2, 1, 3).reshape(B, M, self.inner_dim), None
         key_value_states = None if is_self else True
         hidden_dtype = dtype
@@ -376,7 +393,7 @@ class FlashT5Attention(nn.Module):
                 out = flash_attention_v2_bias(q, k, v, None, self.is_causal, self.softmax_scale)
             else:
                 rpe1d, radius = position_bias
-                out = flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, self.is_causal, self.softmax_scale)
+                out = flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, self.is_causal, self.softmax_scale, window=window)
         else:
             if position_bias is None and isinstance(self.pe_encoding, FIRE):  # (the reference's FIRE.forward: (1, H, S, S), S = M)
                 # (no .contiguous(): when S is not a multiple of 8 the bias rows are padded to 16 bytes, which the kernels take as is)

@@ -74,8 +74,20 @@ class FAT5Config:
     num_labels: int = 2                    # the encoder-only heads (heads.py): classes of the classifiers; the QA head needs 2
     classifier_dropout: float = 0.0        # the heads' own dropout sites (training only)
     eos_token_id: int = 1                  # FAT5ForSequenceClassification pools the row of the last <eos>
+    encoder_attention_type: str = "full"   # "local": LongT5's sliding-window encoder self-attention (HF LongT5's names)
+    local_radius: int = 127                # ... key n visible to row m iff |n - m| <= local_radius
 
     def __post_init__(self):
+        if self.encoder_attention_type not in ("full", "local"):
+            raise ValueError(f"encoder_attention_type {self.encoder_attention_type!r}: 'full' or 'local'")
+        if self.encoder_attention_type == "local":
+            if self.attention_type != "fat5_rpe" or self.position_encoding_type not in ("t5", "RoPE"):
+                raise ValueError("encoder_attention_type='local' needs attention_type='fat5_rpe' with position_encoding_type 't5' or "
+                                 "'RoPE': the local kernels carry the T5 generator or no bias, never a dense one")
+            if self.d_kv != 64:
+                raise ValueError(f"encoder_attention_type='local' needs d_kv = 64, got {self.d_kv}")
+            if int(self.local_radius) < 1:
+                raise ValueError(f"local_radius = {self.local_radius} must be at least 1")
         if self.position_encoding_type == "FIRE" and self.attention_type == "fat5_rpe":
             raise ValueError("position_encoding_type='FIRE' needs attention_type='triton' (dense bias): FIRE's bias is not "
                              "Toeplitz once a row passes the threshold T, so fat5_rpe cannot carry it")

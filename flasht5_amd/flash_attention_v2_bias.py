@@ -385,11 +385,21 @@ class FlashAttentionRPE(torch.autograd.Function):
 
 
 def flash_attention_v2_rpe(q, k, v, rpe_table, bidirectional=True, num_buckets=32, max_distance=128,
-                           causal=False, sm_scale=None):
+                           causal=False, sm_scale=None, window=None):
     """Attention with the T5 relative-position bias generated in-kernel from the `(num_buckets, H)` table
     (`RelativePositionalEncoding.relative_attention_bias.weight` of the reference).  Equivalent to
     `flash_attention_v2_bias(q, k, v, compute_bias(table, M, N), ...)` with O(S) memory; differentiable in
-    q, k, v and the table."""
+    q, k, v and the table.  window: local attention as in `flash_attention_v2_rpe1d`; the generator is then gathered from
+    the table with torch ops, whose backward scatters its gradient into the table."""
+    if window is not None:
+        _check_inputs(q, k, v)
+        window = _check_local(q, k, v, window, causal)
+        R = _pe.rpe_radius(max_distance)
+        if rpe_table.shape != (num_buckets, q.shape[1]):
+            raise ValueError("rpe_table must be (num_buckets, n_heads)")
+        idx = _pe.bucket_index(R, bidirectional, num_buckets, max_distance, rpe_table.device)
+        rpe1d = rpe_table.index_select(0, idx).transpose(0, 1)
+        return FlashAttentionLocal.apply(q, k, v, rpe1d, R, window, sm_scale, None, None)
     nat = None if _tracing() else _lib.native()
     if nat is None:
         return FlashAttentionRPE.apply(q, k, v, rpe_table, bidirectional, num_buckets, max_distance, causal, sm_scale)
@@ -441,8 +451,14 @@ class FlashAttentionRPE1D(torch.autograd.Function):
         return dq, dk, dv, (d1.to(rdtype) if d1 is not None else None), None, None, None
 
 
-def flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, causal=False, sm_scale=None):
-    """Attention with the Toeplitz bias generated in-kernel from `rpe1d (H, 2*radius+1)` (see FlashAttentionRPE1D)."""
+def flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, causal=False, sm_scale=None, window=None):
+    """Attention with the Toeplitz bias generated in-kernel from `rpe1d (H, 2*radius+1)` (see FlashAttentionRPE1D).
+    window: None, or w >= 1 for local attention -- key n visible to row m iff |n - m| <= w (self-attention, head_dim 64, not
+    causal; `FlashAttentionLocal`).  With a window, rpe1d may be None: no bias."""
+    if window is not None:
+        _check_inputs(q, k, v)
+        window = _check_local(q, k, v, window, causal)
+        return FlashAttentionLocal.apply(q, k, v, rpe1d, int(radius), window, sm_scale, None, None)
     nat = None if _tracing() else _lib.native()
     if nat is None:
         return FlashAttentionRPE1D.apply(q, k, v, rpe1d, int(radius), causal, sm_scale)
@@ -634,11 +650,128 @@ class FlashAttentionVarlen(torch.autograd.Function):
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=False, sm_scale=None,
-                           rpe1d=None, radius=0):
+                           rpe1d=None, radius=0, window=None):
     """Differentiable packed attention (argument order of the flash_attn var-len entry point the reference's `fa2`
-    attention types would call), optionally with the in-kernel T5 bias of `flash_attention_v2_rpe1d`."""
+    attention types would call), optionally with the in-kernel T5 bias of `flash_attention_v2_rpe1d`.
+    window: None, or w >= 1 for local attention inside each sequence (self-attention, head_dim 64, not causal).  The local
+    kernel reads cu_seqlens_q only: cu_seqlens_k / max_seqlen_k must be the query's."""
+    if window is not None:
+        if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+            raise ValueError("packed attention takes q (total_q, H, D) and k, v (total_k, H, D)")
+        window = _check_local(q, k, v, window, causal, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+        cu = _as_cu(cu_seqlens_q, q.device)
+        if cu.dim() != 1 or cu.numel() < 2:
+            raise ValueError("cu_seqlens_q must have (number of sequences + 1) entries")
+        return FlashAttentionLocal.apply(q, k, v, rpe1d, int(radius), window, sm_scale, cu, int(max_seqlen_q))
     return FlashAttentionVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, sm_scale,
                                       rpe1d, int(radius))
+
+
+# ------------------------------------------------------------------------------------------------
+# local (sliding-window) attention: LongT5's encoder attention, O(S * window) work (csrc/local_attn_kernels.h)
+# ------------------------------------------------------------------------------------------------
+def _check_local(q, k, v, window, causal, cu_q=None, cu_k=None, max_q=None, max_k=None):
+    """host rejections of the windowed path (ValueError, before anything is launched); returns the window as an int"""
+    if causal:
+        raise ValueError("window= is LongT5's two-sided local attention: causal=True is not supported")
+    if tuple(k.shape) != tuple(q.shape) or tuple(v.shape) != tuple(q.shape):
+        raise ValueError(f"window= is self-attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must agree")
+    if q.shape[-1] != 64:
+        raise ValueError(f"window= needs head_dim 64, got {q.shape[-1]}")
+    if int(window) != window or int(window) < 1:
+        raise ValueError(f"window = {window!r} must be an integer >= 1")
+    if cu_q is not None:
+        # the kernel reads cu_seqlens_q only: the key side must be the very same sequences
+        same = cu_k is cu_q or (cu_k.data_ptr() == cu_q.data_ptr() and cu_k.numel() == cu_q.numel() and cu_k.dtype == cu_q.dtype)
+        if not same or int(max_k) != int(max_q):
+            raise ValueError("window= is self-attention: cu_seqlens_k / max_seqlen_k must be the query's")
+    return int(window)
+
+
+def _local_params(ts, names, window, sm_scale, r1, radius, cu, max_seqlen):
+    q = ts[0]
+    p = _lib.LocalAttnParams()
+    if cu is None:
+        p.B, p.H, p.S, p.D = q.shape
+        strides = _lib.strides3
+    else:
+        p.B, p.H, p.S, p.D, p.total = cu.numel() - 1, q.shape[1], int(max_seqlen), q.shape[2], q.shape[0]
+        p.cu_seqlens = cu.data_ptr()
+        strides = lambda t: _lib.c_i64x3(0, t.stride(1), t.stride(0))
+    p.dtype, p.window, p.sm_scale = _lib.dtype_code(q.dtype), window, float(sm_scale)
+    for name, t in zip(names, ts):
+        setattr(p, name, t.data_ptr())
+        setattr(p, ("do" if name == "dout" else name) + "_stride", strides(t))
+    if r1 is not None:
+        p.bias_mode, p.rpe1d, p.rpe_radius = _lib.BIAS_RPE1D, r1.data_ptr(), int(radius)
+    return p
+
+
+def _local_ready(t, packed):
+    return t if (_varlen_ok(t) if packed else _lib.kernel_ready(t)) else t.contiguous()
+
+
+def _local_like(t):
+    e = torch.empty_like(t)
+    return e if _lib.kernel_ready(e) else torch.empty(t.shape, dtype=t.dtype, device=t.device)
+
+
+class FlashAttentionLocal(torch.autograd.Function):
+    """Local attention over the ctypes ABI (`fat5_attn_local_fwd` / `_bwd`), dense (B, H, S, D) views or packed (total, H, D)
+    tensors with `cu_seqlens`; differentiable in q, k, v and rpe1d (None: no bias).  Eager and HIP-graph capture; the C++
+    binding and the traced custom ops do not carry a window."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rpe1d, radius, window, sm_scale, cu, max_seqlen):
+        packed = cu is not None
+        if not q.is_cuda:
+            raise RuntimeError("flasht5_amd attention needs tensors on the HIP device (no CPU fallback)")
+        if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+            raise TypeError("q, k, v must share dtype float16 or bfloat16")
+        if sm_scale is None:
+            sm_scale = 1.0 / math.sqrt(q.shape[-1])
+        H = q.shape[1]
+        r1 = None
+        if rpe1d is not None:
+            if radius > _lib.MAX_RPE_RADIUS:
+                raise ValueError(f"radius {radius} exceeds the RPE-mode limit {_lib.MAX_RPE_RADIUS}")
+            r1 = rpe1d.detach().float().contiguous()
+            _check_rpe1d(r1, H, radius, q.device)
+        q, k, v = (_local_ready(t, packed) for t in (q, k, v))
+        o = _local_like(q)
+        lse = torch.empty((H, q.shape[0]) if packed else (q.shape[0], H, q.shape[2]), dtype=torch.float32, device=q.device)
+        p = _local_params((q, k, v, o), ("q", "k", "v", "o"), window, sm_scale, r1, radius, cu, max_seqlen)
+        p.lse = lse.data_ptr()
+        with _lib.on_device(q.device):
+            _lib.check(_lib.load().fat5_attn_local_fwd(ctypes.byref(p), _lib.stream_ptr(q.device)), "fat5_attn_local_fwd")
+        ctx.save_for_backward(q, k, v, o, lse, *([cu] if packed else []), *([r1] if r1 is not None else []))
+        ctx.meta = (packed, r1 is not None, int(radius), window, sm_scale, max_seqlen, rpe1d.dtype if rpe1d is not None else None)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        packed, has_bias, radius, window, sm_scale, max_seqlen, rdtype = ctx.meta
+        q, k, v, o, lse, *rest = ctx.saved_tensors
+        cu = rest.pop(0) if packed else None
+        r1 = rest.pop(0) if has_bias else None
+        do = _local_ready(do, packed)
+        if not packed and packed_slices((q, k, v)):  # gradients of one stacked projection: slices of one buffer
+            dq, dk, dv = empty_packed_like((q, k, v))
+        else:
+            dq, dk, dv = _local_like(q), _local_like(k), _local_like(v)
+        p = _local_params((q, k, v, o, do, dq, dk, dv), ("q", "k", "v", "o", "dout", "dq", "dk", "dv"), window, sm_scale, r1, radius,
+                          cu, max_seqlen)
+        p.lse = lse.data_ptr()
+        d1 = None
+        if has_bias and ctx.needs_input_grad[3]:
+            d1 = torch.empty_like(r1)
+            p.drpe1d = d1.data_ptr()
+        lib = _lib.load()
+        with _lib.on_device(q.device):
+            ws = _workspace(lib.fat5_attn_local_bwd_workspace_bytes(ctypes.byref(p)), q.device)
+            p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+            _lib.check(lib.fat5_attn_local_bwd(ctypes.byref(p), _lib.stream_ptr(q.device)), "fat5_attn_local_bwd")
+        return dq, dk, dv, (d1.to(rdtype) if d1 is not None else None), None, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------

@@ -211,7 +211,7 @@ def _packed_encoder(stack, input_ids, pad):
             if bias is None:
                 bias = att.pe_encoding.forward_1d()   # (block 0 owns the generator; the others are handed it)
             rpe1d, radius = bias
-        o = flash_attn_varlen_func(q, k, v, cu, cu, mx, mx, False, att.softmax_scale, rpe1d, radius)
+        o = flash_attn_varlen_func(q, k, v, cu, cu, mx, mx, False, att.softmax_scale, rpe1d, radius, window=att.window)
         h = h + att.o(o.reshape(1, total, att.inner_dim))
         h = blk.ff_layer(h)
     h = stack.final_layer_norm(h)

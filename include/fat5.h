@@ -1489,6 +1489,64 @@ int fat5_adafactor_step(const fat5_adafactor_tensor* host_table, const fat5_adaf
                         double weight_decay, int scale_parameter, int dtype, int grad_dtype, const float* dev_scalars,
                         void* hip_stream);
 
+/*
+ * Local (sliding-window) self-attention with the T5 bias -- LongT5's encoder attention, in time and memory linear in S.
+ *
+ *   o[m] = softmax_n( q[m] . k[n] * sm_scale + bias[h][m][n] ) v[n]   over the keys n with |n - m| <= window inside the sequence;
+ *   bias: FAT5_BIAS_NONE, or FAT5_BIAS_RPE1D with the rule of the full kernels, rpe1d[h][clamp(n - m, -R, R) + R] -- only the
+ *   entries |d| <= window are ever read.  lse: natural log, fp32.  No causal mode, no dense bias, no dropout.
+ *
+ * Self-attention only: q, k, v hold the same S tokens; D = 64; FAT5_F16 / FAT5_BF16 with fp32 accumulation.
+ * Dense layout (cu_seqlens NULL): (B, H, S, D) views with element strides [b, h, s], innermost stride 1 (the (B, S, H, D) storage
+ * of a projection included); lse is (B, H, S) contiguous.  Packed layout: (total, H, D) tensors, cu_seqlens (B + 1,) int32 in device
+ * memory, S the LONGEST sequence; token s of sequence b sits at (cu_seqlens[b] + s) * stride[2] + h * stride[1] (stride[0] ignored),
+ * positions are local to each sequence, lse is (H, total).  The one cu_seqlens serves queries and keys.  A window of S - 1 or more
+ * is full attention.
+ *
+ * Backward: dq, dk, dv in the layouts of q, k, v; drpe1d (H, 2R+1) fp32, overwritten (may be NULL): the sum over b and m of
+ * dS[m][m + d] for |d| <= window at entry d + R, zeros beyond the window, the clamp ends +-R collecting |d| >= R when
+ * window > R.  No atomics: the same bits on every run.  The workspace (16-byte aligned, the size the query below answers) holds
+ * delta and the per-workgroup partial diagonal sums.
+ *
+ * Rejected with FAT5_EINVAL before anything is launched: NULL params, D other than 64, a dtype outside {FAT5_F16, FAT5_BF16},
+ * window < 1, B or H outside [1, 65535], S outside [1, 2^30), a bias_mode other than the two above, rpe_radius outside
+ * [1, 1024], a packed batch without tokens, NULL or misaligned pointers, strides that are no multiples of 8 elements;
+ * FAT5_EWORKSPACE when the workspace is missing, misaligned or too small.
+ */
+typedef struct fat5_local_attn_params {
+  int32_t B, H, S, D;
+  int32_t dtype;            /* FAT5_F16 | FAT5_BF16: q, k, v, o, dout, dq, dk, dv */
+  int32_t bias_mode;        /* FAT5_BIAS_NONE | FAT5_BIAS_RPE1D */
+  int32_t window;           /* >= 1 */
+  int32_t rpe_radius;       /* R of FAT5_BIAS_RPE1D: 1..1024 */
+  float sm_scale;
+  int32_t total;            /* packed: tokens of the batch */
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  float* lse;
+  int64_t q_stride[3], k_stride[3], v_stride[3], o_stride[3];
+  const float* rpe1d;       /* (H, 2R+1) fp32 contiguous */
+  const int32_t* cu_seqlens; /* packed: (B + 1,) int32 on the device; NULL: dense */
+  /* ---- backward (ignored by the forward) ---- */
+  const void* dout;
+  void* dq;
+  void* dk;
+  void* dv;
+  int64_t do_stride[3], dq_stride[3], dk_stride[3], dv_stride[3];
+  float* drpe1d;
+  void* workspace;
+  size_t workspace_bytes;
+} fat5_local_attn_params;
+size_t fat5_sizeof_local_attn_params(void);
+/* forward: writes o, lse */
+int fat5_attn_local_fwd(const fat5_local_attn_params* p, void* hip_stream);
+size_t fat5_attn_local_bwd_workspace_bytes(const fat5_local_attn_params* p);
+/* backward: reads q, k, v, o, lse, dout (, rpe1d); writes dq, dk, dv (, drpe1d).  Three launches: dQ with delta and the partial
+ * diagonal sums, dK / dV, and the fixed-order sum of the partial rows. */
+int fat5_attn_local_bwd(const fat5_local_attn_params* p, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
