@@ -17,7 +17,9 @@ every self-attention cache and incremented on the device at the end of each step
 How the modes below share code: `_decoder_blocks` is the one pass through the decoder blocks (`decode_step` and `decode_chunk`
 add their own checks, length increment and head), `_step` is `decode_step` + `_pick` (processors, argmax or sampler, bookkeeping),
 `_run_steps` is the one eager / capture / replay loop -- greedy, sampled, beam and speculative decoding hand it their step and
-their stop predicate -- and `_prefill_prompt` is the one decoder-prompt prefill.
+their stop predicate -- and `_prefill_prompt` is the one decoder-prompt prefill.  On the encoder's side `_padded_encoder` is the
+one pass of a padded batch (the packed rows or the masked dense bias): `encode` hands it the stack's runner, the 16-bit block
+loop (`_encoder_blocks`) or the MXFP4 one (w4a8.encoder_forward_mxfp4), so an attention feature of the blocks reaches both.
 
 Sampling (`do_sample=True`) replaces the argmax by `sample_logits` (one HIP launch: temperature, top-k, top-p and a Philox draw
 keyed by the call's seed with the token's position, cache_seqlens, as the counter), so it is captured and replayed the same way.
@@ -45,7 +47,7 @@ With `prompt_lookup_num_tokens` (flasht5_amd/prompt_lookup.py) the 
 searches input_ids and the row's own sequence for the row's last n-gram and proposes what followed it; the same rounds otherwise.
 
 Padding (`attention_mask`, `decoder_attention_mask`): right-padded masks are validated with one host read before an
-encoder runs (`check_padding`).  The encoder then sees only each row's valid keys (packed through `flash_attn_varlen_func` under
+encoder runs (`check_padding`).  The encoder then sees only each row's valid keys (`_padded_encoder`: packed rows under
 fat5_rpe and RoPE, the mask folded into the dense bias otherwise), every cross-attention launch gets the row's encoder length as
 its `cache_seqlens`, and a ragged decoder prompt is prefilled by one chunk step with per-row `chunk_seqlens`.  All-ones masks and
 None take the code path above.
@@ -61,6 +63,7 @@ MXFP4 weights (`weight_dtype="mxfp4"`): the same pass over e2m1 nib
 projection one `w4_linear` launch.
 """
 from dataclasses import dataclass
+from functools import partial
 from typing import List, Optional, Tuple
 
 import torch
@@ -183,98 +186,65 @@ def check_padding(input_ids, attention_mask=None, decoder_input_ids=None, decode
     return out["attention_mask"], out["decoder_attention_mask"]
 
 
-def _packed_encoder(stack, input_ids, pad):
-    """the encoder stack over the valid tokens only (fat5_rpe and RoPE): unpad with indices built from the host lengths, every
-    self-attention through flash_attn_varlen_func (the T5 generator or rotated q / k / v, positions local to each row), then the
-    rows scattered back into a zero (B, L, d_model) tensor"""
-    from .flash_attention_v2_bias import flash_attn_varlen_func
-    from .rotary import apply_rotary_emb_qkv
-    B, L = input_ids.shape
-    dev = input_ids.device
-    lens = pad.lengths
-    idx = torch.cat([torch.arange(n) + b * L for b, n in enumerate(lens)]).to(dev)
-    cu = torch.tensor([0] + [sum(lens[:b + 1]) for b in range(B)], dtype=torch.int32).to(dev)
-    mx, total = max(lens), sum(lens)
-    h = _embed(stack.embed_tokens, input_ids.reshape(-1).index_select(0, idx).unsqueeze(0))   # (1, total, d_model)
-    bias = None
+def _encoder_blocks(stack, ids, packing=None, position_bias=None):
+    """the 16-bit runner of `_padded_encoder`: the encoder stack's plain block loop over `ids` -- (1, total) valid tokens with a
+    `Packed` (every self-attention through FlashT5Attention._forward_packed), or (B, L) under a dense `position_bias` handed to
+    every block.  Not `stack.forward`: the padded encoders have always run the plain path whatever fuse_add_norm /
+    fuse_norm_linear say, and their bits stay what they were"""
+    h = _embed(stack.embed_tokens, ids)
     for blk in stack.block:
-        sa = blk.self_attention_layer
-        att = sa.self_attention
-        H, D = att.n_heads, att.key_value_proj_dim
-        n = sa.layer_norm(h)
-        q, k, v = (w(n).view(total, H, D) for w in (att.Wq, att.Wk, att.Wv))
-        rpe1d, radius = None, 0
-        if att.rotary:
-            cos, sin, cos_k, sin_k = att.pe_encoding.tables(q.device, q.dtype)
-            q, k, v = apply_rotary_emb_qkv(q, k, v, cos, sin, cos_k, sin_k, att.pe_encoding.interleaved, cu_seqlens=cu, max_seqlen=mx)
-        else:
-            if bias is None:
-                bias = att.pe_encoding.forward_1d()   # (block 0 owns the generator; the others are handed it)
-            rpe1d, radius = bias
-        o = flash_attn_varlen_func(q, k, v, cu, cu, mx, mx, False, att.softmax_scale, rpe1d, radius, window=att.window)
-        h = h + att.o(o.reshape(1, total, att.inner_dim))
-        h = blk.ff_layer(h)
-    h = stack.final_layer_norm(h)
-    enc = h.new_zeros((B * L, h.shape[-1]))
-    enc.index_copy_(0, idx, h[0])
-    return enc.view(B, L, -1)
+        h, position_bias = blk(h, position_bias, None, packing)
+    return stack.final_layer_norm(h)
 
 
-def _masked_bias_encoder(stack, input_ids, pad):
-    """the encoder stack under the dense-bias type: block 0's (1, H, L, L) bias with the padded key columns at the dtype's minimum,
-    as FlashT5Attention folds a mask in under use_masking, handed to every block; the padded rows of the result are zeroed"""
+def _padded_encoder(stack, input_ids, pad, run, dtype):
+    """The one pass of a right-padded batch through an encoder stack -> (B, L, d_model), zeros at the padded rows.
+    `run(ids, packing=None, position_bias=None)` runs the stack (`_encoder_blocks`, or w4a8.encoder_forward_mxfp4 bound to its
+    weights) on activations of `dtype`.  fat5_rpe and RoPE: the valid tokens only, gathered with indices built from the host
+    lengths and run packed (the T5 generator or rotated q / k / v, positions local to each row), then scattered back.  The dense
+    T5 bias: block 0's (1, H, L, L) bias with the padded key columns at the dtype's minimum, as FlashT5Attention folds a mask in
+    under use_masking, handed to every block; the padded rows of the result are zeroed"""
     B, L = input_ids.shape
-    h = _embed(stack.embed_tokens, input_ids)
     att = stack.block[0].self_attention_layer.self_attention
-    bias = att.pe_encoding.compute_bias(L, L, device=h.device).to(h.dtype)
-    bias = torch.where(pad.mask.view(B, 1, 1, L), bias, torch.finfo(h.dtype).min).contiguous()
-    for blk in stack.block:
-        h, bias = blk(h, bias, None)
-    return stack.final_layer_norm(h).masked_fill(~pad.mask.unsqueeze(-1), 0)
-
-
-def encode(model, input_ids, pad=None, encoder_weight_dtype=None):
-    """the encoder's output (B, L, d_model); with a `Padding`, every row's self-attention sees its own valid keys only and the
-    padded rows come back as zeros.  encoder_weight_dtype="mxfp4" (DESIGN 4.28): the stack over the model's MXFP4 encoder weights
-    (`quantize_encoder_weights_mxfp4`) through `w4a8_linear`; None: the code below as it always ran"""
-    if encoder_weight_dtype is not None:
-        return _encode_mxfp4(model, input_ids, pad, encoder_weight_dtype)
-    if pad is None:
-        return model.encoder(input_ids)
-    att = model.encoder.block[0].self_attention_layer.self_attention
     if att.rotary or att.attention_type == "fat5_rpe":
-        return _packed_encoder(model.encoder, input_ids, pad)
-    if att.position_encoding_type != "t5":
-        raise NotImplementedError(f"attention_mask with position_encoding_type {att.position_encoding_type!r}")
-    return _masked_bias_encoder(model.encoder, input_ids, pad)
-
-
-def _encode_mxfp4(model, input_ids, pad, encoder_weight_dtype, what="generate"):
-    """`encode` over the MXFP4 encoder weights: the three paths above (unpadded, packed rows, masked dense bias) with every
-    projection a `w4a8_linear` (w4a8.encoder_forward_mxfp4); the host checks come before anything runs"""
-    from .packing import Packed
-    from .w4a8 import check_encoder_weight_dtype, encoder_forward_mxfp4, encoder_weights_mxfp4
-    check_encoder_weight_dtype(encoder_weight_dtype, what)
-    weights = encoder_weights_mxfp4(model, what)
-    stack = model.encoder
-    if pad is None:
-        return encoder_forward_mxfp4(stack, weights, input_ids)
-    B, L = input_ids.shape
-    att = stack.block[0].self_attention_layer.self_attention
-    if att.rotary or att.attention_type == "fat5_rpe":   # (_packed_encoder's indices)
+        from .packing import Packed
         lens, dev = pad.lengths, input_ids.device
         idx = torch.cat([torch.arange(n) + b * L for b, n in enumerate(lens)]).to(dev)
         cu = torch.tensor([0] + [sum(lens[:b + 1]) for b in range(B)], dtype=torch.int32).to(dev)
-        h = encoder_forward_mxfp4(stack, weights, input_ids.reshape(-1).index_select(0, idx).unsqueeze(0), packing=Packed(cu, max(lens)))
+        h = run(input_ids.reshape(-1).index_select(0, idx).unsqueeze(0), packing=Packed(cu, max(lens)))   # (1, total, d_model)
         enc = h.new_zeros((B * L, h.shape[-1]))
         enc.index_copy_(0, idx, h[0])
         return enc.view(B, L, -1)
     if att.position_encoding_type != "t5":
         raise NotImplementedError(f"attention_mask with position_encoding_type {att.position_encoding_type!r}")
-    dtype = stack.embed_tokens.weight.dtype
-    bias = att.pe_encoding.compute_bias(L, L, device=input_ids.device).to(dtype)   # (_masked_bias_encoder's bias)
+    bias = att.pe_encoding.compute_bias(L, L, device=input_ids.device).to(dtype)
     bias = torch.where(pad.mask.view(B, 1, 1, L), bias, torch.finfo(dtype).min).contiguous()
-    return encoder_forward_mxfp4(stack, weights, input_ids, position_bias=bias).masked_fill(~pad.mask.unsqueeze(-1), 0)
+    return run(input_ids, position_bias=bias).masked_fill(~pad.mask.unsqueeze(-1), 0)
+
+
+def encode(model, input_ids, pad=None, encoder_weight_dtype=None):
+    """the encoder's output (B, L, d_model); with a `Padding`, every row's self-attention sees its own valid keys only and the
+    padded rows come back as zeros (`_padded_encoder`).  encoder_weight_dtype="mxfp4" (DESIGN 4.28): the stack over the model's
+    MXFP4 encoder weights (`quantize_encoder_weights_mxfp4`) through `w4a8_linear`, checked on the host before anything runs;
+    None: the 16-bit stack as it always ran"""
+    stack = model.encoder
+    dtype = stack.embed_tokens.weight.dtype
+    if encoder_weight_dtype is None:
+        if pad is None:
+            return stack(input_ids)
+        run = partial(_encoder_blocks, stack)
+        if torch.is_autocast_enabled() and input_ids.is_cuda:   # (`_embed`'s rule; the MXFP4 stack keeps the weights' dtype)
+            dtype = torch.get_autocast_dtype("cuda")
+    else:
+        from . import w4a8
+        w4a8.check_encoder_weight_dtype(encoder_weight_dtype, "generate")
+        weights = w4a8.encoder_weights_mxfp4(model, "generate")
+
+        def run(ids, **kw):   # (the entry point is looked up per call: it can be wrapped)
+            return w4a8.encoder_forward_mxfp4(stack, weights, ids, **kw)
+        if pad is None:
+            return run(input_ids)
+    return _padded_encoder(stack, input_ids, pad, run, dtype)
 
 
 @torch.no_grad()
@@ -466,14 +436,9 @@ def decode_step(model, state, token_ids):
         raise ValueError(f"decode_step: the caches hold {state.capacity} positions and all of them are used (init_decode_state with a "
                          "larger max_length)")
     state.steps += 1
-    if state.w8 is not None:
-        h = _decoder_blocks_w8(model, state, _embed(model.shared, token_ids.reshape(B, 1)))
-        state.cache_seqlens.add_(1)
-        return _head(model, state, h)[:, 0]
-    h = _decoder_blocks(model, state, _embed(model.shared, token_ids.reshape(B, 1)))
-    h = model.decoder.final_layer_norm(h)
+    h = _blocks(model, state, _embed(model.shared, token_ids.reshape(B, 1)))
     state.cache_seqlens.add_(1)
-    return model.lm_head(h)[:, 0]
+    return _head(model, state, h)[:, 0]
 
 
 @torch.no_grad()

@@ -19,6 +19,7 @@ positions into both); logits at padding are 0, or the dtype's minimum for QA (th
 there); a sequence without an <eos> is pooled from its last token and flagged -- `FAT5ForSequenceClassification.check` is the
 optional host read that raises for it -- where the reference raises inside every forward."""
 import copy
+from functools import partial
 
 import torch
 import torch.distributed as dist
@@ -127,37 +128,28 @@ class _EncoderOnly(nn.Module):
         from .w4a8 import quantize_encoder_weights_mxfp4
         return quantize_encoder_weights_mxfp4(self)
 
-    def _encode_mxfp4(self, input_ids, attention_mask):
-        """`_encode` over the MXFP4 encoder weights: inference only, checked on the host before anything runs"""
-        from .packing import Packed
-        from .w4a8 import encoder_forward_mxfp4, encoder_weights_mxfp4
-        weights = encoder_weights_mxfp4(self, "forward")
-        plan = self._plan(input_ids, attention_mask)
-        B, L = input_ids.shape
-        if plan is None:
-            ids = input_ids.reshape(-1)
-            h = encoder_forward_mxfp4(self.encoder, weights, input_ids)
-        else:
-            ids = input_ids.reshape(-1).index_select(0, plan.index)
-            h = encoder_forward_mxfp4(self.encoder, weights, ids.unsqueeze(0), packing=Packed(plan.cu_seqlens, plan.max_seqlen))
-        return _Rows(h.reshape(-1, h.shape[-1]), ids, plan, B, L), None
-
     def _encode(self, input_ids, attention_mask, weight_dtype=None):
-        """-> (_Rows, the head's dropout context); weight_dtype="mxfp4": the encoder over its MXFP4 weights"""
-        if weight_dtype is not None:
-            from .w4a8 import check_encoder_weight_dtype
-            check_encoder_weight_dtype(weight_dtype, "forward")
-            return self._encode_mxfp4(input_ids, attention_mask)
+        """-> (_Rows, the head's dropout context); weight_dtype="mxfp4": the encoder over its MXFP4 weights, inference
+        only and without dropout, checked on the host before `_plan` reads the mask"""
         from .packing import Packed
+        if weight_dtype is not None:
+            from . import w4a8
+            w4a8.check_encoder_weight_dtype(weight_dtype, "forward")
+            weights = w4a8.encoder_weights_mxfp4(self, "forward")
         plan = self._plan(input_ids, attention_mask)
-        drop, head_drop = self._drops()
+        if weight_dtype is None:
+            drop, head_drop = self._drops()
+            run = partial(self.encoder, drop=drop)
+        else:   # (no `_drops()`: the step counter does not advance here)
+            head_drop = None
+            run = partial(w4a8.encoder_forward_mxfp4, self.encoder, weights)
         B, L = input_ids.shape
         if plan is None:
             ids = input_ids.reshape(-1)
-            h = self.encoder(input_ids, drop=drop)
+            h = run(input_ids)
         else:
             ids = input_ids.reshape(-1).index_select(0, plan.index)
-            h = self.encoder(ids.unsqueeze(0), packing=Packed(plan.cu_seqlens, plan.max_seqlen), drop=drop)
+            h = run(ids.unsqueeze(0), packing=Packed(plan.cu_seqlens, plan.max_seqlen))
         return _Rows(h.reshape(-1, h.shape[-1]), ids, plan, B, L), head_drop
 
     def _head_drop(self, x, drop, k):

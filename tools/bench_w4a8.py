@@ -7,7 +7,8 @@ accepts these row counts), `quantize_activation_mxfp8` alone, `w4a8_matmul` alon
 `encoder_weight_dtype="mxfp4"`.  Every variant is captured in a HIP graph and the graphs are timed in alternating repeats (REPEATS
 blocks of ITERS replays each, device events around a block), so a drift of the clocks hits all alike; reported are the median and
 the spread (min .. max) of the block means.  TFLOP/s counts 2 R K N over the median.  No ratio is asserted: the table says what was
-measured.  Writes profiles/encoder_w4a8_bench.log (or $FAT5_BENCH_LOG) and prints one JSON line at the end."""
+measured.  Writes profiles/encoder_w4a8_bench.log (or $FAT5_BENCH_LOG) and prints one JSON line at the end.
+`--padded` measures instead the padded encoder pass of generation (16-bit and MXFP4) and one padded `generate` call, eagerly."""
 import json
 import os
 import statistics
@@ -39,10 +40,12 @@ def capture(fn):
 
 
 def block(g):
+    """the mean time of ITERS runs of g: a captured graph's replays, or a callable's eager calls"""
+    run = getattr(g, "replay", g)
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
     for _ in range(ITERS):
-        g.replay()
+        run()
     e.record()
     torch.cuda.synchronize()
     return s.elapsed_time(e) / ITERS * 1e-3
@@ -107,6 +110,43 @@ def e2e(say):
     return rows
 
 
+@torch.no_grad()
+def padded(say):
+    """`--padded`: the padded encoder pass of generation and one whole padded `generate`, eagerly (the pass builds its indices from
+    the host lengths with two host-to-device copies, which a graph does not capture): REPEATS alternating blocks of ITERS
+    `generation.encode` calls at B = 8 x 512 with ragged lengths, device events around a block; then REPEATS
+    `generate(graph=True, max_length=32)` calls, a host clock around each call and its synchronise"""
+    import time
+    say("# ms of one eager padded FAT5-base generation.encode at B 8 x 512 (lengths 512 .. 64), median (min..max): 16-bit | mxfp4")
+    torch.manual_seed(0)
+    model = FAT5ForConditionalGeneration(FAT5Config()).bfloat16().cuda().eval()
+    model.quantize_encoder_weights_mxfp4()
+    B = 8
+    ids = torch.randint(2, model.lm_head.weight.shape[0], (B, L_ENC), device="cuda")
+    lens = torch.tensor([L_ENC - 64 * b for b in range(B)], device="cuda")
+    mask = torch.arange(L_ENC, device="cuda").unsqueeze(0) < lens.unsqueeze(1)
+    pad, _ = generation.check_padding(ids, mask)
+
+    calls = [lambda: generation.encode(model, ids, pad), lambda: generation.encode(model, ids, pad, "mxfp4")]
+    for fn in calls:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    t16, t4 = alternate(calls)
+    say(f"  B {B:3d} | default {fmt(t16, 1e3)} | mxfp4 {fmt(t4, 1e3)}")
+    gen = []
+    for i in range(REPEATS + 1):   # (the first call is the warm-up)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = model.generate(ids, attention_mask=mask, max_length=32, graph=True)
+        torch.cuda.synchronize()
+        if i:
+            gen.append(time.perf_counter() - t0)
+    say(f"# ms of one padded generate(graph=True, max_length=32) call, {out.shape[1] - 1} steps: {fmt(gen, 1e3)}")
+    return {"encode_default_ms": round(statistics.median(t16) * 1e3, 4), "encode_mxfp4_ms": round(statistics.median(t4) * 1e3, 4),
+            "generate_ms": round(statistics.median(gen) * 1e3, 4)}
+
+
 def main():
     log = open(os.environ.get("FAT5_BENCH_LOG", os.path.join(ROOT, "profiles", "encoder_w4a8_bench.log")), "w")
 
@@ -116,10 +156,13 @@ def main():
         log.flush()
     say(f"# MXFP4 encoder weights (W4A8); {REPEATS} alternating blocks of {ITERS} graph replays; {torch.cuda.get_device_name(0)}")
     res = {}
-    if "--e2e-only" not in sys.argv:
-        res["kernel"] = kernels(say)
-    if "--kernel-only" not in sys.argv:
-        res["end_to_end"] = e2e(say)
+    if "--padded" in sys.argv:
+        res["padded"] = padded(say)
+    else:
+        if "--e2e-only" not in sys.argv:
+            res["kernel"] = kernels(say)
+        if "--kernel-only" not in sys.argv:
+            res["end_to_end"] = e2e(say)
     log.close()
     print(json.dumps({"encoder_w4a8": res}))
 
