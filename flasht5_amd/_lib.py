@@ -338,7 +338,27 @@ class LocalAttnParams(ctypes.Structure):
     ]
 
 
+class TGlobalAttnParams(ctypes.Structure):
+    """Mirror of `fat5_tglobal_attn_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("S", ctypes.c_int32), ("D", ctypes.c_int32),
+        ("dtype", ctypes.c_int32), ("bias_mode", ctypes.c_int32), ("window", ctypes.c_int32), ("rpe_radius", ctypes.c_int32),
+        ("sm_scale", ctypes.c_float), ("total", ctypes.c_int32),
+        ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("o", ctypes.c_void_p), ("lse", ctypes.c_void_p),
+        ("q_stride", c_i64x3), ("k_stride", c_i64x3), ("v_stride", c_i64x3), ("o_stride", c_i64x3),
+        ("rpe1d", ctypes.c_void_p), ("cu_seqlens", ctypes.c_void_p),
+        ("gk", ctypes.c_void_p), ("gv", ctypes.c_void_p), ("gk_stride", c_i64x3), ("gv_stride", c_i64x3),
+        ("grpe1d", ctypes.c_void_p), ("cu_seqlens_g", ctypes.c_void_p), ("g_radius", ctypes.c_int32), ("total_g", ctypes.c_int32),
+        ("dout", ctypes.c_void_p), ("dq", ctypes.c_void_p), ("dk", ctypes.c_void_p), ("dv", ctypes.c_void_p),
+        ("dgk", ctypes.c_void_p), ("dgv", ctypes.c_void_p),
+        ("do_stride", c_i64x3), ("dq_stride", c_i64x3), ("dk_stride", c_i64x3), ("dv_stride", c_i64x3),
+        ("dgk_stride", c_i64x3), ("dgv_stride", c_i64x3),
+        ("drpe1d", ctypes.c_void_p), ("dgrpe1d", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 EXPORTS = (
+    "fat5_sizeof_tglobal_attn_params", "fat5_attn_tglobal_fwd", "fat5_attn_tglobal_bwd_workspace_bytes", "fat5_attn_tglobal_bwd",
     "fat5_sizeof_local_attn_params", "fat5_attn_local_fwd", "fat5_attn_local_bwd_workspace_bytes", "fat5_attn_local_bwd",
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches", "fat5_attn_bwd_kvres",
     "fat5_attn_bwd_stages", "fat5_attn_describe", "fat5_rpe1d_from_table",
@@ -591,6 +611,15 @@ def load():
     if lib.fat5_sizeof_local_attn_params() != ctypes.sizeof(LocalAttnParams):
         raise ImportError(f"fat5_local_attn_params layout mismatch: library {lib.fat5_sizeof_local_attn_params()} B, "
                           f"binding {ctypes.sizeof(LocalAttnParams)} B")
+    for fn in (lib.fat5_attn_tglobal_fwd, lib.fat5_attn_tglobal_bwd):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(TGlobalAttnParams), ctypes.c_void_p]
+    lib.fat5_attn_tglobal_bwd_workspace_bytes.restype = ctypes.c_size_t
+    lib.fat5_attn_tglobal_bwd_workspace_bytes.argtypes = [ctypes.POINTER(TGlobalAttnParams)]
+    lib.fat5_sizeof_tglobal_attn_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_tglobal_attn_params() != ctypes.sizeof(TGlobalAttnParams):
+        raise ImportError(f"fat5_tglobal_attn_params layout mismatch: library {lib.fat5_sizeof_tglobal_attn_params()} B, "
+                          f"binding {ctypes.sizeof(TGlobalAttnParams)} B")
     lib.fat5_sizeof_attn_params.restype = ctypes.c_size_t
     if lib.fat5_sizeof_attn_params() != ctypes.sizeof(AttnParams):
         raise ImportError(f"fat5_attn_params layout mismatch: library {lib.fat5_sizeof_attn_params()} B, "

@@ -31,6 +31,7 @@ from torch import nn
 
 from .flash_attention_v2_bias import flash_attention_v2_bias, flash_attention_v2_rpe1d
 from .fire import FIRE
+from .modules import FlashT5LayerNorm
 from .positional_encoding import RelativePositionalEncoding
 from .rotary import RotaryPositionalEncoding, apply_rotary_emb, apply_rotary_emb_packed, apply_rotary_emb_qkv
 
@@ -106,17 +107,24 @@ class FlashT5Attention(nn.Module):
         if self.attention_type == "fat5_rpe" and (self.position_encoding_type not in ("t5", "RoPE") or self.use_masking):
             raise ValueError("fat5_rpe needs the T5 relative-position encoding or RoPE, and no key masking (use var-len batches)")
         # LongT5's local encoder self-attention: |n - m| <= local_radius (decoder self- and cross-attention stay full)
+        # "transient-global" (LongT5 TGlobal): the band plus one global key per 16 tokens under the same softmax
         self.window = None
-        if _cfg(config, "encoder_attention_type", "full") == "local":
+        self.tglobal = False
+        enc_type = _cfg(config, "encoder_attention_type", "full")
+        if enc_type in ("local", "transient-global"):
             if self.attention_type != "fat5_rpe" or self.position_encoding_type not in ("t5", "RoPE") or self.key_value_proj_dim != 64:
-                raise ValueError("encoder_attention_type='local' needs attention_type='fat5_rpe', position_encoding_type 't5' or 'RoPE' "
-                                 "and d_kv = 64")
+                raise ValueError(f"encoder_attention_type={enc_type!r} needs attention_type='fat5_rpe', position_encoding_type 't5' or "
+                                 "'RoPE' and d_kv = 64")
+            if enc_type == "transient-global" and self.position_encoding_type != "t5":
+                raise ValueError("encoder_attention_type='transient-global' needs position_encoding_type='t5': the global keys carry "
+                                 "a T5 table over block distances")
             if not self.is_decoder:
                 self.window = int(_cfg(config, "local_radius", 127))
                 if self.window < 1:
                     raise ValueError(f"local_radius = {self.window} must be at least 1")
-        elif _cfg(config, "encoder_attention_type", "full") != "full":
-            raise ValueError(f"encoder_attention_type {_cfg(config, 'encoder_attention_type', None)!r}: 'full' or 'local'")
+                self.tglobal = enc_type == "transient-global"
+        elif enc_type != "full":
+            raise ValueError(f"encoder_attention_type {enc_type!r}: 'full', 'local' or 'transient-global'")
         self.pe_encoding = None
         self._randomized = bool(_cfg(config, "use_randomized_position_encoding", False))  # (decode time: forward_decode refuses it)
         self.rotary = self.position_encoding_type == "RoPE"
@@ -139,6 +147,69 @@ class FlashT5Attention(nn.Module):
         self.Wk = nn.Linear(self.d_model, self.inner_dim, bias=False)
         self.Wv = nn.Linear(self.d_model, self.inner_dim, bias=False)
         self.o = nn.Linear(self.inner_dim, self.d_model, bias=False)
+        if self.tglobal:
+            # HF LongT5's names: the norm of the block aggregates, and (block 0) the table over block distances
+            self.global_input_layer_norm = FlashT5LayerNorm(self.d_model, eps=_cfg(config, "layer_norm_epsilon", 1e-6))
+            self.global_pe_encoding = None
+            if has_positional_encoding:
+                self.global_pe_encoding = RelativePositionalEncoding(
+                    config.relative_attention_num_buckets, config.relative_attention_max_distance, self.n_heads, bidirectional=True)
+
+    def _global_kv(self, x, cu_seqlens=None):
+        """TGlobal's side inputs from the sub-layer's normed input x, dense (B, S, d_model) or packed (1, total, d_model) under
+        cu_seqlens: per sequence of length L the G = L // 16 block aggregates (the L % 16 orphan tokens join the last block),
+        global_input_layer_norm, then this layer's Wk / Wv -> (gk, gv, cu_seqlens_g): dense (B, H, S // 16, D) views and None, or
+        packed (total // 16, H, D) tensors and the (nseq + 1,) int32 offsets.  Device-side index arithmetic only: no host read.
+        A global row gathers its <= 31 tokens into 32 slots (zeros elsewhere) and adds them as a fixed fp32 tree, so a sequence's
+        aggregates have the same bits alone, in a batch and in a packed batch."""
+        dev, dm = x.device, x.shape[-1]
+        if cu_seqlens is None:
+            B, S = x.shape[:2]
+            G = S // 16
+            n = B * G
+            j = torch.arange(n, device=dev)
+            g = j % max(G, 1)
+            start = (j // max(G, 1)) * S + 16 * g
+            count = 16 + (g == G - 1) * (S % 16)
+            cu_g = None
+        else:
+            cu = cu_seqlens.to(torch.int64)
+            lens = cu[1:] - cu[:-1]
+            gs = lens // 16
+            cu_g = torch.cat((gs.new_zeros(1), gs.cumsum(0)))
+            n = x.shape[1] // 16
+            j = torch.arange(n, device=dev)
+            seq = torch.bucketize(j, cu_g[1:], right=True).clamp_(max=lens.numel() - 1)
+            g = j - cu_g[seq]
+            start = cu[seq] + 16 * g
+            count = (16 + (g == gs[seq] - 1) * (lens[seq] % 16)) * (j < cu_g[-1])
+            cu_g = cu_g.to(torch.int32)
+        slot = torch.arange(32, device=dev)
+        used = slot[None, :] < count[:, None]
+        idx = torch.where(used, start[:, None] + slot[None, :], 0)
+        if n == 0:  # no sequence can hold 16 tokens: plain local attention
+            H, Dh = self.n_heads, self.key_value_proj_dim
+            e = x.new_zeros((n, H, Dh) if cu_seqlens is not None else (x.shape[0], H, 0, Dh))
+            return e, e, cu_g
+        rows = x.reshape(-1, dm).index_select(0, idx.reshape(-1)).view(n, 32, dm).float() * used[:, :, None]
+        for half in (16, 8, 4, 2, 1):
+            rows = rows[:, :half] + rows[:, half:]
+        gx = self.global_input_layer_norm(rows[:, 0].to(x.dtype))
+        H, Dh = self.n_heads, self.key_value_proj_dim
+        if cu_seqlens is None:
+            gk, gv = (w(gx).view(B, G, H, Dh).permute(0, 2, 1, 3) for w in (self.Wk, self.Wv))
+        else:
+            gk, gv = (w(gx).view(n, H, Dh) for w in (self.Wk, self.Wv))
+        return gk, gv, cu_g
+
+    def _global_bias(self, position_bias):
+        """block 0's (rpe1d, radius, grpe1d, global radius), built once and handed on to the following blocks"""
+        if position_bias is None and self.pe_encoding is not None and self.global_pe_encoding is not None:
+            position_bias = self.pe_encoding.forward_1d() + self.global_pe_encoding.forward_1d()
+        if position_bias is None or len(position_bias) != 4:
+            raise ValueError("transient-global self-attention without the bias producers needs position_bias=(rpe1d, radius, "
+                             "global rpe1d, global radius) from block 0")
+        return position_bias
 
     def forward(self, hidden_states, mask=None, key_value_states=None, position_bias=None, cu_seqlens=None, max_seqlen=None,
                 kv_cu_seqlens=None, kv_max_seqlen=None):
@@ -157,7 +228,7 @@ class FlashT5Attention(nn.Module):
         if self.rotary and position_bias is None:  # q, k, v in one launch (new tensors: nothing autograd saved is touched)
             q, k, v, _ = self.pe_encoding(q, k, v)
         q, k, v = q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3)
-        out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias)
+        out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias, x=hidden_states)
         return self.o(out), position_bias
 
     def forward_fused(self, hidden_states, norm_weight, eps, mask=None, key_value_states=None, position_bias=None, cu_seqlens=None,
@@ -167,6 +238,12 @@ class FlashT5Attention(nn.Module):
         (`fused_linear.rmsnorm_linear` / `linear_residual`): `hidden_states` is the UN-normalised residual stream,
         `norm_weight` / `eps` the sub-layer's `layer_norm`.  Returns (new residual stream, position_bias)."""
         from .fused_linear import rmsnorm_linear, linear_residual
+        if self.tglobal and key_value_states is None:
+            # the block aggregates need the normed input itself, which the fused projection never materialises: norm explicitly
+            from .rms_norm import fast_rms_layernorm
+            a, position_bias = self.forward(fast_rms_layernorm(hidden_states, norm_weight, eps), mask, None, position_bias, cu_seqlens,
+                                            max_seqlen)
+            return hidden_states + a, position_bias
         B, M = hidden_states.shape[:2]
         H, Dh = self.n_heads, self.key_value_proj_dim
         if cu_seqlens is not None:    # packed rows: the same GEMMs, then (total, H, D) views of their outputs
@@ -233,15 +310,26 @@ class FlashT5Attention(nn.Module):
         k = self.Wk(src).view(src.shape[1], H, Dh)
         v = self.Wv(src).view(src.shape[1], H, Dh)
         out, position_bias = self._attend_packed(q, k, v, key_value_states is None, position_bias, cu_seqlens, max_seqlen,
-                                                 kv_cu_seqlens, kv_max_seqlen)
+                                                 kv_cu_seqlens, kv_max_seqlen, x=hidden_states)
         return self.o(out), position_bias
 
-    def _attend_packed(self, q, k, v, is_self, position_bias, cu, mx, kv_cu, kv_mx):
+    def _attend_packed(self, q, k, v, is_self, position_bias, cu, mx, kv_cu, kv_mx, x=None):
         """packed attention of projected (total, H, D) views -> (1, total_q, inner_dim), plus the position bias to hand on: the T5
-        generator of block 0's forward_1d() in-kernel, or rotated q / k / v and no bias, positions local to each sequence"""
+        generator of block 0's forward_1d() in-kernel, or rotated q / k / v and no bias, positions local to each sequence.
+        x: the sub-layer's normed input (1, total, d_model), which a transient-global layer aggregates its global keys from"""
         from .flash_attention_v2_bias import flash_attn_varlen_func
         if is_self:
             kv_cu, kv_mx = cu, mx
+        if self.tglobal and is_self:
+            if x is None:
+                raise NotImplementedError("transient-global attention needs the sub-layer's normed input for its block aggregates: "
+                                          "this caller hands over projections only")
+            position_bias = self._global_bias(position_bias)
+            gk, gv, cu_g = self._global_kv(x, cu)
+            out = flash_attn_varlen_func(q, k, v, cu, cu, mx, mx, False, self.softmax_scale, position_bias[0], position_bias[1],
+                                         window=self.window, global_kv=(gk, gv), global_rpe1d=position_bias[2],
+                                         global_radius=position_bias[3], cu_seqlens_g=cu_g)
+            return out.reshape(1, q.shape[0], self.inner_dim), position_bias
         rpe1d, radius = None, 0
         if self.rotary and position_bias is None:
             cos, sin, cos_k, sin_k = self._rotary_tables(q)
@@ -367,11 +455,21 @@ class FlashT5Attention(nn.Module):
     def _rotary_tables(self, x):
         return self.pe_encoding.tables(x.device, x.dtype)
 
-    def _attend(self, q, k, v, dtype, mask, is_self, position_bias):
-        """attention of projected (B, H, S, D) views -> (B, M, inner_dim), plus the position bias to hand on"""
+    def _attend(self, q, k, v, dtype, mask, is_self, position_bias, x=None):
+        """attention of projected (B, H, S, D) views -> (B, M, inner_dim), plus the position bias to hand on.
+        x: the sub-layer's normed input (B, S, d_model), which a transient-global layer aggregates its global keys from"""
         B, _, M, _ = q.shape
         N = k.shape[2]
         window = self.window if is_self else None
+        if self.tglobal and is_self:
+            if x is None:
+                raise NotImplementedError("transient-global attention needs the sub-layer's normed input for its block aggregates: "
+                                          "this caller hands over projections only")
+            position_bias = self._global_bias(position_bias)
+            gk, gv, _ = self._global_kv(x)
+            out = flash_attention_v2_rpe1d(q, k, v, position_bias[0], position_bias[1], False, self.softmax_scale, window=window,
+                                           global_kv=(gk, gv), global_rpe1d=position_bias[2], global_radius=position_bias[3])
+            return out.permute(0, 2, 1, 3).reshape(B, M, self.inner_dim), position_bias
         if self.rotary and position_bias is None:  # (q, k, v already rotated: no bias, and none handed on)
             if window is not None:
                 out = flash_attention_v2_rpe1d(q, k, v, None, 0, self.is_causal, self.softmax_scale, window=window)

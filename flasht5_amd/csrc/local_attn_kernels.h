@@ -412,7 +412,7 @@ __global__ __launch_bounds__(kLocalNT) void local_attn_bwd_kv_kernel(const Local
 }
 
 // drpe1d[h][j] = sum over (b, block) of the partial rows, in that order; entries outside the window's slice are zero
-__global__ void local_drpe_reduce_kernel(const float* part, float* drpe1d, int B, int H, int n_blk, int wc, int R) {
+static __global__ void local_drpe_reduce_kernel(const float* part, float* drpe1d, int B, int H, int n_blk, int wc, int R) {
   const int n1 = 2 * R + 1, n1c = 2 * wc + 1;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= H * n1) return;

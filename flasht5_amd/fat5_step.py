@@ -74,18 +74,23 @@ class FAT5Config:
     num_labels: int = 2                    # the encoder-only heads (heads.py): classes of the classifiers; the QA head needs 2
     classifier_dropout: float = 0.0        # the heads' own dropout sites (training only)
     eos_token_id: int = 1                  # FAT5ForSequenceClassification pools the row of the last <eos>
-    encoder_attention_type: str = "full"   # "local": LongT5's sliding-window encoder self-attention (HF LongT5's names)
+    encoder_attention_type: str = "full"   # "local": LongT5's sliding-window encoder self-attention (HF LongT5's names);
+                                           # "transient-global": ... plus one global key per 16 tokens under the same softmax
     local_radius: int = 127                # ... key n visible to row m iff |n - m| <= local_radius
 
     def __post_init__(self):
-        if self.encoder_attention_type not in ("full", "local"):
-            raise ValueError(f"encoder_attention_type {self.encoder_attention_type!r}: 'full' or 'local'")
-        if self.encoder_attention_type == "local":
+        if self.encoder_attention_type not in ("full", "local", "transient-global"):
+            raise ValueError(f"encoder_attention_type {self.encoder_attention_type!r}: 'full', 'local' or 'transient-global'")
+        if self.encoder_attention_type != "full":
+            kind = self.encoder_attention_type
             if self.attention_type != "fat5_rpe" or self.position_encoding_type not in ("t5", "RoPE"):
-                raise ValueError("encoder_attention_type='local' needs attention_type='fat5_rpe' with position_encoding_type 't5' or "
+                raise ValueError(f"encoder_attention_type={kind!r} needs attention_type='fat5_rpe' with position_encoding_type 't5' or "
                                  "'RoPE': the local kernels carry the T5 generator or no bias, never a dense one")
+            if kind == "transient-global" and self.position_encoding_type != "t5":
+                raise ValueError("encoder_attention_type='transient-global' needs position_encoding_type='t5': its global keys carry "
+                                 "a T5 table over block distances")
             if self.d_kv != 64:
-                raise ValueError(f"encoder_attention_type='local' needs d_kv = 64, got {self.d_kv}")
+                raise ValueError(f"encoder_attention_type={kind!r} needs d_kv = 64, got {self.d_kv}")
             if int(self.local_radius) < 1:
                 raise ValueError(f"local_radius = {self.local_radius} must be at least 1")
         if self.position_encoding_type == "FIRE" and self.attention_type == "fat5_rpe":
@@ -364,6 +369,8 @@ def init_stack_weights(root, c):
             # (RoPE has no table; FIRE keeps its own initialisation, which the reference's _init_weights does not touch)
             if m.pe_encoding is not None and hasattr(m.pe_encoding, "relative_attention_bias"):
                 m.pe_encoding.relative_attention_bias.weight.normal_(0.0, c.d_model ** -0.5)
+            if getattr(m, "global_pe_encoding", None) is not None:  # (transient-global, block 0: drawn after everything above)
+                m.global_pe_encoding.relative_attention_bias.weight.normal_(0.0, c.d_model ** -0.5)
 
 
 class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; cached greedy / sampled generation in generation.py)

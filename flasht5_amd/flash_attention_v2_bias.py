@@ -451,10 +451,19 @@ class FlashAttentionRPE1D(torch.autograd.Function):
         return dq, dk, dv, (d1.to(rdtype) if d1 is not None else None), None, None, None
 
 
-def flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, causal=False, sm_scale=None, window=None):
+def flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, causal=False, sm_scale=None, window=None, global_kv=None, global_rpe1d=None,
+                             global_radius=None):
     """Attention with the Toeplitz bias generated in-kernel from `rpe1d (H, 2*radius+1)` (see FlashAttentionRPE1D).
     window: None, or w >= 1 for local attention -- key n visible to row m iff |n - m| <= w (self-attention, head_dim 64, not
-    causal; `FlashAttentionLocal`).  With a window, rpe1d may be None: no bias."""
+    causal; `FlashAttentionLocal`).  With a window, rpe1d may be None: no bias.
+    global_kv=(gk, gv), each (B, H, S // 16, 64): LongT5's transient-global attention (`FlashAttentionTGlobal`) -- every row also
+    attends to the S // 16 global keys under the same softmax, with `global_rpe1d (H, 2*global_radius+1)` indexed by the block
+    distance g - min(m // 16, S // 16 - 1).  Needs window=; both tables or neither."""
+    if global_kv is not None or global_rpe1d is not None or global_radius is not None:
+        window, Rg = _check_tglobal(q, k, v, window, causal, global_kv, rpe1d, global_rpe1d, global_radius)
+        _check_inputs(q, k, v)
+        return FlashAttentionTGlobal.apply(q, k, v, global_kv[0], global_kv[1], rpe1d, global_rpe1d, int(radius), Rg, window, sm_scale,
+                                           None, None, None)
     if window is not None:
         _check_inputs(q, k, v)
         window = _check_local(q, k, v, window, causal)
@@ -650,11 +659,23 @@ class FlashAttentionVarlen(torch.autograd.Function):
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=False, sm_scale=None,
-                           rpe1d=None, radius=0, window=None):
+                           rpe1d=None, radius=0, window=None, global_kv=None, global_rpe1d=None, global_radius=None, cu_seqlens_g=None):
     """Differentiable packed attention (argument order of the flash_attn var-len entry point the reference's `fa2`
     attention types would call), optionally with the in-kernel T5 bias of `flash_attention_v2_rpe1d`.
     window: None, or w >= 1 for local attention inside each sequence (self-attention, head_dim 64, not causal).  The local
-    kernel reads cu_seqlens_q only: cu_seqlens_k / max_seqlen_k must be the query's."""
+    kernel reads cu_seqlens_q only: cu_seqlens_k / max_seqlen_k must be the query's.
+    global_kv=(gk, gv), each (total_g, H, 64), with cu_seqlens_g (nseq + 1,) int32, cu_seqlens_g[b] = sum over j < b of L_j // 16:
+    transient-global attention inside each sequence (see `flash_attention_v2_rpe1d`); total_g = total // 16 always suffices."""
+    if global_kv is not None or global_rpe1d is not None or global_radius is not None or cu_seqlens_g is not None:
+        if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+            raise ValueError("packed attention takes q (total_q, H, D) and k, v (total_k, H, D)")
+        window, Rg = _check_tglobal(q, k, v, window, causal, global_kv, rpe1d, global_rpe1d, global_radius, cu_seqlens_q, cu_seqlens_k,
+                                    max_seqlen_q, max_seqlen_k, cu_seqlens_g)
+        if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2:
+            raise ValueError("cu_seqlens_q must have (number of sequences + 1) entries")
+        cu, cu_g = _as_cu(cu_seqlens_q, q.device), _as_cu(cu_seqlens_g, q.device)
+        return FlashAttentionTGlobal.apply(q, k, v, global_kv[0], global_kv[1], rpe1d, global_rpe1d, int(radius), Rg, window, sm_scale,
+                                           cu, cu_g, int(max_seqlen_q))
     if window is not None:
         if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
             raise ValueError("packed attention takes q (total_q, H, D) and k, v (total_k, H, D)")
@@ -772,6 +793,133 @@ class FlashAttentionLocal(torch.autograd.Function):
             p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
             _lib.check(lib.fat5_attn_local_bwd(ctypes.byref(p), _lib.stream_ptr(q.device)), "fat5_attn_local_bwd")
         return dq, dk, dv, (d1.to(rdtype) if d1 is not None else None), None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# transient-global attention: LongT5's TGlobal -- the band plus one global key per 16 tokens under one softmax
+# (csrc/tglobal_attn_kernels.h)
+# ------------------------------------------------------------------------------------------------
+def _check_tglobal(q, k, v, window, causal, global_kv, rpe1d, global_rpe1d, global_radius, cu_q=None, cu_k=None, max_q=None, max_k=None,
+                   cu_g=None):
+    """host rejections of the transient-global path (ValueError, before anything is launched); returns (window, global radius)"""
+    if window is None:
+        raise ValueError("global_kv= / global_rpe1d= extend local attention: window= is required")
+    window = _check_local(q, k, v, window, causal, cu_q, cu_k, max_q, max_k)
+    if global_kv is None or len(global_kv) != 2:
+        raise ValueError("global_rpe1d= / global_radius= / cu_seqlens_g= need global_kv=(gk, gv)")
+    gk, gv = global_kv
+    if cu_q is None:
+        want = (q.shape[0], q.shape[1], q.shape[2] // 16, 64)
+        if tuple(gk.shape) != want or tuple(gv.shape) != want:
+            raise ValueError(f"global_kv must be two (B, H, S // 16, 64) = {want} tensors, got {tuple(gk.shape)}, {tuple(gv.shape)}")
+        if cu_g is not None:
+            raise ValueError("cu_seqlens_g= belongs to packed batches")
+    else:
+        if gk.dim() != 3 or tuple(gk.shape[1:]) != tuple(q.shape[1:]) or tuple(gv.shape) != tuple(gk.shape):
+            raise ValueError(f"packed global_kv must be two (total_g, H, 64) tensors, got {tuple(gk.shape)}, {tuple(gv.shape)}")
+        if cu_g is None or cu_g.dim() != 1 or cu_g.numel() != cu_q.numel():
+            raise ValueError("packed global_kv needs cu_seqlens_g with cu_seqlens_q's (number of sequences + 1) entries")
+    if gk.dtype != q.dtype or gv.dtype != q.dtype or gk.device != q.device or gv.device != q.device:
+        raise ValueError(f"global_kv must share q's dtype {q.dtype} and device")
+    if (rpe1d is None) != (global_rpe1d is None):
+        raise ValueError("rpe1d and global_rpe1d come together (both tables) or not at all (no bias)")
+    Rg = 0
+    if global_rpe1d is not None:
+        if global_radius is None or int(global_radius) != global_radius or not 1 <= int(global_radius) <= _lib.MAX_RPE_RADIUS:
+            raise ValueError(f"global_radius = {global_radius!r} must be an integer in [1, {_lib.MAX_RPE_RADIUS}]")
+        Rg = int(global_radius)
+        if tuple(global_rpe1d.shape) != (q.shape[1], 2 * Rg + 1):
+            raise ValueError(f"global_rpe1d must be (n_heads, 2 * global_radius + 1) = ({q.shape[1]}, {2 * Rg + 1}), got "
+                             f"{tuple(global_rpe1d.shape)}")
+    return window, Rg
+
+
+def _tglobal_params(ts, names, window, sm_scale, r1, radius, g1, g_radius, cu, cu_g, max_seqlen):
+    q = ts[0]
+    p = _lib.TGlobalAttnParams()
+    if cu is None:
+        p.B, p.H, p.S, p.D = q.shape
+        strides = _lib.strides3
+    else:
+        p.B, p.H, p.S, p.D, p.total = cu.numel() - 1, q.shape[1], int(max_seqlen), q.shape[2], q.shape[0]
+        p.cu_seqlens, p.cu_seqlens_g = cu.data_ptr(), cu_g.data_ptr()
+        strides = lambda t: _lib.c_i64x3(0, t.stride(1), t.stride(0))
+    p.dtype, p.window, p.sm_scale = _lib.dtype_code(q.dtype), window, float(sm_scale)
+    for name, t in zip(names, ts):
+        if name in ("gk", "gv", "dgk", "dgv") and t.numel() == 0:  # no sequence has 16 tokens: nothing to point at
+            continue
+        if name == "gk" and cu is not None:
+            p.total_g = t.shape[0]
+        setattr(p, name, t.data_ptr())
+        setattr(p, ("do" if name == "dout" else name) + "_stride", strides(t))
+    if r1 is not None:
+        p.bias_mode, p.rpe1d, p.rpe_radius, p.grpe1d, p.g_radius = _lib.BIAS_RPE1D, r1.data_ptr(), int(radius), g1.data_ptr(), int(g_radius)
+    return p
+
+
+class FlashAttentionTGlobal(torch.autograd.Function):
+    """Transient-global attention over the ctypes ABI (`fat5_attn_tglobal_fwd` / `_bwd`), dense (B, H, S, D) views with globals
+    (B, H, S // 16, D), or packed (total, H, D) tensors with globals (total_g, H, D) under `cu_seqlens` / `cu_seqlens_g`;
+    differentiable in q, k, v, gk, gv and both tables (None: no bias).  Eager and HIP-graph capture, like FlashAttentionLocal."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, gk, gv, rpe1d, grpe1d, radius, g_radius, window, sm_scale, cu, cu_g, max_seqlen):
+        packed = cu is not None
+        if not q.is_cuda:
+            raise RuntimeError("flasht5_amd attention needs tensors on the HIP device (no CPU fallback)")
+        if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+            raise TypeError("q, k, v must share dtype float16 or bfloat16")
+        if sm_scale is None:
+            sm_scale = 1.0 / math.sqrt(q.shape[-1])
+        H = q.shape[1]
+        r1 = g1 = None
+        if rpe1d is not None:
+            if radius > _lib.MAX_RPE_RADIUS:
+                raise ValueError(f"radius {radius} exceeds the RPE-mode limit {_lib.MAX_RPE_RADIUS}")
+            r1, g1 = rpe1d.detach().float().contiguous(), grpe1d.detach().float().contiguous()
+            _check_rpe1d(r1, H, radius, q.device)
+            _check_rpe1d(g1, H, g_radius, q.device)
+        q, k, v, gk, gv = (_local_ready(t, packed) for t in (q, k, v, gk, gv))
+        o = _local_like(q)
+        lse = torch.empty((H, q.shape[0]) if packed else (q.shape[0], H, q.shape[2]), dtype=torch.float32, device=q.device)
+        p = _tglobal_params((q, k, v, o, gk, gv), ("q", "k", "v", "o", "gk", "gv"), window, sm_scale, r1, radius, g1, g_radius, cu, cu_g,
+                            max_seqlen)
+        p.lse = lse.data_ptr()
+        with _lib.on_device(q.device):
+            _lib.check(_lib.load().fat5_attn_tglobal_fwd(ctypes.byref(p), _lib.stream_ptr(q.device)), "fat5_attn_tglobal_fwd")
+        ctx.save_for_backward(q, k, v, gk, gv, o, lse, *([cu, cu_g] if packed else []), *([r1, g1] if r1 is not None else []))
+        ctx.meta = (packed, r1 is not None, int(radius), int(g_radius), window, sm_scale, max_seqlen,
+                    rpe1d.dtype if rpe1d is not None else None, grpe1d.dtype if grpe1d is not None else None)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        packed, has_bias, radius, g_radius, window, sm_scale, max_seqlen, rdtype, gdtype = ctx.meta
+        q, k, v, gk, gv, o, lse, *rest = ctx.saved_tensors
+        cu, cu_g = (rest.pop(0), rest.pop(0)) if packed else (None, None)
+        r1, g1 = (rest.pop(0), rest.pop(0)) if has_bias else (None, None)
+        do = _local_ready(do, packed)
+        if not packed and packed_slices((q, k, v)):  # gradients of one stacked projection: slices of one buffer
+            dq, dk, dv = empty_packed_like((q, k, v))
+        else:
+            dq, dk, dv = _local_like(q), _local_like(k), _local_like(v)
+        # (zeros: a packed batch's rows past cu_seqlens_g[-1] belong to no sequence and are never written)
+        dgk, dgv = (torch.zeros(t.shape, dtype=t.dtype, device=t.device) for t in (gk, gv))
+        p = _tglobal_params((q, k, v, o, gk, gv, do, dq, dk, dv, dgk, dgv),
+                            ("q", "k", "v", "o", "gk", "gv", "dout", "dq", "dk", "dv", "dgk", "dgv"), window, sm_scale, r1, radius, g1,
+                            g_radius, cu, cu_g, max_seqlen)
+        p.lse = lse.data_ptr()
+        d1 = dg1 = None
+        if has_bias and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]):
+            d1, dg1 = torch.empty_like(r1), torch.empty_like(g1)
+            p.drpe1d, p.dgrpe1d = d1.data_ptr(), dg1.data_ptr()
+        lib = _lib.load()
+        with _lib.on_device(q.device):
+            ws = _workspace(lib.fat5_attn_tglobal_bwd_workspace_bytes(ctypes.byref(p)), q.device)
+            p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+            _lib.check(lib.fat5_attn_tglobal_bwd(ctypes.byref(p), _lib.stream_ptr(q.device)), "fat5_attn_tglobal_bwd")
+        return (dq, dk, dv, dgk, dgv, (d1.to(rdtype) if d1 is not None else None), (dg1.to(gdtype) if dg1 is not None else None),
+                None, None, None, None, None, None, None)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1547,6 +1547,74 @@ size_t fat5_attn_local_bwd_workspace_bytes(const fat5_local_attn_params* p);
  * diagonal sums, dK / dV, and the fixed-order sum of the partial rows. */
 int fat5_attn_local_bwd(const fat5_local_attn_params* p, void* hip_stream);
 
+/*
+ * Transient-global self-attention -- LongT5's TGlobal encoder attention: the local attention above plus one "global" key per 16
+ * tokens of the sequence, under ONE softmax.
+ *
+ *   Per sequence of length L: G = L / 16 global keys gk[g], gv[g] (given: the caller aggregates and projects them); the block of
+ *   row m is blk(m) = min(m / 16, G - 1).  Row m scores the band keys |n - m| <= window as the local entries do, and every g < G
+ *   with q[m] . gk[g] * sm_scale + grpe1d[h][clamp(g - blk(m), -Rg, Rg) + Rg];
+ *   o[m] = P_band v + P_glob gv, lse the joint log-sum-exp.  G = 0: local attention.
+ *   bias_mode FAT5_BIAS_RPE1D takes BOTH tables (rpe1d and grpe1d), FAT5_BIAS_NONE neither.
+ *
+ * Layouts: q, k, v, o, lse and cu_seqlens as in the local descriptor.  Dense: gk, gv are (B, H, S / 16, D) views with element
+ * strides [b, h, g].  Packed: (total_g, H, D) tensors; cu_seqlens_g (B + 1,) int32 on the device with
+ * cu_seqlens_g[b] = sum over j < b of L_j / 16, total_g the rows the tensors hold (total / 16 always suffices; a sequence's
+ * globals never reach past it).
+ *
+ * Backward: dq, dk, dv as in the local descriptor, dgk, dgv in the layouts of gk, gv (rows g < G of every sequence are written);
+ * drpe1d (H, 2R+1) and dgrpe1d (H, 2Rg+1) fp32, overwritten, both or neither: dgrpe1d[h][e] is the sum of dS[m][g] over the pairs
+ * with clamp(g - blk(m)) + Rg = e, zeros where no pair reaches.  No atomics: the same bits on every run.  Launches: dQ (with delta
+ * and both tables' partial sums), the local dK / dV, dgK / dgV, and the fixed-order sum of the partial rows.
+ *
+ * Rejected with FAT5_EINVAL before anything is launched: what the local entries reject, g_radius outside [1, 1024], a packed
+ * batch without cu_seqlens_g or with total_g < 0 (and cu_seqlens_g without cu_seqlens), exactly one of drpe1d / dgrpe1d;
+ * S >= 16 with NULL or misaligned gk / gv (dgk / dgv); FAT5_EWORKSPACE as above.
+ */
+typedef struct fat5_tglobal_attn_params {
+  int32_t B, H, S, D;
+  int32_t dtype;            /* FAT5_F16 | FAT5_BF16: q, k, v, gk, gv, o and every 16-bit gradient */
+  int32_t bias_mode;        /* FAT5_BIAS_NONE | FAT5_BIAS_RPE1D (both tables) */
+  int32_t window;           /* >= 1 */
+  int32_t rpe_radius;       /* R: 1..1024 */
+  float sm_scale;
+  int32_t total;            /* packed: tokens of the batch */
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  float* lse;
+  int64_t q_stride[3], k_stride[3], v_stride[3], o_stride[3];
+  const float* rpe1d;       /* (H, 2R+1) fp32 contiguous */
+  const int32_t* cu_seqlens; /* packed: (B + 1,) int32 on the device; NULL: dense */
+  /* ---- the global keys ---- */
+  const void* gk;
+  const void* gv;
+  int64_t gk_stride[3], gv_stride[3];
+  const float* grpe1d;      /* (H, 2Rg+1) fp32 contiguous */
+  const int32_t* cu_seqlens_g; /* packed: (B + 1,) int32 on the device */
+  int32_t g_radius;         /* Rg: 1..1024 */
+  int32_t total_g;          /* packed: rows of gk / gv */
+  /* ---- backward (ignored by the forward) ---- */
+  const void* dout;
+  void* dq;
+  void* dk;
+  void* dv;
+  void* dgk;
+  void* dgv;
+  int64_t do_stride[3], dq_stride[3], dk_stride[3], dv_stride[3], dgk_stride[3], dgv_stride[3];
+  float* drpe1d;
+  float* dgrpe1d;
+  void* workspace;
+  size_t workspace_bytes;
+} fat5_tglobal_attn_params;
+size_t fat5_sizeof_tglobal_attn_params(void);
+/* forward: writes o, lse */
+int fat5_attn_tglobal_fwd(const fat5_tglobal_attn_params* p, void* hip_stream);
+size_t fat5_attn_tglobal_bwd_workspace_bytes(const fat5_tglobal_attn_params* p);
+/* backward: reads q, k, v, gk, gv, o, lse, dout (and the tables); writes dq, dk, dv, dgk, dgv (and the table gradients) */
+int fat5_attn_tglobal_bwd(const fat5_tglobal_attn_params* p, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
