@@ -357,7 +357,24 @@ class TGlobalAttnParams(ctypes.Structure):
     ]
 
 
+class AttnDropoutParams(ctypes.Structure):
+    """Mirror of `fat5_attn_dropout_params` (include/fat5.h) -- field order must match exactly."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("D", ctypes.c_int32),
+        ("dtype", ctypes.c_int32), ("bias_mode", ctypes.c_int32), ("causal", ctypes.c_int32), ("rpe_radius", ctypes.c_int32),
+        ("sm_scale", ctypes.c_float), ("total_q", ctypes.c_int32), ("total_k", ctypes.c_int32),
+        ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("o", ctypes.c_void_p), ("lse", ctypes.c_void_p),
+        ("q_stride", c_i64x3), ("k_stride", c_i64x3), ("v_stride", c_i64x3), ("o_stride", c_i64x3),
+        ("rpe1d", ctypes.c_void_p), ("cu_seqlens_q", ctypes.c_void_p), ("cu_seqlens_k", ctypes.c_void_p),
+        ("seed", ctypes.c_uint64), ("step", ctypes.c_void_p), ("site", ctypes.c_uint32), ("p", ctypes.c_float),
+        ("dout", ctypes.c_void_p), ("dq", ctypes.c_void_p), ("dk", ctypes.c_void_p), ("dv", ctypes.c_void_p),
+        ("do_stride", c_i64x3), ("dq_stride", c_i64x3), ("dk_stride", c_i64x3), ("dv_stride", c_i64x3),
+        ("drpe1d", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 EXPORTS = (
+    "fat5_sizeof_attn_dropout_params", "fat5_attn_dropout_fwd", "fat5_attn_dropout_bwd_workspace_bytes", "fat5_attn_dropout_bwd",
     "fat5_sizeof_tglobal_attn_params", "fat5_attn_tglobal_fwd", "fat5_attn_tglobal_bwd_workspace_bytes", "fat5_attn_tglobal_bwd",
     "fat5_sizeof_local_attn_params", "fat5_attn_local_fwd", "fat5_attn_local_bwd_workspace_bytes", "fat5_attn_local_bwd",
     "fat5_version", "fat5_chip_cus", "fat5_last_error", "fat5_sizeof_attn_params", "fat5_attn_fwd", "fat5_attn_bwd_workspace_bytes", "fat5_attn_bwd", "fat5_attn_bwd_launches", "fat5_attn_bwd_kvres",
@@ -602,6 +619,15 @@ def load():
     if lib.fat5_sizeof_dropout_desc() != ctypes.sizeof(DropoutDesc):
         raise ImportError(f"fat5_dropout_desc layout mismatch: library {lib.fat5_sizeof_dropout_desc()} B, "
                           f"binding {ctypes.sizeof(DropoutDesc)} B")
+    for fn in (lib.fat5_attn_dropout_fwd, lib.fat5_attn_dropout_bwd):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(AttnDropoutParams), ctypes.c_void_p]
+    lib.fat5_attn_dropout_bwd_workspace_bytes.restype = ctypes.c_size_t
+    lib.fat5_attn_dropout_bwd_workspace_bytes.argtypes = [ctypes.POINTER(AttnDropoutParams)]
+    lib.fat5_sizeof_attn_dropout_params.restype = ctypes.c_size_t
+    if lib.fat5_sizeof_attn_dropout_params() != ctypes.sizeof(AttnDropoutParams):
+        raise ImportError(f"fat5_attn_dropout_params layout mismatch: library {lib.fat5_sizeof_attn_dropout_params()} B, "
+                          f"binding {ctypes.sizeof(AttnDropoutParams)} B")
     for fn in (lib.fat5_attn_local_fwd, lib.fat5_attn_local_bwd):
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.POINTER(LocalAttnParams), ctypes.c_void_p]

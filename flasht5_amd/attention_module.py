@@ -23,7 +23,8 @@ does not rotate.
 its (1, H, S, S) bias comes from one HIP kernel (flasht5_amd/fire.py) and is handed on to the following blocks like the T5 bias,
 with `use_full_bias_size` and `use_masking` applied the same way.  FIRE needs the dense-bias type ("triton"): its bias is not
 Toeplitz once a row passes the threshold T, so `fat5_rpe` cannot carry it.  Other producers' dense outputs (ALiBi, ...) can be
-passed as `position_bias`.  Dropout is not supported (like the reference's Triton path, :201)."""
+passed as `position_bias`.  `attention_dropout_rate` > 0 (training only) needs "fat5_rpe" with the T5 table or RoPE: the attention
+then runs on the dropout kernel family; the dense-bias type refuses it (like the reference's Triton path, :201)."""
 import math
 
 import torch
@@ -99,8 +100,17 @@ class FlashT5Attention(nn.Module):
         self.use_masking = _cfg(config, "use_masking", False)
         if self.attention_type not in ("triton", "fat5_rpe"):
             raise ValueError(f"attention_type {self.attention_type!r}: this module implements 'triton' (dense bias) and 'fat5_rpe'")
-        if _cfg(config, "attention_dropout_rate", 0.0) != 0.0:
-            raise ValueError("attention dropout is not supported by the fused kernels")
+        # dropout on the attention weights, training only: a kernel family of its own that carries the T5 generator or
+        # no bias; `attn_site` is this layer's site number in the mask counter (the model numbers its layers)
+        self.attention_dropout = float(_cfg(config, "attention_dropout_rate", 0.0))
+        self.attn_site = 0
+        if not 0.0 <= self.attention_dropout < 1.0:
+            raise ValueError(f"attention_dropout_rate = {self.attention_dropout} outside [0, 1)")
+        if self.attention_dropout > 0 and (self.attention_type != "fat5_rpe" or self.position_encoding_type not in ("t5", "RoPE")
+                                           or _cfg(config, "encoder_attention_type", "full") != "full" or self.key_value_proj_dim != 64):
+            raise ValueError("attention dropout needs attention_type='fat5_rpe' with position_encoding_type 't5' or 'RoPE', "
+                             "encoder_attention_type='full' and d_kv = 64: the dropout kernels carry the T5 generator or no bias, never "
+                             "a dense one (attention_type='triton', FIRE), and no window")
         if self.attention_type == "fat5_rpe" and self.position_encoding_type == "FIRE":
             raise ValueError("FIRE needs attention_type='triton' (dense bias): its bias is not Toeplitz once a row passes the "
                              "threshold T, so fat5_rpe cannot carry it")
@@ -211,13 +221,23 @@ class FlashT5Attention(nn.Module):
                              "global rpe1d, global radius) from block 0")
         return position_bias
 
+    def _dropout_kw(self, attn_drop):
+        """the dropout_* arguments of this layer's attention call: none in eval mode or with a zero rate (today's call, bit for bit)"""
+        if not (self.training and self.attention_dropout > 0):
+            return {}
+        if attn_drop is None:
+            raise RuntimeError("attention_dropout_rate > 0 in training mode needs attn_drop=(seed, step): the Philox key and the "
+                               "forward's int64 one-element device copy of the step counter")
+        return dict(dropout_p=self.attention_dropout, dropout_seed=attn_drop[0], dropout_step=attn_drop[1], dropout_site=self.attn_site)
+
     def forward(self, hidden_states, mask=None, key_value_states=None, position_bias=None, cu_seqlens=None, max_seqlen=None,
-                kv_cu_seqlens=None, kv_max_seqlen=None):
+                kv_cu_seqlens=None, kv_max_seqlen=None, attn_drop=None):
         """cu_seqlens / max_seqlen (and, for cross-attention, kv_cu_seqlens / kv_max_seqlen of the key / value side): packed
-        hidden states (1, total, d_model), every sequence attending inside itself with positions of its own (packed_supported)"""
+        hidden states (1, total, d_model), every sequence attending inside itself with positions of its own (packed_supported).
+        attn_drop = (seed, step): the attention-dropout context of a training forward (attention_dropout_rate > 0)"""
         if cu_seqlens is not None:
             return self._forward_packed(hidden_states, key_value_states, position_bias, cu_seqlens, max_seqlen, kv_cu_seqlens,
-                                        kv_max_seqlen)
+                                        kv_max_seqlen, attn_drop)
         B, M = hidden_states.shape[:2]
         src = hidden_states if key_value_states is None else key_value_states
         N = src.shape[1]
@@ -228,11 +248,12 @@ class FlashT5Attention(nn.Module):
         if self.rotary and position_bias is None:  # q, k, v in one launch (new tensors: nothing autograd saved is touched)
             q, k, v, _ = self.pe_encoding(q, k, v)
         q, k, v = q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3)
-        out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias, x=hidden_states)
+        out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias, x=hidden_states,
+                                          attn_drop=attn_drop)
         return self.o(out), position_bias
 
     def forward_fused(self, hidden_states, norm_weight, eps, mask=None, key_value_states=None, position_bias=None, cu_seqlens=None,
-                      max_seqlen=None, kv_cu_seqlens=None, kv_max_seqlen=None):
+                      max_seqlen=None, kv_cu_seqlens=None, kv_max_seqlen=None, attn_drop=None):
         """One whole T5 attention sub-layer, `h + o(attention(layer_norm(h)))` (reference modeling_flash_t5.py:304-318 / :321-349),
         with the pre-norm inside the projection GEMM and the residual add as the output projection's epilogue
         (`fused_linear.rmsnorm_linear` / `linear_residual`): `hidden_states` is the UN-normalised residual stream,
@@ -258,7 +279,7 @@ class FlashT5Attention(nn.Module):
                 q = q.view(M, H, Dh)
                 k, v = (t[0].transpose(0, 1) for t in unpack_heads(kv, 2, H))
             out, position_bias = self._attend_packed(q, k, v, key_value_states is None, position_bias, cu_seqlens, max_seqlen,
-                                                     kv_cu_seqlens, kv_max_seqlen)
+                                                     kv_cu_seqlens, kv_max_seqlen, attn_drop=attn_drop)
             return linear_residual(out, self.o.weight, res), position_bias
         if key_value_states is None:  # self-attention: ONE GEMM for q, k, v
             qkv, res = rmsnorm_linear(hidden_states, norm_weight, (self.Wq.weight, self.Wk.weight, self.Wv.weight), eps, return_residual=True)
@@ -272,7 +293,7 @@ class FlashT5Attention(nn.Module):
                 q, kv = apply_rotary_emb_packed((q, kv), (1, 2), H, *self._rotary_tables(q), nq=1, interleaved=self.pe_encoding.interleaved)
             q = q.view(B, M, H, Dh).permute(0, 2, 1, 3)
             k, v = unpack_heads(kv, 2, H)
-        out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias)
+        out, position_bias = self._attend(q, k, v, hidden_states.dtype, mask, key_value_states is None, position_bias, attn_drop=attn_drop)
         return linear_residual(out, self.o.weight, res), position_bias
 
     def packed_supported(self):
@@ -301,7 +322,8 @@ class FlashT5Attention(nn.Module):
             if key_value_states.dim() != 3 or key_value_states.shape[0] != 1:
                 raise ValueError(f"packed key / value states are (1, total_k, d_model), got {tuple(key_value_states.shape)}")
 
-    def _forward_packed(self, hidden_states, key_value_states, position_bias, cu_seqlens, max_seqlen, kv_cu_seqlens, kv_max_seqlen):
+    def _forward_packed(self, hidden_states, key_value_states, position_bias, cu_seqlens, max_seqlen, kv_cu_seqlens, kv_max_seqlen,
+                        attn_drop=None):
         self.packed_supported()
         self._packed_args(hidden_states, key_value_states, cu_seqlens, max_seqlen, kv_cu_seqlens, kv_max_seqlen)
         H, Dh = self.n_heads, self.key_value_proj_dim
@@ -310,10 +332,10 @@ class FlashT5Attention(nn.Module):
         k = self.Wk(src).view(src.shape[1], H, Dh)
         v = self.Wv(src).view(src.shape[1], H, Dh)
         out, position_bias = self._attend_packed(q, k, v, key_value_states is None, position_bias, cu_seqlens, max_seqlen,
-                                                 kv_cu_seqlens, kv_max_seqlen, x=hidden_states)
+                                                 kv_cu_seqlens, kv_max_seqlen, x=hidden_states, attn_drop=attn_drop)
         return self.o(out), position_bias
 
-    def _attend_packed(self, q, k, v, is_self, position_bias, cu, mx, kv_cu, kv_mx, x=None):
+    def _attend_packed(self, q, k, v, is_self, position_bias, cu, mx, kv_cu, kv_mx, x=None, attn_drop=None):
         """packed attention of projected (total, H, D) views -> (1, total_q, inner_dim), plus the position bias to hand on: the T5
         generator of block 0's forward_1d() in-kernel, or rotated q / k / v and no bias, positions local to each sequence.
         x: the sub-layer's normed input (1, total, d_model), which a transient-global layer aggregates its global keys from"""
@@ -349,7 +371,7 @@ class FlashT5Attention(nn.Module):
                                  "block that owns the RelativePositionalEncoding")
             rpe1d, radius = position_bias
         out = flash_attn_varlen_func(q, k, v, cu, kv_cu, mx, kv_mx, self.is_causal and is_self, self.softmax_scale, rpe1d, radius,
-                                     window=self.window if is_self else None)
+                                     window=self.window if is_self else None, **self._dropout_kw(attn_drop))
         return out.reshape(1, q.shape[0], self.inner_dim), position_bias
 
     def decode_supported(self):
@@ -455,12 +477,13 @@ class FlashT5Attention(nn.Module):
     def _rotary_tables(self, x):
         return self.pe_encoding.tables(x.device, x.dtype)
 
-    def _attend(self, q, k, v, dtype, mask, is_self, position_bias, x=None):
+    def _attend(self, q, k, v, dtype, mask, is_self, position_bias, x=None, attn_drop=None):
         """attention of projected (B, H, S, D) views -> (B, M, inner_dim), plus the position bias to hand on.
         x: the sub-layer's normed input (B, S, d_model), which a transient-global layer aggregates its global keys from"""
         B, _, M, _ = q.shape
         N = k.shape[2]
         window = self.window if is_self else None
+        drop_kw = self._dropout_kw(attn_drop)
         if self.tglobal and is_self:
             if x is None:
                 raise NotImplementedError("transient-global attention needs the sub-layer's normed input for its block aggregates: "
@@ -471,8 +494,8 @@ class FlashT5Attention(nn.Module):
                                            global_kv=(gk, gv), global_rpe1d=position_bias[2], global_radius=position_bias[3])
             return out.permute(0, 2, 1, 3).reshape(B, M, self.inner_dim), position_bias
         if self.rotary and position_bias is None:  # (q, k, v already rotated: no bias, and none handed on)
-            if window is not None:
-                out = flash_attention_v2_rpe1d(q, k, v, None, 0, self.is_causal, self.softmax_scale, window=window)
+            if window is not None or drop_kw:
+                out = flash_attention_v2_rpe1d(q, k, v, None, 0, self.is_causal, self.softmax_scale, window=window, **drop_kw)
             else:
                 out = flash_attention_v2_bias(q, k, v, None, self.is_causal, self.softmax_scale)
             return out.permute(0, 2, 1, 3).reshape(B, M, self.inner_dim), None
@@ -488,10 +511,13 @@ class FlashT5Attention(nn.Module):
                 if key_value_states is None and self.position_encoding_type == "t5":
                     raise ValueError("fat5_rpe self-attention without a bias producer needs position_bias=(rpe1d, radius) from the "
                                      "block that owns the RelativePositionalEncoding")
-                out = flash_attention_v2_bias(q, k, v, None, self.is_causal, self.softmax_scale)
+                if drop_kw:
+                    out = flash_attention_v2_rpe1d(q, k, v, None, 0, self.is_causal, self.softmax_scale, **drop_kw)
+                else:
+                    out = flash_attention_v2_bias(q, k, v, None, self.is_causal, self.softmax_scale)
             else:
                 rpe1d, radius = position_bias
-                out = flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, self.is_causal, self.softmax_scale, window=window)
+                out = flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, self.is_causal, self.softmax_scale, window=window, **drop_kw)
         else:
             if position_bias is None and isinstance(self.pe_encoding, FIRE):  # (the reference's FIRE.forward: (1, H, S, S), S = M)
                 # (no .contiguous(): when S is not a multiple of 8 the bias rows are padded to 16 bytes, which the kernels take as is)

@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-mllvm", "-amdg
 
 # (source, object name, extra defines)
 # the C API, one unit per kernel family (helpers they share: api_common.h)
-UNITS = [(f"api_{n}.hip", f"api_{n}.o", []) for n in ("core", "attn", "rowwise", "position", "decode", "generate", "pack", "dropout", "ul2", "w8", "pool", "kd", "local", "tglobal")]
+UNITS = [(f"api_{n}.hip", f"api_{n}.o", []) for n in ("core", "attn", "rowwise", "position", "decode", "generate", "pack", "dropout", "ul2", "w8", "pool", "kd", "local", "tglobal", "attn_dropout")]
 # the matrix-pipe FP8-weight linear: scalar fp32 ops only in its VALU code (no v_pk_{add,mul,fma}_f32)
 UNITS.append(("api_w8_mma.hip", "api_w8_mma.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
 # the MXFP4-weight linear: its staging expression and statistics are that unit's, kept under the same code generation

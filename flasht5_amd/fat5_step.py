@@ -70,6 +70,8 @@ class FAT5Config:
     fuse_gated_act: bool = True            # act(wi_0 x) * wi_1 x in one kernel forward, one backward (gated_act.py / fat5_gated_act_*)
     dropout_rate: float = 0.0              # the reference's six dropout sites (modeling_flash_t5.py :124/:143, :163, :316, :342, :440, :460), training only
     dropout_seed: Optional[int] = None     # the Philox key of the masks; None: drawn from torch's default CPU generator when the model is built
+    attention_dropout_rate: float = 0.0    # dropout on the attention weights (the reference's dropout_p of its attention), training only: a kernel
+                                           # family of its own; needs attention_type="fat5_rpe", "t5" or "RoPE", d_kv = 64
     is_decoder: bool = False
     num_labels: int = 2                    # the encoder-only heads (heads.py): classes of the classifiers; the QA head needs 2
     classifier_dropout: float = 0.0        # the heads' own dropout sites (training only)
@@ -100,6 +102,14 @@ class FAT5Config:
             raise ValueError(f"dropout_rate = {self.dropout_rate} outside [0, 1)")
         if not 0.0 <= float(self.classifier_dropout) < 1.0:
             raise ValueError(f"classifier_dropout = {self.classifier_dropout} outside [0, 1)")
+        if not 0.0 <= float(self.attention_dropout_rate) < 1.0:
+            raise ValueError(f"attention_dropout_rate = {self.attention_dropout_rate} outside [0, 1)")
+        if self.attention_dropout_rate > 0:
+            if (self.attention_type != "fat5_rpe" or self.position_encoding_type not in ("t5", "RoPE")
+                    or self.encoder_attention_type != "full" or self.d_kv != 64):
+                raise ValueError("attention_dropout_rate > 0 needs attention_type='fat5_rpe' with position_encoding_type 't5' or 'RoPE', "
+                                 "encoder_attention_type='full' and d_kv = 64: the dropout kernels carry the T5 generator or no bias, "
+                                 "never a dense one (attention_type='triton', FIRE), and no window")
         if int(self.num_labels) < 1:
             raise ValueError(f"num_labels = {self.num_labels} must be at least 1")
         if self.dropout_rate > 0 and self.fuse_norm_linear:
@@ -132,16 +142,21 @@ class FAT5GatedAct(nn.Module):  # reference FlashT5DenseGatedAct / FlashT5DenseA
         return self.act(self.wi(x))
 
 
-def _self_kw(packing):
-    """the packed-row keyword arguments of a self-attention layer (none without a packing.Packed: today's call)"""
-    return {} if packing is None else dict(cu_seqlens=packing.cu_seqlens, max_seqlen=packing.max_seqlen)
+def _self_kw(packing, adrop=None):
+    """the packed-row keyword arguments of a self-attention layer (none without a packing.Packed: today's call), and the forward's
+    attention-dropout context adrop = (Philox key, step tensor) when there is one"""
+    kw = {} if packing is None else dict(cu_seqlens=packing.cu_seqlens, max_seqlen=packing.max_seqlen)
+    if adrop is not None:
+        kw["attn_drop"] = adrop
+    return kw
 
 
-def _cross_kw(packing):
+def _cross_kw(packing, adrop=None):
+    kw = {} if adrop is None else dict(attn_drop=adrop)
     if packing is None:
-        return {}
+        return kw
     return dict(cu_seqlens=packing.cu_seqlens, max_seqlen=packing.max_seqlen, kv_cu_seqlens=packing.kv_cu_seqlens,
-                kv_max_seqlen=packing.kv_max_seqlen)
+                kv_max_seqlen=packing.kv_max_seqlen, **kw)
 
 
 class _Drop:
@@ -220,17 +235,17 @@ class FAT5LayerSelfAttention(nn.Module):  # :297-318
 
     site = 0  # dropout site of the sub-layer's output
 
-    def forward(self, h, position_bias=None, packing=None, drop=None):
-        a, position_bias = self.self_attention(self.layer_norm(h), position_bias=position_bias, **_self_kw(packing))
+    def forward(self, h, position_bias=None, packing=None, drop=None, adrop=None):
+        a, position_bias = self.self_attention(self.layer_norm(h), position_bias=position_bias, **_self_kw(packing, adrop))
         return (h + a if drop is None else drop.add(h, a, self.site)), position_bias
 
-    def forward_fused(self, h, position_bias=None, packing=None):
+    def forward_fused(self, h, position_bias=None, packing=None, adrop=None):
         return self.self_attention.forward_fused(h, self.layer_norm.weight, self.layer_norm.variance_epsilon, position_bias=position_bias,
-                                                 **_self_kw(packing))
+                                                 **_self_kw(packing, adrop))
 
-    def forward_deferred(self, h, pending, position_bias=None, packing=None, drop=None, pending_site=0):
+    def forward_deferred(self, h, pending, position_bias=None, packing=None, drop=None, pending_site=0, adrop=None):
         h, n = _pre_norm(self.layer_norm, h, pending, drop, pending_site)
-        a, position_bias = self.self_attention(n, position_bias=position_bias, **_self_kw(packing))
+        a, position_bias = self.self_attention(n, position_bias=position_bias, **_self_kw(packing, adrop))
         return h, a, position_bias
 
 
@@ -242,17 +257,17 @@ class FAT5LayerCrossAttention(nn.Module):  # :321-349
 
     site = 0  # dropout site of the sub-layer's output
 
-    def forward(self, h, key_value_states, packing=None, drop=None):
-        a, _ = self.cross_attention(self.layer_norm(h), key_value_states=key_value_states, **_cross_kw(packing))
+    def forward(self, h, key_value_states, packing=None, drop=None, adrop=None):
+        a, _ = self.cross_attention(self.layer_norm(h), key_value_states=key_value_states, **_cross_kw(packing, adrop))
         return h + a if drop is None else drop.add(h, a, self.site)
 
-    def forward_fused(self, h, key_value_states, packing=None):
+    def forward_fused(self, h, key_value_states, packing=None, adrop=None):
         return self.cross_attention.forward_fused(h, self.layer_norm.weight, self.layer_norm.variance_epsilon, key_value_states=key_value_states,
-                                                  **_cross_kw(packing))[0]
+                                                  **_cross_kw(packing, adrop))[0]
 
-    def forward_deferred(self, h, pending, key_value_states, packing=None, drop=None, pending_site=0):
+    def forward_deferred(self, h, pending, key_value_states, packing=None, drop=None, pending_site=0, adrop=None):
         h, n = _pre_norm(self.layer_norm, h, pending, drop, pending_site)
-        a, _ = self.cross_attention(n, key_value_states=key_value_states, **_cross_kw(packing))
+        a, _ = self.cross_attention(n, key_value_states=key_value_states, **_cross_kw(packing, adrop))
         return h, a
 
 
@@ -275,24 +290,25 @@ class FAT5Block(nn.Module):  # :352-392
         self.ff_layer.site_act, self.ff_layer.site = site, site + 1
         return site + 2
 
-    def forward(self, h, position_bias=None, encoder_hidden_states=None, packing=None, drop=None):
-        h, position_bias = self.self_attention_layer(h, position_bias, packing, drop)
+    def forward(self, h, position_bias=None, encoder_hidden_states=None, packing=None, drop=None, adrop=None):
+        h, position_bias = self.self_attention_layer(h, position_bias, packing, drop, adrop)
         if self.is_decoder and encoder_hidden_states is not None:
-            h = self.cross_attention_layer(h, encoder_hidden_states, packing, drop)
+            h = self.cross_attention_layer(h, encoder_hidden_states, packing, drop, adrop)
         return self.ff_layer(h, drop), position_bias
 
-    def forward_fused(self, h, position_bias=None, encoder_hidden_states=None, packing=None):
-        h, position_bias = self.self_attention_layer.forward_fused(h, position_bias, packing)
+    def forward_fused(self, h, position_bias=None, encoder_hidden_states=None, packing=None, adrop=None):
+        h, position_bias = self.self_attention_layer.forward_fused(h, position_bias, packing, adrop)
         if self.is_decoder and encoder_hidden_states is not None:
-            h = self.cross_attention_layer.forward_fused(h, encoder_hidden_states, packing)
+            h = self.cross_attention_layer.forward_fused(h, encoder_hidden_states, packing, adrop)
         return self.ff_layer.forward_fused(h), position_bias
 
-    def forward_deferred(self, h, pending, position_bias=None, encoder_hidden_states=None, packing=None, drop=None, pending_site=0):
+    def forward_deferred(self, h, pending, position_bias=None, encoder_hidden_states=None, packing=None, drop=None, pending_site=0,
+                         adrop=None):
         """pending_site: the dropout site of the sub-layer that produced `pending` (the previous block's feed-forward)"""
-        h, pending, position_bias = self.self_attention_layer.forward_deferred(h, pending, position_bias, packing, drop, pending_site)
+        h, pending, position_bias = self.self_attention_layer.forward_deferred(h, pending, position_bias, packing, drop, pending_site, adrop)
         pending_site = self.self_attention_layer.site
         if self.is_decoder and encoder_hidden_states is not None:
-            h, pending = self.cross_attention_layer.forward_deferred(h, pending, encoder_hidden_states, packing, drop, pending_site)
+            h, pending = self.cross_attention_layer.forward_deferred(h, pending, encoder_hidden_states, packing, drop, pending_site, adrop)
             pending_site = self.cross_attention_layer.site
         h, pending = self.ff_layer.forward_deferred(h, pending, drop, pending_site)
         return h, pending, position_bias
@@ -314,10 +330,11 @@ class FAT5Stack(nn.Module):  # :394-464
         self.site_final = site
         self.next_site = site + 1
 
-    def forward(self, input_ids, encoder_hidden_states=None, packing=None, drop=None):
+    def forward(self, input_ids, encoder_hidden_states=None, packing=None, drop=None, adrop=None):
         """packing (packing.Packed): input_ids are the (1, total) valid tokens of a padded or packed batch, every attention layer
         runs over cu_seqlens, and the output stays (1, total, d_model).  drop (_Drop): a training forward with dropout; None (what
-        every caller but the training loss passes) runs the code below as it always ran"""
+        every caller but the training loss passes) runs the code below as it always ran.  adrop: the attention layers' dropout context
+        (a training forward with attention_dropout_rate > 0), independent of `drop`"""
         h = self.embed_tokens(input_ids)
         if torch.is_autocast_enabled() and h.is_cuda:  # :424-425
             h = h.to(torch.get_autocast_gpu_dtype())
@@ -327,25 +344,25 @@ class FAT5Stack(nn.Module):  # :394-464
             if self.fuse_add_norm:
                 pending, pending_site = None, 0
                 for blk in self.block:
-                    h, pending, position_bias = blk.forward_deferred(h, pending, position_bias, encoder_hidden_states, packing, drop, pending_site)
+                    h, pending, position_bias = blk.forward_deferred(h, pending, position_bias, encoder_hidden_states, packing, drop, pending_site, adrop)
                     pending_site = blk.ff_layer.site
                 h = _pre_norm(self.final_layer_norm, h, pending, drop, pending_site)[1]
             else:
                 for blk in self.block:
-                    h, position_bias = blk(h, position_bias, encoder_hidden_states, packing, drop)
+                    h, position_bias = blk(h, position_bias, encoder_hidden_states, packing, drop, adrop)
                 h = self.final_layer_norm(h)
             return drop(h, self.site_final)  # :460
         if self.fuse_norm_linear and h.dtype in (torch.float16, torch.bfloat16):
             for blk in self.block:
-                h, position_bias = blk.forward_fused(h, position_bias, encoder_hidden_states, packing)
+                h, position_bias = blk.forward_fused(h, position_bias, encoder_hidden_states, packing, adrop)
             return self.final_layer_norm(h)
         if self.fuse_add_norm:
             pending = None  # the last sub-layer's output: its residual add happens inside the next pre-norm
             for blk in self.block:
-                h, pending, position_bias = blk.forward_deferred(h, pending, position_bias, encoder_hidden_states, packing)
+                h, pending, position_bias = blk.forward_deferred(h, pending, position_bias, encoder_hidden_states, packing, adrop=adrop)
             return _pre_norm(self.final_layer_norm, h, pending)[1]
         for blk in self.block:
-            h, position_bias = blk(h, position_bias, encoder_hidden_states, packing)
+            h, position_bias = blk(h, position_bias, encoder_hidden_states, packing, adrop=adrop)
         return self.final_layer_norm(h)
 
 
@@ -392,23 +409,35 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         # dropout: the step counter is a buffer outside the state dict (reference checkpoints load strictly); a
         # dropout_rate of 0 builds nothing and draws nothing
         self.dropout_seed = config.dropout_seed
-        if config.dropout_rate > 0:
+        if config.dropout_rate > 0 or config.attention_dropout_rate > 0:
             if self.dropout_seed is None:
                 self.dropout_seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64))
             self.register_buffer("dropout_step", torch.zeros(1, dtype=torch.int64), persistent=False)
+        # attention dropout: its E + 2 D sites are numbered AFTER the row-wise ones, so none of those moves
+        site = self.decoder.next_site
+        for blk in self.encoder.block:
+            blk.self_attention_layer.self_attention.attn_site = site
+            site += 1
+        for blk in self.decoder.block:
+            blk.self_attention_layer.self_attention.attn_site = site
+            blk.cross_attention_layer.cross_attention.attn_site = site + 1
+            site += 2
 
     def _drop(self):
-        """the dropout context of this forward, or None (eval, or dropout_rate 0: no new launch, today's code path).  The sites of
-        the forward and of its backward read a COPY of the step counter; the counter itself is advanced on the device right away,
-        so a captured step holds both and every replay draws new masks."""
+        """(the dropout context of this forward's row-wise sites, the one of its attention layers), each None when it has nothing
+        to do (eval, or a zero rate: no new launch, today's code path).  The sites of the forward and of its backward read ONE COPY
+        of the step counter; the counter itself is advanced on the device right away, so a captured step holds both and every
+        replay draws new masks."""
         c = self.config
-        if not (self.training and c.dropout_rate > 0):
-            return None
+        if not (self.training and (c.dropout_rate > 0 or c.attention_dropout_rate > 0)):
+            return None, None
         from .dropout import rank_key
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        key = rank_key(self.dropout_seed, rank)
         step = self.dropout_step.clone()
         self.dropout_step.add_(1)
-        return _Drop(float(c.dropout_rate), rank_key(self.dropout_seed, rank), step)
+        return (_Drop(float(c.dropout_rate), key, step) if c.dropout_rate > 0 else None,
+                (key, step) if c.attention_dropout_rate > 0 else None)
 
     @torch.no_grad()
     def reset_parameters(self):
@@ -454,9 +483,9 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         (a `_plan` result; any model with this vocabulary can run over another's plan), or over the whole batch when it is None"""
         if packed is not None:
             return self._packed_states(*packed)
-        drop = self._drop()
-        enc = self.encoder(input_ids, drop=drop)
-        dec = self.decoder(self._shift_right(labels), encoder_hidden_states=enc, drop=drop)
+        drop, adrop = self._drop()
+        enc = self.encoder(input_ids, drop=drop, adrop=adrop)
+        dec = self.decoder(self._shift_right(labels), encoder_hidden_states=enc, drop=drop, adrop=adrop)
         return dec, labels
 
     def _loss(self, dec, labels):
@@ -533,10 +562,10 @@ class FAT5ForConditionalGeneration(nn.Module):  # :604-736 (training forward; ca
         shifted = torch.cat([lab.new_full((1,), c.decoder_start_token_id), lab[:-1]])
         shifted.index_fill_(0, dp.cu_seqlens[:-1].long(), c.decoder_start_token_id)
         shifted = shifted.masked_fill(shifted == -100, c.pad_token_id).unsqueeze(0)
-        drop = self._drop()   # (the masks index the packed (total, d_model) rows)
-        enc = self.encoder(ids, packing=Packed(ep.cu_seqlens, ep.max_seqlen), drop=drop)
+        drop, adrop = self._drop()   # (the masks index the packed (total, d_model) rows)
+        enc = self.encoder(ids, packing=Packed(ep.cu_seqlens, ep.max_seqlen), drop=drop, adrop=adrop)
         dec = self.decoder(shifted, encoder_hidden_states=enc,
-                           packing=Packed(dp.cu_seqlens, dp.max_seqlen, ep.cu_seqlens, ep.max_seqlen), drop=drop)
+                           packing=Packed(dp.cu_seqlens, dp.max_seqlen, ep.cu_seqlens, ep.max_seqlen), drop=drop, adrop=adrop)
         return dec, lab.unsqueeze(0)
 
     def init_decode_state(self, input_ids, max_length=32, attention_mask=None, prompt_length=1, kv_cache_dtype=None, weight_dtype=None,

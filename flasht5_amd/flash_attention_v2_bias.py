@@ -452,13 +452,19 @@ class FlashAttentionRPE1D(torch.autograd.Function):
 
 
 def flash_attention_v2_rpe1d(q, k, v, rpe1d, radius, causal=False, sm_scale=None, window=None, global_kv=None, global_rpe1d=None,
-                             global_radius=None):
+                             global_radius=None, dropout_p=0.0, dropout_seed=None, dropout_step=None, dropout_site=0):
     """Attention with the Toeplitz bias generated in-kernel from `rpe1d (H, 2*radius+1)` (see FlashAttentionRPE1D).
+    dropout_p > 0: dropout on the attention weights (`FlashAttentionDropout`: head_dim 64, rpe1d may be None) with the Philox key
+    dropout_seed, the int64 one-element device tensor dropout_step and the site number dropout_site; 0 runs today's code.
     window: None, or w >= 1 for local attention -- key n visible to row m iff |n - m| <= w (self-attention, head_dim 64, not
     causal; `FlashAttentionLocal`).  With a window, rpe1d may be None: no bias.
     global_kv=(gk, gv), each (B, H, S // 16, 64): LongT5's transient-global attention (`FlashAttentionTGlobal`) -- every row also
     attends to the S // 16 global keys under the same softmax, with `global_rpe1d (H, 2*global_radius+1)` indexed by the block
     distance g - min(m // 16, S // 16 - 1).  Needs window=; both tables or neither."""
+    if _dropout_on(dropout_p, window, global_kv, global_rpe1d, global_radius):
+        _check_inputs(q, k, v)
+        return FlashAttentionDropout.apply(q, k, v, rpe1d, int(radius), bool(causal), sm_scale, None, None, None, None, float(dropout_p),
+                                           dropout_seed, dropout_step, int(dropout_site))[0]
     if global_kv is not None or global_rpe1d is not None or global_radius is not None:
         window, Rg = _check_tglobal(q, k, v, window, causal, global_kv, rpe1d, global_rpe1d, global_radius)
         _check_inputs(q, k, v)
@@ -659,13 +665,20 @@ class FlashAttentionVarlen(torch.autograd.Function):
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=False, sm_scale=None,
-                           rpe1d=None, radius=0, window=None, global_kv=None, global_rpe1d=None, global_radius=None, cu_seqlens_g=None):
+                           rpe1d=None, radius=0, window=None, global_kv=None, global_rpe1d=None, global_radius=None, cu_seqlens_g=None,
+                           dropout_p=0.0, dropout_seed=None, dropout_step=None, dropout_site=0):
     """Differentiable packed attention (argument order of the flash_attn var-len entry point the reference's `fa2`
     attention types would call), optionally with the in-kernel T5 bias of `flash_attention_v2_rpe1d`.
+    dropout_p > 0: dropout on the attention weights as in `flash_attention_v2_rpe1d` (b of the mask is the sequence's index).
     window: None, or w >= 1 for local attention inside each sequence (self-attention, head_dim 64, not causal).  The local
     kernel reads cu_seqlens_q only: cu_seqlens_k / max_seqlen_k must be the query's.
     global_kv=(gk, gv), each (total_g, H, 64), with cu_seqlens_g (nseq + 1,) int32, cu_seqlens_g[b] = sum over j < b of L_j // 16:
     transient-global attention inside each sequence (see `flash_attention_v2_rpe1d`); total_g = total // 16 always suffices."""
+    if _dropout_on(dropout_p, window, global_kv, global_rpe1d, global_radius, cu_seqlens_g):
+        _check_varlen(q, k, v, _as_cu(cu_seqlens_q, q.device), _as_cu(cu_seqlens_k, q.device), None, 0)
+        return FlashAttentionDropout.apply(q, k, v, rpe1d, int(radius), bool(causal), sm_scale, _as_cu(cu_seqlens_q, q.device),
+                                           _as_cu(cu_seqlens_k, q.device), int(max_seqlen_q), int(max_seqlen_k), float(dropout_p),
+                                           dropout_seed, dropout_step, int(dropout_site))[0]
     if global_kv is not None or global_rpe1d is not None or global_radius is not None or cu_seqlens_g is not None:
         if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
             raise ValueError("packed attention takes q (total_q, H, D) and k, v (total_k, H, D)")
@@ -793,6 +806,120 @@ class FlashAttentionLocal(torch.autograd.Function):
             p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
             _lib.check(lib.fat5_attn_local_bwd(ctypes.byref(p), _lib.stream_ptr(q.device)), "fat5_attn_local_bwd")
         return dq, dk, dv, (d1.to(rdtype) if d1 is not None else None), None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# dropout on the attention weights: a kernel family of its own, Philox masks recomputed in-kernel (csrc/attn_dropout_kernels.h)
+# ------------------------------------------------------------------------------------------------
+def _dropout_on(p, window=None, *others):
+    """whether a call asks for attention dropout (p > 0); ValueError for a p outside [0, 1), NotImplementedError with window= or
+    the transient-global arguments, before any tensor is looked at"""
+    p = float(p)
+    if not 0.0 <= p < 1.0:   # (NaN fails both comparisons)
+        raise ValueError(f"dropout_p = {p} outside [0, 1)")
+    if p == 0.0:
+        return False
+    if window is not None or any(o is not None for o in others):
+        raise NotImplementedError("dropout_p > 0 with window= / global_kv=: the local and transient-global kernels carry no dropout")
+    return True
+
+
+def _adrop_params(ts, names, causal, sm_scale, r1, radius, cu_q, cu_k, max_q, max_k, p, seed, step, site):
+    q, k = ts[0], ts[1]
+    d = _lib.AttnDropoutParams()
+    if cu_q is None:
+        d.B, d.H, d.M, d.D = q.shape
+        d.N = k.shape[2]
+        strides = _lib.strides3
+    else:
+        d.B, d.H, d.M, d.N, d.D = cu_q.numel() - 1, q.shape[1], int(max_q), int(max_k), q.shape[2]
+        d.total_q, d.total_k = q.shape[0], k.shape[0]
+        d.cu_seqlens_q, d.cu_seqlens_k = cu_q.data_ptr(), cu_k.data_ptr()
+        strides = lambda t: _lib.c_i64x3(0, t.stride(1), t.stride(0))  # noqa: E731
+    d.dtype, d.causal, d.sm_scale = _lib.dtype_code(q.dtype), int(bool(causal)), float(sm_scale)
+    for name, t in zip(names, ts):
+        setattr(d, name, t.data_ptr())
+        setattr(d, ("do" if name == "dout" else name) + "_stride", strides(t))
+    if r1 is not None:
+        d.bias_mode, d.rpe1d, d.rpe_radius = _lib.BIAS_RPE1D, r1.data_ptr(), int(radius)
+    d.seed, d.step, d.site, d.p = int(seed) & ((1 << 64) - 1), step.data_ptr(), int(site), float(p)
+    return d
+
+
+class FlashAttentionDropout(torch.autograd.Function):
+    """o = dropout(softmax(scale q k^T + bias), p) v over the ctypes ABI (`fat5_attn_dropout_fwd` / `_bwd`): dense (B, H, S, 64)
+    views or packed (total, H, 64) tensors with cu_seqlens_q / cu_seqlens_k, causal or not, rpe1d (H, 2*radius+1) or None;
+    differentiable in q, k, v and rpe1d.  The mask is a function of (seed, step, site, b, h, m, n) stated in
+    csrc/attn_dropout_kernels.h and is regenerated in the backward: `step`, an int64 one-element device tensor, is SAVED as a
+    tensor and read on the device, so a captured step draws new masks at every replay.  Eager and HIP-graph capture; the C++
+    binding and the traced custom ops do not carry dropout."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rpe1d, radius, causal, sm_scale, cu_q, cu_k, max_q, max_k, p, seed, step, site):
+        packed = cu_q is not None
+        if not q.is_cuda:
+            raise RuntimeError("flasht5_amd attention needs tensors on the HIP device (no CPU fallback)")
+        if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+            raise TypeError("q, k, v must share dtype float16 or bfloat16")
+        if q.shape[-1] != 64:
+            raise ValueError(f"dropout_p > 0 needs head_dim 64, got {q.shape[-1]}")
+        if seed is None:
+            raise ValueError("dropout_p > 0 needs dropout_seed (the Philox key)")
+        if not torch.is_tensor(step) or step.dtype != torch.int64 or step.numel() != 1 or step.device != q.device:
+            raise ValueError("dropout_p > 0 needs dropout_step: an int64 tensor of one element on q's device (the kernels read it there)")
+        H = q.shape[1]
+        nunits = (cu_q.numel() - 1 if packed else q.shape[0]) * H
+        if nunits > (1 << 20) or not 0 <= int(site) < (1 << 12):
+            raise ValueError(f"dropout_p > 0: (batch rows or sequences) * heads = {nunits} must not exceed 2^20 and dropout_site = {site} "
+                             "must lie in [0, 2^12): the mask counter's layout")
+        if sm_scale is None:
+            sm_scale = 1.0 / math.sqrt(q.shape[-1])
+        r1 = None
+        if rpe1d is not None:
+            if radius > _lib.MAX_RPE_RADIUS:
+                raise ValueError(f"radius {radius} exceeds the RPE-mode limit {_lib.MAX_RPE_RADIUS}")
+            r1 = rpe1d.detach().float().contiguous()
+            _check_rpe1d(r1, H, radius, q.device)
+        q, k, v = (_local_ready(t, packed) for t in (q, k, v))
+        o = _local_like(q)
+        lse = torch.empty((H, q.shape[0]) if packed else (q.shape[0], H, q.shape[2]), dtype=torch.float32, device=q.device)
+        d = _adrop_params((q, k, v, o), ("q", "k", "v", "o"), causal, sm_scale, r1, radius, cu_q, cu_k, max_q, max_k, p, seed, step, site)
+        d.lse = lse.data_ptr()
+        with _lib.on_device(q.device):
+            _lib.check(_lib.load().fat5_attn_dropout_fwd(ctypes.byref(d), _lib.stream_ptr(q.device)), "fat5_attn_dropout_fwd")
+        ctx.save_for_backward(q, k, v, o, lse, step, *([cu_q, cu_k] if packed else []), *([r1] if r1 is not None else []))
+        ctx.meta = (packed, r1 is not None, int(radius), bool(causal), sm_scale, max_q, max_k, float(p), int(seed), int(site),
+                    rpe1d.dtype if rpe1d is not None else None)
+        ctx.mark_non_differentiable(lse)
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, do, _dlse):
+        packed, has_bias, radius, causal, sm_scale, max_q, max_k, p, seed, site, rdtype = ctx.meta
+        q, k, v, o, lse, step, *rest = ctx.saved_tensors
+        cu_q, cu_k = (rest.pop(0), rest.pop(0)) if packed else (None, None)
+        r1 = rest.pop(0) if has_bias else None
+        do = _local_ready(do, packed)
+        # gradients of one stacked projection (q | k | v, or the k | v of cross-attention): slices of one buffer, as in _attn_bwd
+        if not packed and q.shape == k.shape and packed_slices((q, k, v)):
+            dq, dk, dv = empty_packed_like((q, k, v))
+        elif not packed and packed_slices((k, v)):
+            dq, (dk, dv) = _local_like(q), empty_packed_like((k, v))
+        else:
+            dq, dk, dv = _local_like(q), _local_like(k), _local_like(v)
+        d = _adrop_params((q, k, v, o, do, dq, dk, dv), ("q", "k", "v", "o", "dout", "dq", "dk", "dv"), causal, sm_scale, r1, radius,
+                          cu_q, cu_k, max_q, max_k, p, seed, step, site)
+        d.lse = lse.data_ptr()
+        d1 = None
+        if has_bias and ctx.needs_input_grad[3]:
+            d1 = torch.empty_like(r1)
+            d.drpe1d = d1.data_ptr()
+        lib = _lib.load()
+        with _lib.on_device(q.device):
+            ws = _workspace(lib.fat5_attn_dropout_bwd_workspace_bytes(ctypes.byref(d)), q.device)
+            d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+            _lib.check(lib.fat5_attn_dropout_bwd(ctypes.byref(d), _lib.stream_ptr(q.device)), "fat5_attn_dropout_bwd")
+        return (dq, dk, dv, (d1.to(rdtype) if d1 is not None else None)) + (None,) * 11
 
 
 # ------------------------------------------------------------------------------------------------

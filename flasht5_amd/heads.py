@@ -71,6 +71,9 @@ class _EncoderOnly(nn.Module):
 
     def __init__(self, config: FAT5Config):
         super().__init__()
+        if config.attention_dropout_rate > 0:
+            raise ValueError("attention_dropout_rate > 0 is wired into FAT5ForConditionalGeneration only: the encoder-only models "
+                             "number no attention sites")
         self.config = config
         self.shared = nn.Embedding(config.vocab_size, config.d_model)
         enc = copy.copy(config)

@@ -1615,6 +1615,73 @@ size_t fat5_attn_tglobal_bwd_workspace_bytes(const fat5_tglobal_attn_params* p);
 /* backward: reads q, k, v, gk, gv, o, lse, dout (and the tables); writes dq, dk, dv, dgk, dgv (and the table gradients) */
 int fat5_attn_tglobal_bwd(const fat5_tglobal_attn_params* p, void* hip_stream);
 
+/*
+ * Attention with dropout on the attention weights (attn_dropout_kernels.h) -- a kernel family of its own, for p > 0.
+ *
+ *   S = q k^T * sm_scale + bias,  P = softmax(S) (with `causal` bottom-right aligned: key n visible to query m iff n <= m + N - M),
+ *   P~ = round_to_dtype(fp32(P) * s) where kept, +0 where dropped, s = 1.0f / (1.0f - p);  o = P~ v;  lse: the log-sum-exp of the
+ *   UNDROPPED row (natural log, fp32).  A row that sees no key gives o = 0, lse = -inf.
+ *   bias: FAT5_BIAS_NONE, or FAT5_BIAS_RPE1D, rpe1d[h][clamp(n - m, -R, R) + R].
+ *
+ * The mask, for query m and key n (positions inside the sequence) of head h of batch row / packed sequence b:
+ *   w = Philox4x32-10(key = (seed lo, seed hi ^ 0x80000000), counter = (n >> 2, m, (site << 20) | (b * H + h), step mod 2^32));
+ *   the element is kept iff (w[n & 3] >> 8) * 2^-24 >= p, the rule of fat5_dropout_desc.  The flipped key bit keeps the stream
+ *   disjoint from every fat5_dropout_desc site under the same seed.  `step` is read on the device (a captured launch draws a new
+ *   mask at every replay once the caller advances the counter); nothing of size M x N is stored, the backward regenerates the mask.
+ *
+ * D = 64; FAT5_F16 / FAT5_BF16 with fp32 accumulation; M != N allowed.  Layouts as in fat5_local_attn_params: dense (B, H, S, D)
+ * views with element strides [b, h, s], lse (B, H, M); packed (total, H, D) tensors with cu_seqlens_q / cu_seqlens_k (B + 1,)
+ * int32 on the device (both or neither; zero-length sequences allowed), M / N the longest sequences, lse (H, total_q).
+ *
+ * Backward: dS = P o (keep dP s - delta), delta = rowsum(dO o O), dV = P~^T dO, dQ = sm_scale dS K, dK = sm_scale dS^T Q; drpe1d
+ * (H, 2R+1) fp32, overwritten (may be NULL): the sum of dS[m][n] at entry clamp(n - m, -R, R) + R.  No atomics: the same bits on
+ * every run.  Launches: dQ (with delta and the partial diagonal sums), dK / dV, the fixed-order sum of the partial rows.
+ *
+ * Rejected with FAT5_EINVAL before anything is launched: NULL params, D other than 64, a dtype outside {FAT5_F16, FAT5_BF16},
+ * p outside [0, 1) (NaN included), FAT5_BIAS_DENSE or an unknown bias_mode, B or H outside [1, 65535], M or N outside [1, 2^30),
+ * B * H > 2^20, site >= 2^12, rpe_radius outside [1, 1024], one cu_seqlens without the other, a packed batch without tokens,
+ * NULL or misaligned pointers (step included), strides that are no multiples of 8 elements; FAT5_EWORKSPACE when the workspace is
+ * missing, misaligned or too small.
+ */
+typedef struct fat5_attn_dropout_params {
+  int32_t B, H, M, N, D;
+  int32_t dtype;            /* FAT5_F16 | FAT5_BF16: q, k, v, o, dout, dq, dk, dv */
+  int32_t bias_mode;        /* FAT5_BIAS_NONE | FAT5_BIAS_RPE1D */
+  int32_t causal;           /* 0 | 1 */
+  int32_t rpe_radius;       /* R of FAT5_BIAS_RPE1D: 1..1024 */
+  float sm_scale;
+  int32_t total_q, total_k; /* packed: tokens of the batch on each side */
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  float* lse;
+  int64_t q_stride[3], k_stride[3], v_stride[3], o_stride[3];
+  const float* rpe1d;       /* (H, 2R+1) fp32 contiguous */
+  const int32_t* cu_seqlens_q; /* packed: (B + 1,) int32 on the device; NULL: dense */
+  const int32_t* cu_seqlens_k;
+  /* ---- the mask ---- */
+  uint64_t seed;
+  const int64_t* step;      /* DEVICE pointer to the step counter (8-byte aligned); its low 32 bits enter the counter */
+  uint32_t site;            /* < 2^12 */
+  float p;                  /* drop probability, 0 <= p < 1 */
+  /* ---- backward (ignored by the forward) ---- */
+  const void* dout;
+  void* dq;
+  void* dk;
+  void* dv;
+  int64_t do_stride[3], dq_stride[3], dk_stride[3], dv_stride[3];
+  float* drpe1d;
+  void* workspace;
+  size_t workspace_bytes;
+} fat5_attn_dropout_params;
+size_t fat5_sizeof_attn_dropout_params(void);
+/* forward: writes o, lse */
+int fat5_attn_dropout_fwd(const fat5_attn_dropout_params* p, void* hip_stream);
+size_t fat5_attn_dropout_bwd_workspace_bytes(const fat5_attn_dropout_params* p);
+/* backward: reads q, k, v, o, lse, dout (, rpe1d); writes dq, dk, dv (, drpe1d) */
+int fat5_attn_dropout_bwd(const fat5_attn_dropout_params* p, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
